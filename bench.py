@@ -7,6 +7,13 @@ the hot path over one stereo pair per GPU (pairs shard one per GPU, SURVEY.md
 section 8e), inputs already resident in HBM, followed by the RCCL gather of
 the disparity maps to rank 0 when N > 1.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line.
+``--dump-outputs DIR`` also writes the last timed step's disparity map to
+DIR/disparity.npy (float32; the inputs are the same in every run, so two
+builds can be compared map for map).  ``--full`` adds what takes runs of its
+own: the per-kernel profile pass behind `roofline` / `kernels` and the CPU
+baseline (`cpu_baseline`); without it those fields are null / empty.
+
 Metric (BASELINE.json): V*W*H*D / t in Mpixel-disparities/s, V = views
 aggregated.  Default workload = BASELINE.json configs[1] ("config 2"):
 1242x375, D=128, census 9x7 + 8-path SGM + WTA, left view (V=1).
@@ -15,7 +22,7 @@ roofline: the dominant kernel (largest share of the per-step kernel time),
 its algorithmic bytes per launch (DESIGN.md "Roofline") over its average
 launch duration, measured with HIP events recorded by libsgm_hip.so around
 every launch on the stream that launch runs on (sgm_set_profiling), in a
-second pass of the same K steps right after the timed region.
+second pass of the same K steps right after the timed region (--full).
 """
 from __future__ import annotations
 
@@ -179,13 +186,20 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="k128", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel profile pass (roofline, kernels) and the CPU "
+                         "baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's disparity map to DIR/disparity.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=3,
                     help="minimum samples of the CPU baseline (median reported); sampling goes on "
                          "until --cpu-seconds of CPU work have run (at most 12 samples)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="CPU work the baseline sample spans (the contract asks for ~10-30 s)")
-    ap.add_argument("--no-profile-pass", action="store_true")
+    ap.add_argument("--no-profile-pass", action="store_true",
+                    help="--full without the per-kernel profile pass")
     ap.add_argument("--post-filter", action="store_true",
                     help="end each step with post_filter() on the GPU (SGM.cpp:821; V=2 configs)")
     ap.add_argument("--lk-refine", action="store_true",
@@ -211,7 +225,10 @@ def parse():
                          "optional split; a latency option, not the default sharding)")
     ap.add_argument("--host-io", action="store_true",
                     help="also time sgm_process on host buffers (PCIe-inclusive, not `value`)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
@@ -255,6 +272,7 @@ def main():
         from stereo_matching_amd.distributed import PipelinedGather
         pipe = PipelinedGather((gk, h, w) if gk > 1 else (h, w), torch.float32, dev, depth=2)
     nstep = [0]
+    last_out = [d_out]  # the map the latest step wrote (--dump-outputs)
     verified = []
 
     if cfg.get("full"):
@@ -314,6 +332,7 @@ def main():
             out = out[nstep[0] % gk] if gk > 1 else out
         sgm.process_device(d_left.data_ptr(), d_right.data_ptr(), out.data_ptr(),
                            stream=stream.cuda_stream)
+        last_out[0] = out
         nstep[0] += 1
         if pipe and nstep[0] % gk == 0:
             pipe.submit()
@@ -367,6 +386,13 @@ def main():
 
     elapsed = timed_steps(args.steps)
     verify("timed")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the disparity map of the
+        # last timed step (this rank's own pair), before any later pass
+        # overwrites it
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "disparity.npy"),
+                last_out[0].detach().to("cpu", torch.float32).numpy())
     rank_min = rank_max = elapsed
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -384,7 +410,7 @@ def main():
     # per-kernel durations: HIP events around every launch, same K steps
     roofline = None
     kernels = {}
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         sgm.set_profiling(True)
         step = eager_step
         prof_elapsed = timed_steps(args.steps)
@@ -535,7 +561,7 @@ def main():
     if world > 1:
         cpu_note = ("measured on rank 0 at N=1 only (bench contract); the N=1 line of the same "
                     "config carries it")
-    elif rank == 0 and not args.no_cpu_baseline:
+    elif rank == 0 and args.full and not args.no_cpu_baseline:
         import oracle
         oracle.build()
         # every host thread this process may use: OMP_NUM_THREADS when the

@@ -276,7 +276,7 @@ def test_bench_under_torch_distributed_run(extra):
     # on a caller's stream)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", _port(), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-profile-pass"] + extra
+           "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-profile-pass"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-4000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]

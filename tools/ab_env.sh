@@ -7,7 +7,7 @@ CFG=$1; REPS=$2; VAR=$3; shift 3
 mkdir -p gpurun_out
 for r in $(seq 1 $REPS); do
   for X in "$@"; do
-    env $VAR=$X timeout -k 10 180 python bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline \
+    env $VAR=$X timeout -k 10 180 python bench.py --full --config $CFG --steps 10 --warmup 3 --no-cpu-baseline \
       > gpurun_out/ab_last.json 2>> gpurun_out/ab.err || { echo "bench failed for $VAR=$X"; tail -20 gpurun_out/ab.err; exit 1; }
     python -c "
 import json; r=json.loads(open('gpurun_out/ab_last.json').read().strip().splitlines()[-1])

@@ -10,9 +10,11 @@ for part in "$@"; do
   case $part in
   bench)
     for c in k128 k64 k128lr k128full hd256 4k256 4k256full; do
-      timeout -k 10 300 python bench.py --config $c > gpurun_out/${TAG}_bench_$c.json 2>> gpurun_out/${TAG}_bench.err || { echo "bench $c failed"; tail -20 gpurun_out/${TAG}_bench.err; exit 1; }
+      # the bench lines (with --full: roofline and CPU baseline) go to $OUT
+      OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+      timeout -k 10 300 python bench.py --full --config $c > $OUT/${TAG}_bench_$c.json 2>> $OUT/${TAG}_bench.err || { echo "bench $c failed"; tail -20 $OUT/${TAG}_bench.err; exit 1; }
       python -c "
-import json; r=json.loads(open('gpurun_out/${TAG}_bench_$c.json').read().strip().splitlines()[-1])
+import json; r=json.loads(open('$OUT/${TAG}_bench_$c.json').read().strip().splitlines()[-1])
 print('$c', r['value'], 'MPD/s', r['ms_per_step'], 'ms', 'roof', r['roofline']['kernel'], r['roofline']['frac'], 'cpu', (r['cpu_baseline'] or {}).get('value'))"
     done ;;
   prof)

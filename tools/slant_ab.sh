@@ -5,7 +5,7 @@ TAG=${1:-ab}
 shift
 for c in ${@:-hd256 4k256}; do
   for m in 0 1; do
-    SGM_SLANT=$m timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline \
+    SGM_SLANT=$m timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline \
       > gpurun_out/${TAG}_${c}_slant$m.json 2> gpurun_out/${TAG}_${c}_slant$m.err || exit 1
     python3 -c "
 import json; r=json.load(open('gpurun_out/${TAG}_${c}_slant$m.json'))

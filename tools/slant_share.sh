@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 $REPS); do
   for e in $SHARES; do
     SGM_HIP_LIB=stereo_matching_amd/libsgm_hip_slantdbg.so SGM_SLANT_DOWN_EIGHTHS=$e \
-      timeout -k 10 120 python bench.py --config $CFG --steps 20 --warmup 5 --no-cpu-baseline \
+      timeout -k 10 120 python bench.py --full --config $CFG --steps 20 --warmup 5 --no-cpu-baseline \
       > gpurun_out/share_last.json 2>> gpurun_out/share.err || { echo "bench failed ($e)"; tail -20 gpurun_out/share.err; exit 1; }
     python -c "
 import json; r=json.loads(open('gpurun_out/share_last.json').read().strip().splitlines()[-1]); k=r['kernels']
