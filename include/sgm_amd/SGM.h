@@ -9,6 +9,7 @@
  *
  *   SGM(h, w, s, d)              Solver.cpp:4-16   (asserts: h,w,s,d > 0,
  *                                s in {1,2}, d in {32,64,128} -- widened to 256)
+ *   SGM(h, w, s, d, paths)       inc/SGM.h:7        (paths = 4: USE_8_PATH = false; 8: as above)
  *   process(l, r)                SGM.cpp:32-826     (LR-checked, post-filtered)
  *   process(l, r, sky, sky_b)    SGM.cpp:829-834    (masks kept as members)
  *   BM(h, w, s, d)               BM.cpp:4-97        (filtered-cost WTA, post-filtered)
@@ -248,11 +249,14 @@ public:
 
 protected:
     // views = 1: the left view alone (BM; GPU_SGM, gpu_sgm/src/SGM.cu:105-232)
-    HipSolver(int h, int w, int s, int d, int solver, int views = 2)
+    // paths = 4: the reference built with USE_8_PATH = false (inc/SGM.h:7)
+    HipSolver(int h, int w, int s, int d, int solver, int views = 2, int paths = 8)
         : Solver(h, w, s, d), bm_(solver == SGM_SOLVER_BM) {
+        if (paths != 4 && paths != 8) fail("Solver", "paths must be 4 or 8 (USE_8_PATH, inc/SGM.h:7)");
         sgm_params p;
         if (sgm_default_params(&p, h, w, s, d) != SGM_OK) fail("Solver", "sgm_default_params");
         p.solver = solver;
+        p.paths = paths;
         p.post_filter = 1;  // process() ends with post_filter(): SGM.cpp:821, BM.cpp:88 (on the GPU)
         p.views = bm_ ? 1 : views;
         const int rc = sgm_create(&p, device(), &handle_);
@@ -290,6 +294,8 @@ private:
 class SGM : public HipSolver {
 public:
     explicit SGM(int h, int w, int s, int d) : HipSolver(h, w, s, d, SGM_SOLVER_SGM) {}
+    // paths = 4: the reference's USE_8_PATH = false (inc/SGM.h:7), S = ((L1+L2)+L3)+L4
+    SGM(int h, int w, int s, int d, int paths) : HipSolver(h, w, s, d, SGM_SOLVER_SGM, 2, paths) {}
     SGM(const SGM &) = delete;
     SGM &operator=(const SGM &) = delete;
 };

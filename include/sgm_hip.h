@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define SGM_HIP_VERSION 1
+#define SGM_HIP_VERSION 2  /* 2: sgm_params ends with `paths` */
 
 /* Status codes (the reference only asserts, Solver.cpp:6-10; GPU errors were
  * printed and ignored, gpu_sgm/inc/cuda_inc.cuh:4-9 -- here they are returned). */
@@ -114,6 +114,15 @@ typedef struct sgm_params {
                           A right-view handle has no post_filter/lk_refine (they follow the
                           LR check on the left view's GPU) and uses sky_r (or the right image's
                           detected mask) */
+    int paths;         /* aggregation paths per view: 8 (default; 0 means 8, so zero-initialised
+                          structs keep working) or 4, the reference's USE_8_PATH = false
+                          (inc/SGM.h:7): SGM.cpp:15,241,387-390,619,765,847 drop L5..L8 and
+                          S = ((L1+L2)+L3)+L4 goes straight into WTA, uniqueness, sub-pixel and
+                          the LR check.  Any other value: sgm_create returns
+                          SGM_ERR_INVALID_ARG.  A 4-path handle holds no diagonal checkpoints,
+                          band carries or slanted-tile buffers and always runs whole-volume
+                          passes (SGM_SLANT and SGM_BAND_ROWS are ignored).  BM and aux_only
+                          handles ignore the field */
 } sgm_params;
 
 enum { SGM_VIEW_LEFT = 0, SGM_VIEW_RIGHT = 1 };
@@ -337,9 +346,11 @@ int sgm_stage_census(sgm_handle *h, const uint8_t *img, int pitch, uint64_t *ct)
 int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr,
                    const uint8_t *sky, int view, int filters, float *cost);
 /* One path DP over a cost volume (SGM.cpp:81-369): L (rows x cols x D) and
- * minL (rows x cols). */
+ * minL (rows x cols).  A 4-path handle (params.paths == 4) serves L1..L4 and
+ * returns SGM_ERR_INVALID_ARG for L5..L8. */
 int sgm_stage_path(sgm_handle *h, int dir, const float *cost, float *L, float *minL);
-/* 8 paths + aggregation + WTA + uniqueness + sub-pixel (SGM.cpp:81-443). */
+/* 8 paths (4 with params.paths == 4: ((L1+L2)+L3)+L4) + aggregation + WTA +
+ * uniqueness + sub-pixel (SGM.cpp:81-443). */
 int sgm_stage_aggregate(sgm_handle *h, const float *cost, uint16_t *disp, float *sub);
 /* LR check (SGM.cpp:803-818): out = checked copy of fl. */
 int sgm_stage_lr(sgm_handle *h, const float *fl, const float *fr, float *out);

@@ -55,6 +55,7 @@ class Params(ctypes.Structure):
         ("lk_refine", ctypes.c_int), ("sky_detect", ctypes.c_int),
         ("solver", ctypes.c_int), ("aux_only", ctypes.c_int),
         ("view", ctypes.c_int),
+        ("paths", ctypes.c_int),
     ]
 
 

@@ -689,8 +689,11 @@ struct SplitFinalLds {
 // NB: register buffers of segment costs in the producer (NB-1 segments of
 // loads in flight while one is recomputed); RH: the consumer's ring of
 // accumulator loads is RH*K steps deep (chunks processed RH at a time).
+// NOT (FINAL, 4-path frames: no diagonal paths, so no T stream): the WTA waves
+// take X = (S12 + L3) + L4 from the LDS ring as the total (SGM.cpp:387-390
+// with USE_8_PATH off); a.acc_in is not read.
 template <int FAM, int V, bool FULL, int MODE, int K, int NB = 2, int RH = 1, int NWTA = 1,
-          bool BAND = false, bool NTC = false>
+          bool BAND = false, bool NTC = false, bool NOT = false>
 __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g, int path,
                                                 int wave, SplitLds<K, V> &L,
                                                 SplitFinalLds<K, V> *F) {
@@ -709,6 +712,7 @@ __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g
 #endif
 
     static_assert(NB == 2 || NB == 3, "producer buffers");
+    static_assert(!NOT || (MODE == PAIR_FINAL && !BAND), "4-path final pass: whole-volume only");
     static_assert(RH == 1 || RH == 2, "consumer ring halves");
     // the final pass's WTA loads reach K-1 rows above row 0 of T: the guard
     // allocated before T (t_guard_rows, sgm_capi.hip) must cover them
@@ -1029,19 +1033,43 @@ __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g
                                    s_off, cnt, lane, g.D, a.uniq, a.disp, a.sub);
             bar();
         };
-        float t0[QQ], t1[QQ], t2[QQ];
-        tload(t0, c_lo);
-        tload(t1, c_lo + 1 < c_hi ? c_lo + 1 : c_lo);
-        bar();
-        bar();
-        int c = c_lo;
-        for (; c + 2 < c_hi; c += 3) {
-            chunk(t0, t2, c);
-            chunk(t1, t0, c + 1);
-            chunk(t2, t1, c + 2);
+        if constexpr (NOT) {
+            // the ring's rows are the totals already: read this lane's share,
+            // leave the rows in place for the sub-pixel's neighbours
+            auto chunk4 = [&](int c) {
+                const int cnt_all = c == nseg - 1 ? r0 : K;
+                const int cnt = cnt_all - half * KP < 0 ? 0 : (cnt_all - half * KP > KP ? KP : cnt_all - half * KP);
+                const float *row = &F->t[c & 1][slot][d0];
+                float x[QQ];
+#pragma unroll
+                for (int k = 0; k < QQ; k += 4) {
+                    const float4 x4 = *reinterpret_cast<const float4 *>(row + k);
+                    x[k] = x4.x; x[k + 1] = x4.y; x[k + 2] = x4.z; x[k + 3] = x4.w;
+                }
+                const long long row_top = H - c * K - (half + 1) * KP;
+                wta_chunk_q<V, KP, QQ>(x, F->t[c & 1] + half * KP, row_top * W + path, o_off,
+                                       a.sub_cm ? (long long)path * H + row_top : row_top * W + path,
+                                       s_off, cnt, lane, g.D, a.uniq, a.disp, a.sub);
+                bar();
+            };
+            bar();
+            bar();
+            for (int c = c_lo; c < c_hi; ++c) chunk4(c);
+        } else {
+            float t0[QQ], t1[QQ], t2[QQ];
+            tload(t0, c_lo);
+            tload(t1, c_lo + 1 < c_hi ? c_lo + 1 : c_lo);
+            bar();
+            bar();
+            int c = c_lo;
+            for (; c + 2 < c_hi; c += 3) {
+                chunk(t0, t2, c);
+                chunk(t1, t0, c + 1);
+                chunk(t2, t1, c + 2);
+            }
+            if (c < c_hi) chunk(t0, t2, c);
+            if (c + 1 < c_hi) chunk(t1, t0, c + 1);
         }
-        if (c < c_hi) chunk(t0, t2, c);
-        if (c + 1 < c_hi) chunk(t1, t0, c + 1);
     }
 #ifdef SGM_STAMPS
     if (lane == 0) {

@@ -58,6 +58,8 @@ struct sgm_handle {
     unsigned long long *d_gran;  // slant: hand-off granules (both views)
     sgm::SlantCtl *d_slant_ctl;  // slant: launch bookkeeping of the passes
     float *d_slant_dummy;        // slant: the target of inactive lanes' stores
+    bool paths4;          // params.paths == 4: the 4-path schedule (aggregate4; no bands, no slant)
+    bool p4_split;        //   its H pair as forward + two-wave backward launches (SGM_P4_HPAIR)
     int band_rows;        // rows per band of the backward phase (0: whole volume)
     int mf_rows;          // median fill tile rows (4 or 8 by frame size; SGM_MF_ROWS)
     // post_filter scratch (sgm_post.hip)
@@ -168,6 +170,10 @@ bool valid_params(const sgm_params *p, char *why, size_t n) {
     const int H = p->height / p->scale, W = p->width / p->scale;
     if (W < 5 || H < 3) { snprintf(why, n, "working size %dx%d below the 5x3 cost window", H, W); return false; }
     if (p->views != 1 && p->views != 2) { snprintf(why, n, "views must be 1 or 2"); return false; }
+    if (p->paths != 0 && p->paths != 4 && p->paths != 8) {
+        snprintf(why, n, "paths must be 8 (or 0) or 4 (USE_8_PATH, inc/SGM.h:7)");
+        return false;
+    }
     // SGM.cpp:374-408 keeps the previous pixel's sec_min_d when a pixel has no
     // second distinct cost; that stale index decides a pixel when
     // min/FLT_MAX > UNIQUE_RATIO.  A path cost is at most C + P2 (SGM.cpp:
@@ -563,6 +569,47 @@ int aggregate_joint(sgm_handle *h, float *sub0, uint16_t *raw, int cm, hipStream
     return SGM_OK;
 }
 
+// The 4-path aggregation (params.paths == 4: the reference's USE_8_PATH off,
+// inc/SGM.h:7, SGM.cpp:387-390) of nv views, given each view's final cost
+// volume and L3 checkpoints, as whole-volume passes at every size (DESIGN.md
+// 5g):
+//   H pair: L1 fwd (ckpt), L2 bwd: S12 = L1 + L2
+//   final:  L4 bwd recomputing L3: total = (S12 + L3) + L4 -> WTA, sub-pixel
+// each with both views in one launch (per-view vfwd and final launches
+// measured +5.4% at K128, +7.5% at K64, +2.2% at HD256 on the frame).  No T
+// chain, no diagonal checkpoints, no bands, no slanted tiles.
+int aggregate4(sgm_handle *h, int nv, float *sub0, uint16_t *raw, int cm, hipStream_t st) {
+    const Geom g = h->g;
+    const double elems = (double)g.H * g.W * g.D;
+    sgm::PairArgs h1[2], h2[2], fin[2];
+    for (int v = 0; v < nv; ++v) {
+        float **ck = h->d_ck[v];
+        sgm::PairArgs pa = pair_args(h);
+        pa.cost = cost_buf(h, v);
+        h1[v] = pa;
+        h1[v].ckpt = ck[sgm::PAIR_H];
+        h2[v] = h1[v];
+        h2[v].out = h->d_s[v];
+        fin[v] = pa;
+        fin[v].ckpt = ck[sgm::PAIR_V];
+        fin[v].s_in = h->d_s[v];
+        fin[v].disp = v ? nullptr : raw;
+        fin[v].sub = v ? h->d_sub[1] : sub0;
+        fin[v].sub_cm = cm;
+    }
+    if (h->p4_split) {
+        HIPCHK(h, timed(h, "hpair4_fwd", nv * elems, st,
+                        [&] { return sgm::launch_h_fwd4(h1, nv, g, st); }));
+        HIPCHK(h, timed(h, "hpair4_bwd", nv * elems, st,
+                        [&] { return sgm::launch_h_bwd4(h2, nv, g, st); }));
+    } else {
+        HIPCHK(h, timed(h, "hpair4", nv * elems, st,
+                        [&] { return sgm::launch_hpair4(h1, h2, nv, g, st); }));
+    }
+    HIPCHK(h, timed(h, "final4", nv * elems, st, [&] { return sgm::launch_final4(fin, nv, g, st); }));
+    return SGM_OK;
+}
+
 // build_dsi_from_table[_beta] (dsi 0 / 1) + horizontal IIR (cost_h), then
 // the vertical IIR fused with the L3 forward pass (vfwd), into view slot
 // `view`'s buffers.
@@ -865,7 +912,9 @@ int run_frame(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int 
     // cache lines; lr_cm_kernel reads them through LDS tiles); the slanted
     // pass writes row-major ones
     const bool cm = h->nviews == 2 && !h->slant;
-    if (h->slant) {
+    if (h->paths4) {
+        if ((rc = aggregate4(h, h->nviews, sub0, d_raw, cm ? 1 : 0, st)) != SGM_OK) return rc;
+    } else if (h->slant) {
         if ((rc = slant_views(h, sub0, d_raw, st, vstrip)) != SGM_OK) return rc;
     } else if (h->nviews == 2 && !banded && 2.0 * vol_bytes <= 256.0 * 1024 * 1024) {
         // both volumes fit the Infinity Cache together: joint launches
@@ -1072,6 +1121,7 @@ int sgm_default_params(sgm_params *p, int h, int w, int s, int d) {
     p->solver = SGM_SOLVER_SGM;
     p->aux_only = 0;
     p->view = SGM_VIEW_LEFT;
+    p->paths = 8;            // USE_8_PATH = true (inc/SGM.h:7)
     return SGM_OK;
 }
 
@@ -1101,6 +1151,22 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
     const size_t nvol = npx * h->g.D;
     const size_t nin = (size_t)p->height * p->width;
     h->mf_rows = sgm::median_rows_default(h->g);
+    // the 4-path schedule (BM and aux_only handles aggregate nothing: ignored)
+    h->paths4 = p->paths == 4 && !p->aux_only && p->solver == SGM_SOLVER_SGM;
+    if (h->paths4) {
+        // Its one choice by size, forced either way by SGM_P4_HPAIR (read
+        // here): the H pair as one launch of one-wave rows (0),
+        // or as a forward launch and a backward launch of two-wave rows (1).
+        // With fewer rows in the launch than the device has SIMDs each SIMD
+        // holds at most one chain and the pair's time is its chain latency,
+        // which the two-wave rows cut (K128 one view 299 -> 235 us, two views
+        // 376 -> 336, K64 two views 278 -> 189); with more rows the SIMDs are
+        // filled either way and the single launch measured faster (HD256 two
+        // views 2585 vs 2679 us; profiles/paths4_timing.txt)
+        const char *e = getenv("SGM_P4_HPAIR");
+        h->p4_split = e && (*e == '0' || *e == '1') ? *e == '1'
+                                                    : (long long)h->nviews * h->g.H < 4LL * slant_cus();
+    }
     int rc = SGM_OK;
     do {
         if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) { rc = SGM_ERR_HIP; break; }
@@ -1131,13 +1197,15 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
             if ((rc = dalloc(h, &h->d_s[v], nvol))) break;
             if ((rc = dalloc(h, &h->d_disp[v], npx))) break;
             if ((rc = dalloc(h, &h->d_sub[v], npx))) break;
+            // (a 4-path handle has no diagonal pair and never runs bands)
             for (int f = 0; f < 3 && !rc; ++f)
-                rc = dalloc(h, &h->d_ck[v][f], sgm::pair_ckpt_floats(f, h->g));
+                if (!(h->paths4 && f == sgm::PAIR_D2))
+                    rc = dalloc(h, &h->d_ck[v][f], sgm::pair_ckpt_floats(f, h->g));
             // slot 2 also holds vfwd's forward-band state (3 D-vectors per column)
-            for (int f = 0; f < 3 && !rc; ++f)
+            for (int f = 0; f < 3 && !rc && !h->paths4; ++f)
                 rc = dalloc(h, &h->d_carry[v][f], (size_t)h->g.W * h->g.D * (f == 2 ? 3 : 1));
         }
-        h->band_rows = band_rows_for(h->g);
+        h->band_rows = h->paths4 ? 0 : band_rows_for(h->g);
         if (!rc && p->aux_only) {  // the side stages' maps (stage_lr, the raw map copy)
             for (int v = 0; v < 2 && !rc; ++v) {
                 if ((rc = dalloc(h, &h->d_disp[v], npx))) break;
@@ -1171,7 +1239,8 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
             const char *e = getenv("SGM_SLANT");
             slant_forced = e && *e == '1';
             const bool want = e && *e ? slant_forced : slant_default(h->g, h->nviews);
-            h->slant = !p->aux_only && p->solver == SGM_SOLVER_SGM && want;
+            h->slant = !p->aux_only && p->solver == SGM_SOLVER_SGM && want && !h->paths4;
+            if (h->paths4) slant_forced = false;  // (SGM_SLANT is ignored: the tiles are built around L5..L8)
             const char *ev = getenv("SGM_VSTRIP");
             h->vstrip = !(ev && *ev == '0');
         }
@@ -1435,6 +1504,8 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, cons
 int sgm_stage_path(sgm_handle *h, int dir, const float *cost, float *L, float *minL) {
     if (!h || !cost || !L || dir < 0 || dir > 7) return SGM_ERR_INVALID_ARG;
     if (h->p.aux_only) return set_err(h, SGM_ERR_INVALID_ARG, "stage needs cost volumes (aux_only)");
+    if (h->paths4 && dir >= SGM_DIR_L5)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_path: a 4-path handle serves L1..L4 only");
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
     const size_t npx = (size_t)h->g.H * h->g.W, nvol = npx * h->g.D;
@@ -1457,8 +1528,17 @@ int sgm_stage_aggregate(sgm_handle *h, const float *cost, uint16_t *disp, float 
     StreamScope scope(h, nullptr);
     const size_t npx = (size_t)h->g.H * h->g.W, nvol = npx * h->g.D;
     HIPCHK(h, hipMemcpyAsync(h->d_c[0], cost, nvol * 4, hipMemcpyHostToDevice, h->st));
-    int rc = aggregate_view(h, 0, h->d_c[0], h->d_s[0], h->d_ch[0], h->d_disp[0], h->d_sub[0],
+    int rc;
+    if (h->paths4) {  // the L3 checkpoints from the final volume, then the 4-path passes
+        sgm::PairArgs pa = pair_args(h);
+        pa.cost = h->d_c[0];
+        pa.ckpt = h->d_ck[0][sgm::PAIR_V];
+        HIPCHK(h, pair_fwd(h, sgm::PAIR_V, pa, h->st));
+        rc = aggregate4(h, 1, h->d_sub[0], h->d_disp[0], 0, h->st);
+    } else {
+        rc = aggregate_view(h, 0, h->d_c[0], h->d_s[0], h->d_ch[0], h->d_disp[0], h->d_sub[0],
                             h->st, true);
+    }
     if (rc) return rc;
     if (disp) HIPCHK(h, hipMemcpyAsync(disp, h->d_disp[0], npx * 2, hipMemcpyDeviceToHost, h->st));
     if (sub) HIPCHK(h, hipMemcpyAsync(sub, h->d_sub[0], npx * 4, hipMemcpyDeviceToHost, h->st));

@@ -133,6 +133,15 @@ hipError_t launch_sweep2_l8(const SweepArgs &a0, const SweepArgs &a1, Geom g, hi
 hipError_t launch_stage_a_hpair(const PairArgs *h1, const PairArgs *h2, int nviews, Geom g,
                                 hipStream_t st);
 hipError_t launch_stage_a_band(const SweepArgs &l5, const PairArgs &d6, Geom g, hipStream_t st);
+// 4-path frames (params.paths == 4), nviews views per launch, C
+// by default loads.  The H pair as one launch (one wave per row: L1 forward,
+// then L2 backward -> h2[v].out), or as a forward launch and a two-wave
+// backward launch; the final pass without the T stream (a[v].acc_in unused):
+// total = (s_in + L3) + L4 -> WTA, sub-pixel
+hipError_t launch_hpair4(const PairArgs *h1, const PairArgs *h2, int nviews, Geom g, hipStream_t st);
+hipError_t launch_h_fwd4(const PairArgs *h1, int nviews, Geom g, hipStream_t st);
+hipError_t launch_h_bwd4(const PairArgs *h2, int nviews, Geom g, hipStream_t st);
+hipError_t launch_final4(const PairArgs *a, int nviews, Geom g, hipStream_t st);
 hipError_t launch_vfwd(const float *in, float *out, const PairArgs &a, Geom g, hipStream_t st);
 // the same vertical IIR + L3, writing every row's L3 to the volume l3 (the
 // slanted schedule's bottom-up pass reads it) instead of checkpoints

@@ -142,7 +142,9 @@ __global__ __launch_bounds__(64) void stage_a_kernel(PairArgs h1, SweepArgs l5, 
 // this launch holds only H (per view) single-wave chains, about one per SIMD
 // at HD256, so it waits on memory latency; both views' rows side by side
 // double the loads in flight.
-template <int V, bool FULL>
+// NTC = false (4-path frames, launch_hpair4): default loads, C stays resident
+// for the final pass.
+template <int V, bool FULL, bool NTC = true>
 __global__ __launch_bounds__(64) void hpair_kernel(PairArgs h1a, PairArgs h2a, PairArgs h1b,
                                                    PairArgs h2b, Geom g) {
 #ifdef SGM_HPF
@@ -157,9 +159,93 @@ __global__ __launch_bounds__(64) void hpair_kernel(PairArgs h1a, PairArgs h2a, P
     // Infinity Cache, where its two reads of C pass through once each (the
     // top-down pass beside it -2.6%, HD256 frame -1.0%, 4K256 -0.6% paired,
     // profiles/r06_experiments/r06x_hpair_nt.txt)
-    pair_fwd_body<0, V, FULL, PFH, false, true>(h1, g, bid_x());
+    pair_fwd_body<0, V, FULL, PFH, false, NTC>(h1, g, bid_x());
     __threadfence();  // this wave's checkpoint stores, before it reads them back
-    pair_bwd_body<PAIR_H, V, FULL, PAIR_INIT2, false, true>(h2, g, bid_x(), nullptr, nullptr);
+    pair_bwd_body<PAIR_H, V, FULL, PAIR_INIT2, false, NTC>(h2, g, bid_x(), nullptr, nullptr);
+}
+
+// ---------------------------------------------------------- 4-path frames
+//
+// paths = 4 (the reference's USE_8_PATH off, inc/SGM.h:7): S = ((L1+L2)+L3)+L4
+// goes straight into the WTA (SGM.cpp:387-390), so a view needs the H pair and
+// a final pass without the T stream; no diagonal role shares their launches.
+
+// C by default loads throughout: it stays in the Infinity Cache from the H
+// pair to the final pass where it fits, and non-temporal loads gained nothing
+// where it does not (profiles/paths4_alternatives.txt).
+
+// The H pair as two launches (the stage A / stage B H roles on their own):
+// L1 forward with checkpoints, workgroup y = view ...
+template <int V, bool FULL>
+__global__ __launch_bounds__(64) void h_fwd2_kernel(PairArgs h1a, PairArgs h1b, Geom g) {
+    constexpr int PFH = V >= 4 ? 16 : 32;
+    const bool vb = __builtin_amdgcn_workgroup_id_y() != 0;
+    pair_fwd_body<0, V, FULL, PFH>(vb ? h1b : h1a, g, bid_x());
+}
+
+// ... then L2 backward on two waves per row (recompute wave + backward wave,
+// pair_split_body) -> S12
+template <int V, bool FULL>
+__global__ __launch_bounds__(128) void h_bwd2_kernel(PairArgs h2a, PairArgs h2b, Geom g) {
+    constexpr int K = pair_k<V>();
+    __shared__ __attribute__((aligned(16))) SplitLds<K, V> lds;
+    const bool vb = __builtin_amdgcn_workgroup_id_y() != 0;
+    pair_split_body<PAIR_H, V, FULL, PAIR_INIT2, K, 3>(vb ? h2b : h2a, g, bid_x(), wave_id(), lds,
+                                                       nullptr);
+}
+
+// The final pass of one or two views (workgroup z = view): L4 backward
+// recomputing L3, X = (S12 + L3) + L4 into the LDS ring, and the WTA waves
+// consume X as the total (pair_split_body's NOT): no acc_in loads.
+template <int V, bool FULL>
+__global__ __launch_bounds__(256) void pair_final4_kernel(PairArgs a0, PairArgs a1, Geom g) {
+    constexpr int K = pair_kv<V>();
+    __shared__ __attribute__((aligned(16))) SplitFinalLds<K, V> lds;
+    const PairArgs a = __builtin_amdgcn_workgroup_id_z() != 0 ? a1 : a0;
+    // row-major output maps (one-view frames): a line's columns on one XCD
+    const int path = a.sub_cm ? bid_x() : xcd_column(bid_x(), g.W);
+    pair_split_body<PAIR_V, V, FULL, PAIR_FINAL, K, 3, 2, final_nwta<V, FULL>(), false, false, true>(
+        a, g, path, wave_id(), lds.s, &lds);
+}
+
+hipError_t launch_hpair4(const PairArgs *h1, const PairArgs *h2, int nviews, Geom g, hipStream_t st) {
+    const dim3 grid(g.H, nviews);
+    const PairArgs &b1 = h1[nviews - 1], &b2 = h2[nviews - 1];
+    if (g.D == 32) hpair_kernel<1, false, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    else if (g.D == 64) hpair_kernel<1, true, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    else if (g.D == 128) hpair_kernel<2, true, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    else hpair_kernel<4, true, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_h_fwd4(const PairArgs *h1, int nviews, Geom g, hipStream_t st) {
+    const dim3 grid(g.H, nviews);
+    const PairArgs &b = h1[nviews - 1];
+    if (g.D == 32) h_fwd2_kernel<1, false><<<grid, 64, 0, st>>>(h1[0], b, g);
+    else if (g.D == 64) h_fwd2_kernel<1, true><<<grid, 64, 0, st>>>(h1[0], b, g);
+    else if (g.D == 128) h_fwd2_kernel<2, true><<<grid, 64, 0, st>>>(h1[0], b, g);
+    else h_fwd2_kernel<4, true><<<grid, 64, 0, st>>>(h1[0], b, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_h_bwd4(const PairArgs *h2, int nviews, Geom g, hipStream_t st) {
+    const dim3 grid(g.H, nviews);
+    const PairArgs &b = h2[nviews - 1];
+    if (g.D == 32) h_bwd2_kernel<1, false><<<grid, 128, 0, st>>>(h2[0], b, g);
+    else if (g.D == 64) h_bwd2_kernel<1, true><<<grid, 128, 0, st>>>(h2[0], b, g);
+    else if (g.D == 128) h_bwd2_kernel<2, true><<<grid, 128, 0, st>>>(h2[0], b, g);
+    else h_bwd2_kernel<4, true><<<grid, 128, 0, st>>>(h2[0], b, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_final4(const PairArgs *a, int nviews, Geom g, hipStream_t st) {
+    const dim3 grid(g.W, 1, nviews);
+    const PairArgs &b = a[nviews - 1];
+    if (g.D == 32) pair_final4_kernel<1, false><<<grid, 64 * (2 + final_nwta<1, false>()), 0, st>>>(a[0], b, g);
+    else if (g.D == 64) pair_final4_kernel<1, true><<<grid, 64 * (2 + final_nwta<1, true>()), 0, st>>>(a[0], b, g);
+    else if (g.D == 128) pair_final4_kernel<2, true><<<grid, 64 * (2 + final_nwta<2, true>()), 0, st>>>(a[0], b, g);
+    else pair_final4_kernel<4, true><<<grid, 64 * (2 + final_nwta<4, true>()), 0, st>>>(a[0], b, g);
+    return hipGetLastError();
 }
 
 // Stage B blocks are two waves: an H block splits its row's L2 pass into a

@@ -52,9 +52,16 @@ class SGM:
                  blur: bool = True, views: int = 2, p1: int = 10, p2: int = 100,
                  uniqueness: float = 0.7, lr_max_diff: float = 1.0, post_filter: bool = False,
                  lk_refine: bool = False, sky_detect: bool = False,
-                 aux_only: bool = False, view: str = "left", _solver: int = _capi.SGM_SOLVER_SGM):
+                 aux_only: bool = False, view: str = "left", paths: int = 8,
+                 _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
+        # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
+        # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
+        # (0 means 8, as in a zero-initialised sgm_params)
+        if paths not in (0, 4, 8):
+            raise ValueError(f"paths must be 4 or 8, got {paths!r}")
         p = _capi.default_params(h, w, s, d)
+        p.paths = paths
         p.blur = int(bool(blur))
         p.views = views
         # post_filter: process_device's output is post_filter()ed on the GPU
