@@ -45,7 +45,12 @@ class BatchSGM {
 public:
     // SGM(h, w, s, d) (node.cpp:49) on every device of `devices` (HIP
     // ordinals, each once), in one communicator (sgm_comm_create).
-    BatchSGM(const std::vector<int> &devices, int h, int w, int s, int d) : in_h_(h), in_w_(w) {
+    // post_filter_launches: the median fill's launch budget on every device's
+    // handle (sgm_set_post_filter_launches; 0 = the adaptive fill).  With a
+    // budget no device thread blocks inside its frame: it enqueues the frame
+    // and waits once, in sgm_check, which also reports an unproven fill.
+    BatchSGM(const std::vector<int> &devices, int h, int w, int s, int d, int post_filter_launches = 0)
+        : in_h_(h), in_w_(w) {
         if (devices.empty()) fail("BatchSGM", "no devices");
         sgm_params p;
         if (sgm_default_params(&p, h, w, s, d) != SGM_OK) fail("BatchSGM", "sgm_default_params");
@@ -57,6 +62,11 @@ public:
             if (sgm_create(&p, sl.device, &sl.h) != SGM_OK) {
                 release();
                 fail("BatchSGM", "sgm_create failed (see stderr)");
+            }
+            if (sgm_set_post_filter_launches(sl.h, post_filter_launches) != SGM_OK) {
+                const std::string why = sgm_last_error(sl.h);
+                release();
+                fail("BatchSGM", why.c_str());
             }
             sgm_get_size(sl.h, &rows_, &cols_, nullptr);
             sl.stream = sgm_get_stream(sl.h);

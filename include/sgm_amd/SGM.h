@@ -14,6 +14,7 @@
  *   process(l, r, sky, sky_b)    SGM.cpp:829-834    (masks kept as members)
  *   BM(h, w, s, d)               BM.cpp:4-97        (filtered-cost WTA, post-filtered)
  *   get_disp()                   Solver.h:36        (CV_32FC1, invalid = d+1)
+ *   set_post_filter_launches(n)  (not in the reference) post_filter without host waits
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -246,6 +247,15 @@ public:
     }
 
     sgm_handle *handle() const { return handle_; }
+
+    // The median fill's launch budget (sgm_set_post_filter_launches): n = 0,
+    // the adaptive fill, whose convergence test blocks the host inside
+    // process(); 1..4096, exactly n fill launches and no host wait before the
+    // frame's end, where process() reports a fill that launch n did not prove.
+    void set_post_filter_launches(int n) {
+        if (sgm_set_post_filter_launches(handle_, n) != SGM_OK)
+            fail("set_post_filter_launches", sgm_last_error(handle_));
+    }
 
 protected:
     // views = 1: the left view alone (BM; GPU_SGM, gpu_sgm/src/SGM.cu:105-232)

@@ -32,10 +32,13 @@
  * it; a rocprof trace shows the record as a ~5 us gap before the next
  * kernel); calls on the handle's own stream (NULL, sgm_get_stream) record
  * nothing.  Device entry points return after
- * enqueueing, EXCEPT with post_filter: its median fill blocks the calling
- * host thread on an event once per two fill launches to read a convergence
- * counter (sgm_post_filter_device, and sgm_process_device with
- * params.post_filter), so those calls are not fully asynchronous.
+ * enqueueing; with post_filter they do so unless a launch budget is set
+ * (sgm_set_post_filter_launches): without one the median fill blocks the
+ * calling host thread on an event once per two fill launches to read a
+ * convergence counter (sgm_post_filter_device, and sgm_process_device with
+ * params.post_filter), so those calls are not fully asynchronous and cannot
+ * be captured into a HIP graph; with one they enqueue a fixed number of fill
+ * launches, return, and the device's verdict is read by sgm_check.
  */
 #ifndef SGM_HIP_H
 #define SGM_HIP_H
@@ -183,8 +186,9 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
 
 /* Same on DEVICE buffers, enqueued on `stream` (a hipStream_t; NULL = the
  * handle's own stream).  Returns after enqueueing; the caller synchronises.
- * With params.post_filter the call synchronises `stream` during the median
- * fill's convergence test (sgm_post_filter_device).
+ * With params.post_filter and no launch budget (sgm_set_post_filter_launches)
+ * the call synchronises `stream` during the median fill's convergence test
+ * (sgm_post_filter_device).
  * Volumes above the Infinity Cache may run the slanted-tile passes
  * (DESIGN.md 5e), whose tile-to-tile hand-offs poll with a bounded spin: a
  * frame in which a poll gave up (seconds without progress: a hung or
@@ -200,9 +204,10 @@ int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_ri
  * no asynchronous work to check: SGM::process is synchronous, SGM.cpp:32-826).
  * Waits for the handle's last call's work (its stream, or the event the call
  * recorded on the caller's stream), then returns SGM_ERR_HIP, with the
- * message in sgm_last_error, if any slanted-pass hand-off gave up since the
- * last report -- the maps of the frames in between are then invalid -- and
- * clears the report; else SGM_OK.  Frames replayed from a captured HIP graph
+ * message in sgm_last_error, if any slanted-pass hand-off gave up, or any
+ * fixed-budget median fill ended unproven (sgm_set_post_filter_launches),
+ * since the last report -- the maps of the frames in between are then invalid
+ * -- and clears the report; else SGM_OK.  Frames replayed from a captured HIP graph
  * are not calls on the handle: synchronise the graph's stream first, then
  * call sgm_check.  A caller that gathers or times maps should call it after
  * synchronising and before trusting them. */
@@ -225,8 +230,33 @@ int sgm_lr_check_device(sgm_handle *h, const float *d_fl, int fl_pitch, const fl
  * pitch in floats), enqueued on `stream` (NULL = the handle's stream).  The
  * median fill iterates to a proven fixed point; the call synchronises
  * `stream` once per two fill launches to read the convergence counter, and
- * returns with the speckle kernels enqueued (the caller synchronises). */
+ * returns with the speckle kernels enqueued (the caller synchronises).  With
+ * a launch budget (sgm_set_post_filter_launches) it only enqueues. */
 int sgm_post_filter_device(sgm_handle *h, float *d_disp, int pitch, void *stream);
+
+/* The median fill's launch budget, a property of the handle (like
+ * sgm_set_profiling; sgm_params is unchanged).
+ * n == 0 (default): the adaptive fill (the host reads the convergence counter).
+ * 1 <= n <= 4096: every post filter on this handle enqueues exactly n median-fill
+ * launches, then the component kernels once, with no host readback, no event wait and
+ * no stream synchronisation: the call returns after enqueueing and may be captured into
+ * a HIP graph.  Launches after the one that proved the fixed point return at once.  If
+ * launch n's change counter is not zero the fixed point is not proven: that frame's map
+ * is invalid and is reported like a slanted hand-off timeout (sgm_check, or the next
+ * sgm_process[_device] call; the synchronous sgm_process and sgm_stage_post_filter
+ * check after their own work and return it themselves), once, then cleared; the
+ * message reads "median fill not proven in <n> launches", n the budget of that filter.
+ * ceil(cols / 64) * rows + 1 launches always prove it (DESIGN.md "Post filter"); stereo
+ * maps need far fewer (sgm_post_filter_proved_at measures it; README).
+ * Any other n, or a handle without post-filter buffers: SGM_ERR_INVALID_ARG. */
+int sgm_set_post_filter_launches(sgm_handle *h, int n);
+
+/* Waits as sgm_check does (without reading or clearing its report), then *launch =
+ * 1-based index of the first fill launch of the handle's last post filter whose counter
+ * was zero (the proof), or 0 if none was (or no post filter has run).  For sizing n.
+ * Works after adaptive and fixed-budget filters, eager or replayed from a graph
+ * (synchronise the graph's stream first). */
+int sgm_post_filter_proved_at(sgm_handle *h, int *launch);
 
 /* LKSubPixelImpl::LKRefine(img_l, img_r, disp_float) (LKRefine/LKSubPixelImpl.cpp:
  * 13-235) on the GPU: per-pixel Gauss-Newton refinement of the disparity over
@@ -355,7 +385,9 @@ int sgm_stage_aggregate(sgm_handle *h, const float *cost, uint16_t *disp, float 
 /* LR check (SGM.cpp:803-818): out = checked copy of fl. */
 int sgm_stage_lr(sgm_handle *h, const float *fl, const float *fr, float *out);
 /* post_filter() (Solver.cpp:600-649) on a HOST rows x cols map, in place,
- * computed on the GPU (sgm_post_filter_device); synchronous. */
+ * computed on the GPU (sgm_post_filter_device); synchronous.  With a launch
+ * budget (sgm_set_post_filter_launches) a fill the budget did not prove is
+ * this call's error: SGM_ERR_HIP, and the map written back is invalid. */
 int sgm_stage_post_filter(sgm_handle *h, float *disp);
 /* LKRefine (sgm_lk_refine_device) with HOST buffers: left/right full-size u8
  * images (pitch bytes), disp a rows x cols map refined in place; synchronous. */

@@ -36,6 +36,7 @@ EXPORTS = (
     "sgm_stage_point_cloud", "sgm_lr_check_device", "sgm_get_stream", "sgm_check",
     "sgm_comm_create", "sgm_comm_unique_id", "sgm_comm_create_rank", "sgm_comm_destroy",
     "sgm_comm_last_error", "sgm_comm_info", "sgm_batch_gather", "sgm_batch_gather_all",
+    "sgm_set_post_filter_launches", "sgm_post_filter_proved_at",
 )
 SGM_COMM_ID_BYTES = 128
 
@@ -155,6 +156,8 @@ def lib():
     L.sgm_process_device.argtypes = [P, P, P, I, P, P, I, P, I, P, P]
     L.sgm_check.argtypes = [P]
     L.sgm_post_filter_device.argtypes = [P, P, I, P]
+    L.sgm_set_post_filter_launches.argtypes = [P, I]
+    L.sgm_post_filter_proved_at.argtypes = [P, ctypes.POINTER(I)]
     L.sgm_lr_check_device.argtypes = [P, P, I, P, I, P, I, P]
     L.sgm_stage_post_filter.argtypes = [P, P]
     L.sgm_lk_refine_device.argtypes = [P, P, P, I, P, I, P]

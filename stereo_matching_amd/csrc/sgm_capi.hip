@@ -71,6 +71,9 @@ struct sgm_handle {
     float *d_pf_snap;     // per median tile: the working-map cells it last read
     int *d_pf_changes;    // per median launch: tiles that changed a pixel
     int *h_pf_changes;    // pinned readback of one counter
+    unsigned *h_pf_err;   // host-mapped word: the budget of a fixed-budget fill that was not proven (0: none)
+    unsigned *d_pf_err;   //   its device-side address (pf_verdict_kernel)
+    int pf_launches;      // sgm_set_post_filter_launches: 0 = adaptive, else the fixed budget
     unsigned *h_slant_err;  // slant: host-mapped hang-guard word (SlantArgs::err_host)
     hipStream_t st_h;       // slant: the H pair's stream, beside the top-down pass
     hipEvent_t ev_fork, ev_join;  //   its fork from / join into the frame's stream
@@ -242,6 +245,8 @@ void free_all(sgm_handle *h) {
     (void)hipFree(h->d_cloud_counts);
     if (h->h_pf_changes) (void)hipHostFree(h->h_pf_changes);
     h->h_pf_changes = nullptr;
+    if (h->h_pf_err) (void)hipHostFree(h->h_pf_err);
+    h->h_pf_err = nullptr;
     if (h->h_slant_err) (void)hipHostFree(h->h_slant_err);
     h->h_slant_err = nullptr;
     (void)hipFree(h->d_min);
@@ -1026,15 +1031,20 @@ void pack_rows(uint8_t *dst, const uint8_t *src, size_t row_bytes, int rows, siz
 // lk_refine(..., staged = true) to read.
 int post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_lk) {
     const Geom g = h->g;
+    const int budget = h->pf_launches;
     // The number of median-fill launches depends on a counter read back to
     // the host each round; under stream capture that copy never runs, so a
-    // captured graph would replay a fixed, possibly unconverged, fill.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "post_filter cannot be captured into a HIP graph (its median-fill launch "
-                       "count is read back to the host); capture frames with post_filter = 0");
+    // captured graph would replay a fixed, possibly unconverged, fill.  (A
+    // launch budget fixes the count and has the device judge it: below.)
+    if (!budget) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIPCHK(h, hipStreamIsCapturing(st, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return set_err(h, SGM_ERR_INVALID_ARG,
+                           "post_filter cannot be captured into a HIP graph (its median-fill launch "
+                           "count is read back to the host); capture frames with post_filter = 0 or "
+                           "set a launch budget (sgm_set_post_filter_launches)");
+    }
     const double dnpx = (double)g.H * g.W;
     float *F = h->d_pf_work;
     HIPCHK(h, timed(h, "post_prep", dnpx, st, [&] {
@@ -1060,6 +1070,25 @@ int post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_
         return SGM_OK;
     };
     int k = 0, rc;
+    if (budget) {
+        // Fixed budget: exactly `budget` fill launches (those after the proof
+        // return at their first instruction), the device's verdict on the
+        // last counter, the component kernels once.  Nothing is read back and
+        // nothing waits: the call returns after enqueueing and can be captured.
+        // (with profiling on, one event pair around the whole sequence: a
+        // budget of thousands must not take thousands of pooled events)
+        HIPCHK(h, timed(h, "post_median", dnpx, st, [&] {
+                   hipError_t e = hipSuccess;
+                   for (; k < budget && e == hipSuccess; ++k)
+                       e = sgm::launch_median_fill(h->d_pf_orig, F, k, h->d_pf_snap,
+                                                   h->d_pf_changes, h->mf_rows, g, st);
+                   if (e == hipSuccess)
+                       e = sgm::launch_pf_verdict(h->d_pf_changes, budget, h->d_pf_err, st);
+                   return e;
+               }));
+        h->pf_iters = k;
+        return components();
+    }
     for (;;) {
         // a fill usually settles in 2 launches and the 3rd proves it
         const int batch = k == 0 ? 3 : 2;
@@ -1230,6 +1259,10 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
         if (!rc && hipHostMalloc((void **)&h->h_pf_changes, sizeof(int), hipHostMallocDefault) !=
                        hipSuccess)
             rc = set_err(h, SGM_ERR_HIP, "hipHostMalloc of the post-filter counter failed");
+        if (!rc && (hipHostMalloc((void **)&h->h_pf_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
+                    hipHostGetDevicePointer((void **)&h->d_pf_err, h->h_pf_err, 0) != hipSuccess))
+            rc = set_err(h, SGM_ERR_HIP, "hipHostMalloc of the post filter's verdict word failed");
+        if (!rc) *h->h_pf_err = 0;
         if (!rc && hipMemset(h->d_zero, 0, 256 * sizeof(float)) != hipSuccess)
             rc = set_err(h, SGM_ERR_HIP, "hipMemset of the zero page failed");
         bool slant_forced = false;
@@ -1331,30 +1364,76 @@ void *sgm_get_stream(const sgm_handle *h) { return h ? (void *)h->st : nullptr; 
 // neighbouring tile's hand-off for seconds gives up, and that frame's maps
 // are wrong.  It sets a host-mapped word; the next call on the handle (or
 // sgm_process, after its own frame) reports it and clears it.
-int check_slant_err(sgm_handle *h) {
+// The fixed-budget post filter (sgm_set_post_filter_launches) reports the
+// same way through a word of its own (every handle has one): its verdict
+// kernel sets it when the budget's last fill launch still changed a tile.
+int check_frame_err(sgm_handle *h) {
     // read and clear in one step: a give-up stored by a frame still running
     // between a plain read and a plain clear would be lost
-    if (!h->h_slant_err || !__atomic_exchange_n(h->h_slant_err, 0u, __ATOMIC_ACQ_REL)) return SGM_OK;
-    return set_err(h, SGM_ERR_HIP, "slanted aggregation: a tile hand-off timed out; that frame's maps are invalid");
+    const bool slant = h->h_slant_err && __atomic_exchange_n(h->h_slant_err, 0u, __ATOMIC_ACQ_REL);
+    // (the verdict kernel stores the budget that was not enough: 1..4096)
+    const unsigned fill = h->h_pf_err ? __atomic_exchange_n(h->h_pf_err, 0u, __ATOMIC_ACQ_REL) : 0u;
+    if (!slant && !fill) return SGM_OK;
+    if (!fill)
+        return set_err(h, SGM_ERR_HIP, "slanted aggregation: a tile hand-off timed out; that frame's maps are invalid");
+    return set_err(h, SGM_ERR_HIP,
+                   "post_filter: median fill not proven in %u launches "
+                   "(sgm_set_post_filter_launches); that frame's map is invalid%s",
+                   fill, slant ? "; slanted aggregation: a tile hand-off timed out too" : "");
+}
+
+// Waits for the last call's work: on a caller's stream its end was recorded
+// in ev_last; on the handle's own stream, that stream (the H pair's stream
+// is joined into the frame's stream before the bottom-up pass).
+static int wait_last(sgm_handle *h) {
+    if (h->last_st && h->last_recorded) HIPCHK(h, hipEventSynchronize(h->ev_last));
+    else if (!h->last_st || h->last_st == h->st) HIPCHK(h, hipStreamSynchronize(h->st));
+    else HIPCHK(h, hipDeviceSynchronize());  // a caller's stream whose end could not be recorded
+    return SGM_OK;
 }
 
 int sgm_check(sgm_handle *h) {
     if (!h) return SGM_ERR_INVALID_ARG;
     DeviceGuard guard(h->device);
-    // the last call's work: on a caller's stream its end was recorded in
-    // ev_last; on the handle's own stream, that stream (the H pair's stream
-    // is joined into the frame's stream before the bottom-up pass)
-    if (h->last_st && h->last_recorded) HIPCHK(h, hipEventSynchronize(h->ev_last));
-    else if (!h->last_st || h->last_st == h->st) HIPCHK(h, hipStreamSynchronize(h->st));
-    else HIPCHK(h, hipDeviceSynchronize());  // a caller's stream whose end could not be recorded
-    return check_slant_err(h);
+    if (int rc = wait_last(h)) return rc;
+    return check_frame_err(h);
+}
+
+int sgm_set_post_filter_launches(sgm_handle *h, int n) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (n < 0 || n > kMedianMaxLaunches)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_post_filter_launches: n must be 0 (adaptive) or 1..%d, got %d",
+                       kMedianMaxLaunches, n);
+    if (!h->d_pf_changes || !h->d_pf_err)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_post_filter_launches: the handle has no post-filter buffers");
+    h->pf_launches = n;
+    return SGM_OK;
+}
+
+int sgm_post_filter_proved_at(sgm_handle *h, int *launch) {
+    if (!h || !launch) return SGM_ERR_INVALID_ARG;
+    *launch = 0;
+    DeviceGuard guard(h->device);
+    if (int rc = wait_last(h)) return rc;
+    if (h->pf_iters <= 0) return SGM_OK;  // no post filter yet
+    // (a query, not part of a frame: the counters are read synchronously)
+    std::vector<int> c((size_t)h->pf_iters);
+    HIPCHK(h, hipMemcpy(c.data(), h->d_pf_changes, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < c.size(); ++k)
+        if (c[k] == 0) {
+            *launch = (int)k + 1;
+            break;
+        }
+    return SGM_OK;
 }
 
 int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int pitch,
                        const uint8_t *d_sky_l, const uint8_t *d_sky_r, int sky_pitch,
                        float *d_out, int out_pitch, uint16_t *d_raw_disp, void *stream) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (int rc = check_slant_err(h)) return rc;
+    if (int rc = check_frame_err(h)) return rc;
     if (!d_left || !d_right || !d_out || pitch < h->p.width || out_pitch < h->g.W ||
         ((d_sky_l || d_sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: bad pointer or pitch");
@@ -1377,7 +1456,7 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
     if (h->p.aux_only)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: handle created with aux_only");
     int rc;
-    if ((rc = check_slant_err(h))) return rc;
+    if ((rc = check_frame_err(h))) return rc;
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
     if ((rc = ensure_pinned(h))) return rc;
@@ -1406,7 +1485,7 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
         HIPCHK(h, hipMemcpyAsync(praw, h->d_disp[0], npx * sizeof(uint16_t), hipMemcpyDeviceToHost,
                                  h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
-    if ((rc = check_slant_err(h))) return rc;
+    if ((rc = check_frame_err(h))) return rc;
     for (int i = 0; i < h->g.H; ++i)
         memcpy(out + (size_t)i * out_pitch, pout + (size_t)i * h->g.W, h->g.W * sizeof(float));
     if (raw_disp) memcpy(raw_disp, praw, npx * sizeof(uint16_t));
@@ -1724,7 +1803,8 @@ int sgm_stage_post_filter(sgm_handle *h, float *disp) {
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(disp, h->d_out, npx * 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
+    // synchronous: a fixed-budget fill that was not proven is this call's error
+    return check_frame_err(h);
 }
 
 int sgm_stage_lr(sgm_handle *h, const float *fl, const float *fr, float *out) {

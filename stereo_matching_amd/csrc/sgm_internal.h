@@ -256,6 +256,8 @@ hipError_t launch_median_fill(const float *orig, float *F, int iter, float *snap
                               int rows, Geom g, hipStream_t st);
 hipError_t launch_pf_prep(const float *map, int pitch, float *orig, float *F, int *changes,
                           int nchanges, Geom g, hipStream_t st);
+// fixed-budget fill: stores n to *err_host (host-mapped) when changes[n-1] != 0
+hipError_t launch_pf_verdict(const int *changes, int n, unsigned *err_host, hipStream_t st);
 hipError_t launch_cc_local(const float *F, int *L, int *cnt, int *area, Geom g, hipStream_t st);
 hipError_t launch_cc_merge(const float *F, int *L, Geom g, hipStream_t st);
 hipError_t launch_cc_count(int *L, const int *cnt, int *area, int max_size, Geom g,

@@ -528,6 +528,18 @@ __global__ __launch_bounds__(256) void pf_prep_kernel(const float *__restrict__ 
     F[k] = v;
 }
 
+// The verdict of a fixed-budget fill (sgm_set_post_filter_launches): launch n
+// proved the fixed point iff its counter is zero (a launch after the proof
+// returns at once and leaves its zeroed counter).  Otherwise the map is not
+// proven: n goes into the handle's host-mapped word (a plain store, as the
+// slanted guard's), which the host reads and clears in sgm_check / the next
+// frame (sgm_capi.hip check_frame_err).
+__global__ __launch_bounds__(64) void pf_verdict_kernel(const int *__restrict__ changes, int n,
+                                                       unsigned *err_host) {
+    if (tid_x() == 0 && changes[n - 1] != 0)
+        __hip_atomic_store(err_host, (unsigned)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 }  // namespace
 
 // Tile rows of the fill (read when a handle is created).  A launch takes
@@ -573,6 +585,11 @@ hipError_t launch_pf_prep(const float *map, int pitch, float *orig, float *F, in
     const int n = g.H * g.W > nchanges ? g.H * g.W : nchanges;
     hipLaunchKernelGGL(pf_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, map, pitch, g.H,
                        g.W, orig, F, changes, nchanges);
+    return hipGetLastError();
+}
+
+hipError_t launch_pf_verdict(const int *changes, int n, unsigned *err_host, hipStream_t st) {
+    hipLaunchKernelGGL(pf_verdict_kernel, dim3(1), dim3(64), 0, st, changes, n, err_host);
     return hipGetLastError();
 }
 

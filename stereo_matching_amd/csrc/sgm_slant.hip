@@ -263,7 +263,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void slant_kernel(SlantArgs a, Geom 
     // wave's, or any workgroup's (ctl->dead == this launch's id) -- later
     // polls skip their wait, so a neighbour that never stores costs one spin
     // limit per launch, not one per step (the frame's maps are invalid
-    // anyway, and the host reports it: sgm_capi.hip check_slant_err)
+    // anyway, and the host reports it: sgm_capi.hip check_frame_err)
     unsigned dead = 0;
     auto give_up = [&]() {
         const unsigned id = __builtin_amdgcn_readfirstlane(L.epoch) + 1u;
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void slant_kernel(SlantArgs a, Geom 
         if (lane == 0) {
             atomicAdd(&ctl->err, 1u);
             atomicExch(&ctl->dead, launch_id);
-            // (the host reports it: sgm_capi.hip check_slant_err)
+            // (the host reports it: sgm_capi.hip check_frame_err)
             __hip_atomic_store(a.err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         dead = 1u;

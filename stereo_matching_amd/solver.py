@@ -53,7 +53,7 @@ class SGM:
                  uniqueness: float = 0.7, lr_max_diff: float = 1.0, post_filter: bool = False,
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
-                 _solver: int = _capi.SGM_SOLVER_SGM):
+                 post_filter_launches: int = 0, _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
         # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
@@ -92,6 +92,14 @@ class SGM:
         self._lr = np.full((self.rows, self.cols), self.invalid_disp, np.float32)
         self._raw = np.zeros((self.rows, self.cols), np.uint16)
         self._final = None
+        # post_filter_launches: the median fill's fixed launch budget
+        # (set_post_filter_launches); 0 = the adaptive, host-synchronised fill
+        if post_filter_launches:
+            try:
+                self.set_post_filter_launches(post_filter_launches)
+            except Exception:
+                self.close()
+                raise
 
     # ---------------------------------------------------------- lifecycle
     def close(self) -> None:
@@ -161,10 +169,28 @@ class SGM:
 
     def check(self) -> None:
         """sgm_check: wait for the frames enqueued so far and raise SGMError
-        (SGM_ERR_HIP) if a slanted-pass hand-off gave up in any of them since
-        the last report (their maps are invalid).  Call it after
-        synchronising and before gathering or timing device maps."""
+        (SGM_ERR_HIP) if a slanted-pass hand-off gave up, or a fixed-budget
+        median fill ended unproven, in any of them since the last report
+        (their maps are invalid).  Call it after synchronising and before
+        gathering or timing device maps."""
         check(self._lib.sgm_check(self._h), self._h)
+
+    def set_post_filter_launches(self, n: int) -> None:
+        """sgm_set_post_filter_launches: n = 0, the adaptive median fill (the
+        host reads its convergence counter: post-filtered frames block the
+        calling thread and cannot be captured into a HIP graph); 1..4096,
+        every post filter enqueues exactly n fill launches and returns, and
+        check() reports a fill that launch n did not prove
+        (ceil(cols / 64) * rows + 1 launches always prove it)."""
+        check(self._lib.sgm_set_post_filter_launches(self._h, int(n)), self._h)
+
+    def post_filter_proved_at(self) -> int:
+        """sgm_post_filter_proved_at: waits for the last call's work, then the
+        1-based index of the first fill launch of the last post filter that
+        changed nothing (0: none did)."""
+        k = ctypes.c_int()
+        check(self._lib.sgm_post_filter_proved_at(self._h, ctypes.byref(k)), self._h)
+        return k.value
 
     def get_disp(self) -> np.ndarray:
         """Post-filtered disparity (inc/Solver.h:36: filtered_disp after
@@ -192,7 +218,8 @@ class SGM:
 
     def post_filter(self, disp) -> np.ndarray:
         """post_filter() (Solver.cpp:600-649) of a rows x cols map on the GPU
-        (sgm_stage_post_filter); returns a filtered copy."""
+        (sgm_stage_post_filter); returns a filtered copy.  Synchronous: with a
+        launch budget, a fill the budget did not prove raises here."""
         f = np.array(disp, dtype=np.float32, copy=True, order="C")
         if f.shape != (self.rows, self.cols):
             raise ValueError(f"disp: expected shape {(self.rows, self.cols)}, got {f.shape}")
@@ -329,9 +356,11 @@ class BM(SGM):
     WTA result."""
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
-                 blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False):
+                 blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
+                 post_filter_launches: int = 0):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
-                         post_filter=True, sky_detect=sky_detect, _solver=_capi.SGM_SOLVER_BM)
+                         post_filter=True, sky_detect=sky_detect,
+                         post_filter_launches=post_filter_launches, _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -343,5 +372,7 @@ class GPU_SGM(SGM):
     (src/SGM.cpp:32-443, Solver.cpp:569-649), not the CUDA tree's
     approximations."""
 
-    def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0):
-        super().__init__(h, w, s, d, device=device, views=1, post_filter=True)
+    def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
+                 post_filter_launches: int = 0):
+        super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
+                         post_filter_launches=post_filter_launches)
