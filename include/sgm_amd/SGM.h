@@ -243,6 +243,9 @@ public:
                                    filtered_disp.template ptr<float>(0),
                                    (int)(filtered_disp.step / sizeof(float)), nullptr);
         if (rc != SGM_OK) fail("process", sgm_last_error(handle_));
+        if (confidence_on_ &&
+            sgm_stage_confidence(handle_, SGM_VIEW_LEFT, confidence_.template ptr<float>(0)) != SGM_OK)
+            fail("process", sgm_last_error(handle_));
         if (scale > 1) decimate_left();
     }
 
@@ -256,6 +259,25 @@ public:
         if (sgm_set_post_filter_launches(handle_, n) != SGM_OK)
             fail("set_post_filter_launches", sgm_last_error(handle_));
     }
+
+    // The per-pixel match confidence (sgm_set_confidence): with it on, every
+    // process() also keeps the left view's uniqueness ratio, min_cost /
+    // sec_min_cost of the aggregated WTA (SGM.cpp:392-409; lower = more
+    // distinctive), for get_confidence().  BM has none: it fails.
+    void set_confidence(bool enable) {
+        if (sgm_set_confidence(handle_, enable ? 1 : 0) != SGM_OK)
+            fail("set_confidence", sgm_last_error(handle_));
+        confidence_on_ = enable;
+        if (enable) {
+            confidence_.create(img_h, img_w, CV_32FC1);
+            std::memset(confidence_.data, 0, (size_t)confidence_.rows * confidence_.step);
+        } else {
+            confidence_ = Mat();
+        }
+    }
+    // CV_32FC1 on the working grid, the left view of the last process();
+    // empty while confidence is off
+    const Mat &get_confidence() const { return confidence_; }
 
 protected:
     // views = 1: the left view alone (BM; GPU_SGM, gpu_sgm/src/SGM.cu:105-232)
@@ -276,6 +298,8 @@ protected:
 private:
     sgm_handle *handle_ = nullptr;
     bool bm_;
+    bool confidence_on_ = false;
+    Mat confidence_;
 
     void check_mask(const Mat &m, const char *what) const {
         if (m.type() != CV_8UC1 || m.rows != img_h || m.cols != img_w)

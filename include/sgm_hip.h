@@ -258,6 +258,52 @@ int sgm_set_post_filter_launches(sgm_handle *h, int n);
  * (synchronise the graph's stream first). */
 int sgm_post_filter_proved_at(sgm_handle *h, int *launch);
 
+/* ---- match confidence: the uniqueness test's own quotient, per pixel ----
+ *
+ * ratio(i, j) = min_cost / sec_min_cost (SGM.cpp:392-409's locals) as one fp32
+ * division: min_cost = min_d S[i, j, d], sec_min_cost the smallest S[i, j, d]
+ * != min_cost, or FLT_MAX (SGM.cpp:399's initial value) when every cost of
+ * the pixel is equal.  S is what the handle aggregates (8 paths, or
+ * ((L1 + L2) + L3) + L4 with paths = 4).  Range [0, 1); lower = more
+ * distinctive.  (Frames with sky masks only: beside a masked pixel's 999999
+ * override a path cost C + min(...) - minL_prev can be negative, and the
+ * quotient of such a pixel lies outside [0, 1); it is still the number the
+ * uniqueness test compared.)  A pixel the uniqueness test invalidated has ratio >
+ * params.uniqueness (and |min_d - sec_d| > 1).  The map is the WTA's: the LR
+ * check, post_filter and LKRefine do not change it.  Bit-exact against the
+ * oracle's aggregated volume (tests/confidence_recipe.py).
+ *
+ * A property of the handle (like sgm_set_post_filter_launches; sgm_params is
+ * unchanged).  enable != 0: allocates one rows x cols f32 map per view the
+ * handle computes (counted in sgm_device_bytes), and every later frame's final
+ * pass (and sgm_stage_aggregate) stores the quotient beside the sub-pixel
+ * map, in that map's layout (column-major in the two-view frames that keep a
+ * column-major sub-pixel map; sgm_confidence_device transposes on the way
+ * out, so no row-major twin is kept).  enable == 0: frees them; frames run
+ * exactly as before.  Synchronises the handle's last work first; call it
+ * outside stream capture, and re-capture graphs afterwards.  BM and aux_only
+ * handles: SGM_ERR_INVALID_ARG. */
+int sgm_set_confidence(sgm_handle *h, int enable);
+
+/* Copies the last frame's ratio map of `view` (SGM_VIEW_LEFT / SGM_VIEW_RIGHT;
+ * a views = 1 handle serves only its own view) to the caller's row-major
+ * DEVICE buffer (rows x cols f32, pitch in floats >= cols; padding untouched).
+ * One kernel enqueued on `stream` (NULL = the handle's stream), no host wait:
+ * capturable into a HIP graph with the frame.  Ordered after the frame as
+ * every call on the handle is ("Streams" above).  SGM_ERR_INVALID_ARG when
+ * confidence is off or the handle does not compute that view. */
+int sgm_confidence_device(sgm_handle *h, int view, float *d_ratio, int pitch, void *stream);
+
+/* In place on a DEVICE working-grid map: disp = D+1 where ratio > max_ratio
+ * (pitches in floats).  One elementwise kernel on `stream`; any handle of the
+ * working size serves, aux_only included.  Applies a stricter uniqueness than
+ * the frame's without re-running it.  It tests the quotient alone: the WTA's
+ * second clause, |min_d - sec_d| > 1 (adjacent minima are kept whatever their
+ * ratio), is NOT reproduced, so max_ratio = params.uniqueness invalidates a
+ * superset of what the frame did. */
+int sgm_confidence_filter_device(sgm_handle *h, float *d_disp, int pitch, const float *d_ratio,
+                                 int ratio_pitch, float max_ratio, void *stream);
+
 /* LKSubPixelImpl::LKRefine(img_l, img_r, disp_float) (LKRefine/LKSubPixelImpl.cpp:
  * 13-235) on the GPU: per-pixel Gauss-Newton refinement of the disparity over
  * a 7x7 window, interior pixels truncated first (:80), border pixels untouched.
@@ -382,6 +428,13 @@ int sgm_stage_path(sgm_handle *h, int dir, const float *cost, float *L, float *m
 /* 8 paths (4 with params.paths == 4: ((L1+L2)+L3)+L4) + aggregation + WTA +
  * uniqueness + sub-pixel (SGM.cpp:81-443). */
 int sgm_stage_aggregate(sgm_handle *h, const float *cost, uint16_t *disp, float *sub);
+/* sgm_confidence_device with a HOST buffer: ratio rows x cols f32 (dense), the
+ * map of `view` left by the last frame or sgm_stage_aggregate (view 0 of a
+ * two-view handle, the handle's own view otherwise); synchronous. */
+int sgm_stage_confidence(sgm_handle *h, int view, float *ratio);
+/* sgm_confidence_filter_device with HOST buffers: disp and ratio rows x cols
+ * f32 (dense), disp filtered in place; synchronous. */
+int sgm_stage_confidence_filter(sgm_handle *h, float *disp, const float *ratio, float max_ratio);
 /* LR check (SGM.cpp:803-818): out = checked copy of fl. */
 int sgm_stage_lr(sgm_handle *h, const float *fl, const float *fr, float *out);
 /* post_filter() (Solver.cpp:600-649) on a HOST rows x cols map, in place,

@@ -37,6 +37,8 @@ EXPORTS = (
     "sgm_comm_create", "sgm_comm_unique_id", "sgm_comm_create_rank", "sgm_comm_destroy",
     "sgm_comm_last_error", "sgm_comm_info", "sgm_batch_gather", "sgm_batch_gather_all",
     "sgm_set_post_filter_launches", "sgm_post_filter_proved_at",
+    "sgm_set_confidence", "sgm_confidence_device", "sgm_stage_confidence",
+    "sgm_confidence_filter_device", "sgm_stage_confidence_filter",
 )
 SGM_COMM_ID_BYTES = 128
 
@@ -158,6 +160,11 @@ def lib():
     L.sgm_post_filter_device.argtypes = [P, P, I, P]
     L.sgm_set_post_filter_launches.argtypes = [P, I]
     L.sgm_post_filter_proved_at.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_set_confidence.argtypes = [P, I]
+    L.sgm_confidence_device.argtypes = [P, I, P, I, P]
+    L.sgm_stage_confidence.argtypes = [P, I, P]
+    L.sgm_confidence_filter_device.argtypes = [P, P, I, P, I, ctypes.c_float, P]
+    L.sgm_stage_confidence_filter.argtypes = [P, P, P, ctypes.c_float]
     L.sgm_lr_check_device.argtypes = [P, P, I, P, I, P, I, P]
     L.sgm_stage_post_filter.argtypes = [P, P]
     L.sgm_lk_refine_device.argtypes = [P, P, P, I, P, I, P]

@@ -47,6 +47,8 @@ struct sgm_handle {
     float *d_s[2];        // S chain
     uint16_t *d_disp[2];  // WTA disparity
     float *d_sub[2];      // sub-pixel disparity
+    float *d_ratio[2];    // match confidence min / second-min (sgm_set_confidence; null: off)
+    bool ratio_cm[2];     //   the last final pass stored it column-major (as its sub-pixel map)
     float *d_out;         // LR-checked output (host API)
     float *d_min;         // minL (stage_path)
     float *d_zero;        // 256 zero floats (PairArgs::zero)
@@ -231,7 +233,7 @@ void free_all(sgm_handle *h) {
         (void)hipFree(h->d_ch_base[v]); (void)hipFree(h->d_c[v]); (void)hipFree(h->d_s[v]);
         for (auto &c : h->d_carry[v]) (void)hipFree(c);
         (void)hipFree(h->d_l3[v]);
-        (void)hipFree(h->d_disp[v]); (void)hipFree(h->d_sub[v]);
+        (void)hipFree(h->d_disp[v]); (void)hipFree(h->d_sub[v]); (void)hipFree(h->d_ratio[v]);
     }
     (void)hipFree(h->d_out);
     (void)hipFree(h->d_gran);
@@ -494,6 +496,8 @@ int aggregate_view(sgm_handle *h, int view, const float *cost, float *S, float *
     pa.disp = disp;
     pa.sub = sub;
     pa.sub_cm = sub_cm;
+    pa.ratio = h->d_ratio[view];  // (null: confidence off)
+    h->ratio_cm[view] = sub_cm != 0;
     if (banded) {
         // bottom band first: the backward passes walk up
         for (int kb = 0; kb < H; kb += BR) {
@@ -563,6 +567,8 @@ int aggregate_joint(sgm_handle *h, float *sub0, uint16_t *raw, int cm, hipStream
         fin[v].disp = v ? nullptr : raw;
         fin[v].sub = v ? h->d_sub[1] : sub0;
         fin[v].sub_cm = cm;
+        fin[v].ratio = h->d_ratio[v];
+        h->ratio_cm[v] = cm != 0;
     }
     const Geom g = h->g;
     HIPCHK(h, timed(h, "stage_a", elems2, st, [&] { return sgm::launch_stage_a2(h1, l5, d6, g, st); }));
@@ -601,6 +607,8 @@ int aggregate4(sgm_handle *h, int nv, float *sub0, uint16_t *raw, int cm, hipStr
         fin[v].disp = v ? nullptr : raw;
         fin[v].sub = v ? h->d_sub[1] : sub0;
         fin[v].sub_cm = cm;
+        fin[v].ratio = h->d_ratio[v];
+        h->ratio_cm[v] = cm != 0;
     }
     if (h->p4_split) {
         HIPCHK(h, timed(h, "hpair4_fwd", nv * elems, st,
@@ -737,7 +745,8 @@ int slant_views(sgm_handle *h, float *sub0, uint16_t *raw, hipStream_t st, bool 
         hp2[v] = hp1[v];
         hp2[v].out = h->d_s[v];
         sa.v[v] = {h->d_c[v], h->d_s[v], h->d_l3[v], t_buf(h, v), t_buf(h, v),
-                   v ? h->d_sub[1] : sub0, v ? nullptr : raw, h->d_gran};
+                   v ? h->d_sub[1] : sub0, v ? nullptr : raw, h->d_gran, h->d_ratio[v]};
+        h->ratio_cm[v] = false;
     }
     sa.ctl = h->d_slant_ctl;
     sa.zero = h->d_zero;
@@ -1332,6 +1341,16 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
         return rc;
     }
     *out = h;
+    // SGM_CONFIDENCE=1: handles start with the confidence maps on (timing the
+    // feature's cost under tools that create their own handles, tools/ab_env.sh)
+    if (const char *e = getenv("SGM_CONFIDENCE"))
+        if (*e == '1' && !p->aux_only && p->solver == SGM_SOLVER_SGM && sgm_set_confidence(h, 1) != SGM_OK) {
+            fprintf(stderr, "sgm_create: %s\n", h->err);
+            *out = nullptr;
+            free_all(h);
+            delete h;
+            return SGM_ERR_OUT_OF_MEMORY;
+        }
     return SGM_OK;
 }
 
@@ -1409,6 +1428,112 @@ int sgm_set_post_filter_launches(sgm_handle *h, int n) {
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_set_post_filter_launches: the handle has no post-filter buffers");
     h->pf_launches = n;
+    return SGM_OK;
+}
+
+// the view slot holding `view`'s maps (-1: the handle does not compute it)
+static int view_slot(const sgm_handle *h, int view) {
+    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT) return -1;
+    if (h->nviews == 2) return view == SGM_VIEW_RIGHT ? 1 : 0;
+    return view == h->p.view ? 0 : -1;  // (a right-view handle runs in slot 0)
+}
+
+int sgm_set_confidence(sgm_handle *h, int enable) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_confidence: BM and aux_only handles run no aggregated WTA");
+    DeviceGuard guard(h->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_confidence: call it outside stream capture");
+    if ((enable != 0) == (h->d_ratio[0] != nullptr)) return SGM_OK;
+    // frames in flight still store through (or read) the maps
+    if (int rc = wait_last(h)) return rc;
+    const size_t npx = (size_t)h->g.H * h->g.W;
+    if (!enable) {
+        for (int v = 0; v < 2; ++v) {
+            if (h->d_ratio[v]) h->bytes -= npx * sizeof(float);
+            (void)hipFree(h->d_ratio[v]);
+            h->d_ratio[v] = nullptr;
+        }
+        return SGM_OK;
+    }
+    for (int v = 0; v < h->nviews; ++v) {
+        int rc = dalloc(h, &h->d_ratio[v], npx);
+        // (a map no frame has written yet reads as zeros)
+        if (!rc && hipMemset(h->d_ratio[v], 0, npx * sizeof(float)) != hipSuccess)
+            rc = set_err(h, SGM_ERR_HIP, "hipMemset of the confidence map failed");
+        if (rc) {
+            for (int w = 0; w < 2; ++w) {
+                if (h->d_ratio[w]) h->bytes -= npx * sizeof(float);
+                (void)hipFree(h->d_ratio[w]);
+                h->d_ratio[w] = nullptr;
+            }
+            return rc;
+        }
+        h->ratio_cm[v] = false;
+    }
+    return SGM_OK;
+}
+
+int sgm_confidence_device(sgm_handle *h, int view, float *d_ratio, int pitch, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!d_ratio || pitch < h->g.W)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_confidence_device: bad pointer or pitch");
+    const int slot = view_slot(h, view);
+    if (slot < 0)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_confidence_device: the handle does not compute view %d", view);
+    if (!h->d_ratio[slot])
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_confidence_device: confidence is off (sgm_set_confidence)");
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "confidence_out", (double)h->g.H * h->g.W, st, [&] {
+               return sgm::launch_ratio_out(h->d_ratio[slot], h->ratio_cm[slot] ? 1 : 0, d_ratio, pitch,
+                                            h->g, st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_stage_confidence(sgm_handle *h, int view, float *ratio) {
+    if (!h || !ratio) return SGM_ERR_INVALID_ARG;
+    // staged through the post filter's working map (dead between calls)
+    if (int rc = sgm_confidence_device(h, view, h->d_pf_work, h->g.W, nullptr)) return rc;
+    DeviceGuard guard(h->device);
+    HIPCHK(h, hipMemcpyAsync(ratio, h->d_pf_work, (size_t)h->g.H * h->g.W * sizeof(float),
+                             hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return SGM_OK;
+}
+
+int sgm_confidence_filter_device(sgm_handle *h, float *d_disp, int pitch, const float *d_ratio,
+                                 int ratio_pitch, float max_ratio, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!d_disp || !d_ratio || pitch < h->g.W || ratio_pitch < h->g.W)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_confidence_filter_device: bad pointer or pitch");
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "confidence_filter", (double)h->g.H * h->g.W, st, [&] {
+               return sgm::launch_confidence_filter(d_disp, pitch, d_ratio, ratio_pitch, max_ratio, h->g,
+                                                    st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_stage_confidence_filter(sgm_handle *h, float *disp, const float *ratio, float max_ratio) {
+    if (!h || !disp || !ratio) return SGM_ERR_INVALID_ARG;
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    const size_t npx = (size_t)h->g.H * h->g.W;
+    HIPCHK(h, hipMemcpyAsync(h->d_out, disp, npx * 4, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipMemcpyAsync(h->d_pf_work, ratio, npx * 4, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, sgm::launch_confidence_filter(h->d_out, h->g.W, h->d_pf_work, h->g.W, max_ratio, h->g,
+                                            h->st));
+    HIPCHK(h, hipMemcpyAsync(disp, h->d_out, npx * 4, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     return SGM_OK;
 }
 

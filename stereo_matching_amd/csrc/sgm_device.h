@@ -463,9 +463,18 @@ __device__ __forceinline__ int first_index(const float (&tot)[V], float x) {
     return best;
 }
 
+// The match confidence of a pixel (the uniqueness test's own quotient,
+// SGM.cpp:392-409): min_cost / sec_min_cost as one fp32 division, over
+// FLT_MAX (SGM.cpp:399's initial value, not the kernels' +inf) when no second
+// distinct cost exists.
+__device__ __forceinline__ float wta_ratio(float m, float sec) {
+    return m / (sec != SGM_INF ? sec : FLT_MAX);
+}
+
 template <int V>
 __device__ __forceinline__ void wta_subpixel(const float (&tot)[V], int D, float uniq,
-                                             int &disp_out, float &sub_out) {
+                                             int &disp_out, float &sub_out,
+                                             bool want_ratio = false, float *ratio_out = nullptr) {
     float lm = tot[0];
 #pragma unroll
     for (int v = 1; v < V; ++v) lm = fminf(lm, tot[v]);
@@ -475,6 +484,8 @@ __device__ __forceinline__ void wta_subpixel(const float (&tot)[V], int D, float
     for (int v = 0; v < V; ++v) ls = fminf(ls, tot[v] != m ? tot[v] : SGM_INF);
     const float sec = wave_min_u(ls);
     const int min_d = first_index<V>(tot, m);
+    // the match confidence (want_ratio is wave-uniform; the caller stores it)
+    if (want_ratio) *ratio_out = wta_ratio(m, sec);
     int d = min_d;
     if (sec != SGM_INF) {  // a second distinct value exists (else sec = FLT_MAX: ratio ~ 0)
         const int sec_d = first_index<V>(tot, sec);
@@ -569,7 +580,8 @@ template <int V, int PF>
 __device__ __forceinline__ void wta_consume_chunk_at(const float (*tb)[tbuf_stride<V>()],
                                                      long long pix0, long long pix_step, int cnt,
                                                      int lane, int Dn, float uniq,
-                                                     uint16_t *disp, float *sub) {
+                                                     uint16_t *disp, float *sub,
+                                                     float *ratio = nullptr) {
     constexpr int LPP = 64 / PF;  // lanes per pixel
     const int Q = Dn / LPP;       // disparities per lane (>= 8)
     const int px = lane / LPP, q = lane - px * LPP;
@@ -615,6 +627,7 @@ __device__ __forceinline__ void wta_consume_chunk_at(const float (*tb)[tbuf_stri
         const long long pix = pix0 + px * pix_step;
         disp[pix] = (uint16_t)d;
         sub[pix] = f;
+        if (ratio) ratio[pix] = wta_ratio(w.m, w.s);
     }
 }
 
@@ -656,12 +669,13 @@ __device__ __forceinline__ int group_min_i(int x) {
 // this lane's constant offset (>= 0), so the stores need no per-lane 64-bit
 // address arithmetic.
 // sub goes to sub_top + sub_off (its own layout: column-major maps of the
-// two-view frames), disp to pix_top + pix_off (row-major).
+// two-view frames), disp to pix_top + pix_off (row-major); ratio (optional:
+// min / second-min, wta_ratio) goes where sub goes.
 template <int V, int PF, int QQ>
 __device__ __forceinline__ void wta_chunk_q(const float (&x)[QQ], const float (*tb)[tbuf_stride<V>()],
                                             long long pix_top, unsigned pix_off, long long sub_top,
                                             unsigned sub_off, int cnt, int lane, int Dn, float uniq,
-                                            uint16_t *disp, float *sub) {
+                                            uint16_t *disp, float *sub, float *ratio) {
     constexpr int LPP = 64 / PF;  // lanes per pixel
     static_assert(QQ % 4 == 0 && LPP <= 32, "QQ a multiple of 4, at most 32 lanes per pixel");
     const int px = lane / LPP, q = lane - px * LPP;
@@ -707,6 +721,8 @@ __device__ __forceinline__ void wta_chunk_q(const float (&x)[QQ], const float (*
         // final pass at K128 for both maps, profiles/r03_experiments/final_stores.txt)
         if (disp) (disp + pix_top)[pix_off] = (uint16_t)d;
         (sub + sub_top)[sub_off] = f;
+        // the match confidence, in sub's layout (null, wave-uniform: not wanted)
+        if (ratio) (ratio + sub_top)[sub_off] = wta_ratio(m, sec);
     }
 }
 
@@ -714,10 +730,10 @@ template <int V, int PF>
 __device__ __forceinline__ void wta_consume_chunk(const float (*tb)[tbuf_stride<V>()],
                                                   const long long *pb, int cnt, int lane,
                                                   int Dn, float uniq, uint16_t *disp,
-                                                  float *sub) {
+                                                  float *sub, float *ratio = nullptr) {
     // pixels of a chunk are equally spaced along the scanline
     const long long step = cnt > 1 ? pb[1] - pb[0] : 0;
-    wta_consume_chunk_at<V, PF>(tb, pb[0], step, cnt, lane, Dn, uniq, disp, sub);
+    wta_consume_chunk_at<V, PF>(tb, pb[0], step, cnt, lane, Dn, uniq, disp, sub, ratio);
 }
 
 }  // namespace sgm

@@ -93,6 +93,8 @@ struct PairArgs {
     uint16_t *disp;      // FINAL: raw WTA map, row-major (null: not wanted)
     float *sub;          // FINAL: sub-pixel map, row-major or (sub_cm) column-major
     int sub_cm;          // 1: sub[col * H + row] (two-view frames: lr_cm_kernel reads it)
+    float *ratio;        // FINAL: match confidence min / second-min, in sub's layout
+                         // (null: not wanted; sgm_set_confidence)
     const float *zero;   // >= 256 zero floats: the cost of the virtual positions
                          // that align forward passes with their checkpoints
     float p1, p2, uniq;
@@ -176,12 +178,13 @@ struct SlantView {
     float *sub;                          // HW sub-pixel map, row-major
     uint16_t *disp;                      // HW raw WTA map (null: not wanted)
     unsigned long long *gran;            // hand-off granules, slant_gran_count
+    float *ratio;                        // HW match confidence, row-major (null: not wanted)
 };
 struct SlantArgs {
     SlantView v[2];
     SlantCtl *ctl;
     const float *zero;  // >= 256 zero floats
-    float *dummy;       // >= 258 words: the target of inactive steps' stores
+    float *dummy;       // >= 259 words: the target of inactive steps' stores
     float p1, p2, uniq;
     int nviews;
     int ntiles, grid;   // set by the launcher
@@ -287,5 +290,13 @@ hipError_t launch_lr(const float *fl, int fl_pitch, const float *fr, int fr_pitc
 // the two-view frame's final passes write them), row-major out
 hipError_t launch_lr_cm(const float *fl_cm, const float *fr_cm, float *out, int out_pitch, float lr,
                         Geom g, hipStream_t st);
+// the match-confidence map of a view to a caller's pitched row-major buffer:
+// src column-major (cm: src[col * H + row], as the two-view final passes
+// store it beside sub) or row-major
+hipError_t launch_ratio_out(const float *src, int cm, float *out, int out_pitch, Geom g,
+                            hipStream_t st);
+// in place: disp = D + 1 where ratio > max_ratio
+hipError_t launch_confidence_filter(float *disp, int pitch, const float *ratio, int ratio_pitch,
+                                    float max_ratio, Geom g, hipStream_t st);
 
 }  // namespace sgm

@@ -563,7 +563,8 @@ __global__ __launch_bounds__(64 * (NW + 1)) void slant_kernel(SlantArgs a, Geom 
         auto wta_out = [&](const float (&tt)[V], int ps) {
             int d;
             float f;
-            wta_subpixel<V>(tt, D, a.uniq, d, f);
+            float rq = 0.0f;  // the match confidence, computed only when wanted
+            wta_subpixel<V>(tt, D, a.uniq, d, f, sv.ratio != nullptr, &rq);
             // outputs: an inactive step writes the dummy words instead
             const int j = u + ps;
             const bool act = ps >= 0 && j >= 0 && j < W;
@@ -573,6 +574,10 @@ __global__ __launch_bounds__(64 * (NW + 1)) void slant_kernel(SlantArgs a, Geom 
             if (sv.disp) {
                 uint16_t *ds = act ? sv.disp + pix : reinterpret_cast<uint16_t *>(a.dummy + 257);
                 if (lane == 0) *ds = (uint16_t)d;
+            }
+            if (sv.ratio) {
+                float *rs = act ? sv.ratio + pix : a.dummy + 258;
+                if (lane == 0) *rs = rq;
             }
         };
 #ifdef SGM_SLANT_STAMPS

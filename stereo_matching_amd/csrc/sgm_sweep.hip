@@ -213,6 +213,64 @@ hipError_t launch_lr_cm(const float *fl_cm, const float *fr_cm, float *out, int 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------ match confidence
+
+// A view's ratio map to the caller's pitched row-major buffer.  CM: the map
+// is column-major (src[col * H + row], stored beside the two-view frames'
+// column-major sub-pixel map); a 64-column x 32-row tile goes through LDS
+// with 128-byte column reads and 256-byte row writes, as lr_cm_kernel's.
+template <bool CM>
+__global__ __launch_bounds__(256) void ratio_out_kernel(const float *__restrict__ src,
+                                                        float *__restrict__ out, int out_pitch,
+                                                        int H, int W) {
+    __shared__ float tile[LRT_J][LRT_I + 1];
+    const int j0 = bid_x() * LRT_J, i0 = bid_y() * LRT_I;
+    const int t = tid_x();
+    if constexpr (CM) {
+#pragma unroll
+        for (int k = 0; k < LRT_J * LRT_I / 256; ++k) {
+            const int idx = t + k * 256, c = idx / LRT_I, ii = idx - c * LRT_I, j = j0 + c, i = i0 + ii;
+            tile[c][ii] = (j < W && i < H) ? src[(size_t)j * H + i] : 0.f;
+        }
+        __syncthreads();
+    }
+    const int jj = t & (LRT_J - 1), j = j0 + jj;
+    if (j >= W) return;
+#pragma unroll
+    for (int k = 0; k < LRT_I / 4; ++k) {
+        const int ii = (t >> 6) + 4 * k, i = i0 + ii;
+        if (i >= H) break;
+        out[(size_t)i * out_pitch + j] = CM ? tile[jj][ii] : src[(size_t)i * W + j];
+    }
+}
+
+hipError_t launch_ratio_out(const float *src, int cm, float *out, int out_pitch, Geom g,
+                            hipStream_t st) {
+    const dim3 grid((g.W + LRT_J - 1) / LRT_J, (g.H + LRT_I - 1) / LRT_I);
+    if (cm) ratio_out_kernel<true><<<grid, 256, 0, st>>>(src, out, out_pitch, g.H, g.W);
+    else ratio_out_kernel<false><<<grid, 256, 0, st>>>(src, out, out_pitch, g.H, g.W);
+    return hipGetLastError();
+}
+
+// A stricter uniqueness after the frame: disp = D + 1 where ratio > max_ratio
+// (the quotient alone: the WTA's |min_d - sec_d| > 1 clause needs the two
+// indices, which the map does not carry).  Pitches in floats.
+__global__ __launch_bounds__(256) void confidence_filter_kernel(float *disp, int pitch,
+                                                                const float *__restrict__ ratio,
+                                                                int ratio_pitch, float max_ratio,
+                                                                int W, int D) {
+    const int j = bid_x() * 256 + tid_x(), i = bid_y();
+    if (j >= W) return;
+    if (ratio[(size_t)i * ratio_pitch + j] > max_ratio) disp[(size_t)i * pitch + j] = (float)(D + 1);
+}
+
+hipError_t launch_confidence_filter(float *disp, int pitch, const float *ratio, int ratio_pitch,
+                                    float max_ratio, Geom g, hipStream_t st) {
+    confidence_filter_kernel<<<dim3((g.W + 255) / 256, g.H), 256, 0, st>>>(disp, pitch, ratio, ratio_pitch,
+                                                                          max_ratio, g.W, g.D);
+    return hipGetLastError();
+}
+
 }  // namespace sgm
 
 #ifdef SGM_STAMPS

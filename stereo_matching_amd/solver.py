@@ -53,7 +53,8 @@ class SGM:
                  uniqueness: float = 0.7, lr_max_diff: float = 1.0, post_filter: bool = False,
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
-                 post_filter_launches: int = 0, _solver: int = _capi.SGM_SOLVER_SGM):
+                 post_filter_launches: int = 0, confidence: bool = False,
+                 _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
         # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
@@ -94,12 +95,16 @@ class SGM:
         self._final = None
         # post_filter_launches: the median fill's fixed launch budget
         # (set_post_filter_launches); 0 = the adaptive, host-synchronised fill
-        if post_filter_launches:
-            try:
+        # confidence: every frame also keeps its per-pixel uniqueness ratio
+        # (set_confidence / get_confidence)
+        try:
+            if post_filter_launches:
                 self.set_post_filter_launches(post_filter_launches)
-            except Exception:
-                self.close()
-                raise
+            if confidence:
+                self.set_confidence(True)
+        except Exception:
+            self.close()
+            raise
 
     # ---------------------------------------------------------- lifecycle
     def close(self) -> None:
@@ -191,6 +196,50 @@ class SGM:
         k = ctypes.c_int()
         check(self._lib.sgm_post_filter_proved_at(self._h, ctypes.byref(k)), self._h)
         return k.value
+
+    # --------------------------------------------------------- confidence
+    def set_confidence(self, enable: bool) -> None:
+        """sgm_set_confidence: keep (or stop keeping) the per-pixel match
+        confidence of every later frame: min_cost / sec_min_cost of the
+        aggregated WTA (SGM.cpp:392-409), in [0, 1), lower = more distinctive.
+        Not inside stream capture; BM and aux_only handles raise."""
+        check(self._lib.sgm_set_confidence(self._h, int(bool(enable))), self._h)
+
+    def get_confidence(self, view: int = 0) -> np.ndarray:
+        """The last frame's ratio map of `view` (0 = left, 1 = right; a
+        one-view handle serves its own view only): rows x cols float32
+        (sgm_stage_confidence; synchronous)."""
+        out = np.empty((self.rows, self.cols), np.float32)
+        check(self._lib.sgm_stage_confidence(self._h, int(view), _ptr(out)), self._h)
+        return out
+
+    def confidence_device(self, d_ratio: int, *, view: int = 0, pitch: int | None = None,
+                          stream: int | None = None) -> None:
+        """The same map into a row-major device buffer (sgm_confidence_device:
+        enqueue only, capturable with the frame)."""
+        check(self._lib.sgm_confidence_device(self._h, int(view), ctypes.c_void_p(d_ratio),
+                                              pitch or self.cols, _stream(stream)), self._h)
+
+    def confidence_filter_device(self, d_disp: int, d_ratio: int, max_ratio: float, *,
+                                 pitch: int | None = None, ratio_pitch: int | None = None,
+                                 stream: int | None = None) -> None:
+        """In place on a device map: disp = D+1 where ratio > max_ratio
+        (sgm_confidence_filter_device)."""
+        check(self._lib.sgm_confidence_filter_device(
+            self._h, ctypes.c_void_p(d_disp), pitch or self.cols, ctypes.c_void_p(d_ratio),
+            ratio_pitch or self.cols, ctypes.c_float(max_ratio), _stream(stream)), self._h)
+
+    def confidence_filter(self, disp, ratio, max_ratio: float) -> np.ndarray:
+        """A stricter uniqueness without re-running the frame: a copy of
+        `disp` with D+1 where ratio > max_ratio, computed on the GPU.  (The
+        WTA's |min_d - sec_d| > 1 clause is not reproduced.)"""
+        f = np.array(disp, dtype=np.float32, copy=True, order="C")
+        r = np.ascontiguousarray(ratio, dtype=np.float32)
+        if f.shape != (self.rows, self.cols) or r.shape != f.shape:
+            raise ValueError(f"disp and ratio: expected shape {(self.rows, self.cols)}")
+        check(self._lib.sgm_stage_confidence_filter(self._h, _ptr(f), _ptr(r),
+                                                    ctypes.c_float(max_ratio)), self._h)
+        return f
 
     def get_disp(self) -> np.ndarray:
         """Post-filtered disparity (inc/Solver.h:36: filtered_disp after
