@@ -12,7 +12,9 @@
 // configured size is the images' size.  The calibration (read_calib,
 // utils.cpp:59-89) comes from the command line.  Every stage runs on the GPU.
 //
-// usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX [scale] [max_disp] [fx fy cx cy]
+// usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX [scale max_disp [fx fy cx cy [min_disp]]]
+// min_disp (not in the node): search disparities [min_disp, min_disp + max_disp);
+// the map, the debug view and the cloud are then in true disparity.
 #include "sgm_amd/SGM.h"
 #include "sgm_amd/SkyAreaDetector.h"
 
@@ -56,8 +58,9 @@ static bool write_ppm(const std::string &path, const Mat &bgr) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 4 && argc != 6 && argc != 10) {
-        std::fprintf(stderr, "usage: %s LEFT.pgm RIGHT.pgm OUT_PREFIX [scale max_disp [fx fy cx cy]]\n",
+    if (argc != 4 && argc != 6 && argc != 10 && argc != 11) {
+        std::fprintf(stderr,
+                     "usage: %s LEFT.pgm RIGHT.pgm OUT_PREFIX [scale max_disp [fx fy cx cy [min_disp]]]\n",
                      argv[0]);
         return 2;
     }
@@ -69,6 +72,7 @@ int main(int argc, char **argv) {
     cam.fy = argc > 7 ? (float)std::atof(argv[7]) : 721.5377f;
     cam.cx = argc > 8 ? (float)std::atof(argv[8]) : 609.5593f;
     cam.cy = argc > 9 ? (float)std::atof(argv[9]) : 172.854f;
+    const int min_disp = argc > 10 ? std::atoi(argv[10]) : 0;   // sgm_set_min_disp
     cam.baseline = 0.5;    // node.cpp:123
     cam.max_range = 100;   // node.cpp:122
 
@@ -82,7 +86,7 @@ int main(int argc, char **argv) {
     std::printf("left size: %d, %d\nright size: %d, %d\n", h, w, img_r.rows, img_r.cols);
 
     // node.cpp:49-51
-    sgm_amd::SolverPtr sv = std::make_shared<sgm_amd::SGM>(h, w, scale, max_disp);
+    sgm_amd::SolverPtr sv = std::make_shared<sgm_amd::SGM>(h, w, scale, max_disp, 8, min_disp);
     SkyDetPtr sky_det = std::make_shared<sky_detector::SkyAreaDetector>();
 
     Mat sky_mask, sky_mask_beta;  // node.cpp:80-87 (no debug image is written)

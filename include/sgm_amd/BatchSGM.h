@@ -49,8 +49,11 @@ public:
     // handle (sgm_set_post_filter_launches; 0 = the adaptive fill).  With a
     // budget no device thread blocks inside its frame: it enqueues the frame
     // and waits once, in sgm_check, which also reports an unproven fill.
-    BatchSGM(const std::vector<int> &devices, int h, int w, int s, int d, int post_filter_launches = 0)
-        : in_h_(h), in_w_(w) {
+    // min_disp: every handle searches disparities [min_disp, min_disp + d)
+    // (sgm_set_min_disp): true-disparity maps, invalid = invalid_disp().
+    BatchSGM(const std::vector<int> &devices, int h, int w, int s, int d, int post_filter_launches = 0,
+             int min_disp = 0)
+        : in_h_(h), in_w_(w), invalid_disp_(d + min_disp + 1) {
         if (devices.empty()) fail("BatchSGM", "no devices");
         sgm_params p;
         if (sgm_default_params(&p, h, w, s, d) != SGM_OK) fail("BatchSGM", "sgm_default_params");
@@ -63,7 +66,8 @@ public:
                 release();
                 fail("BatchSGM", "sgm_create failed (see stderr)");
             }
-            if (sgm_set_post_filter_launches(sl.h, post_filter_launches) != SGM_OK) {
+            if (sgm_set_post_filter_launches(sl.h, post_filter_launches) != SGM_OK ||
+                (min_disp != 0 && sgm_set_min_disp(sl.h, min_disp) != SGM_OK)) {
                 const std::string why = sgm_last_error(sl.h);
                 release();
                 fail("BatchSGM", why.c_str());
@@ -99,9 +103,12 @@ public:
     BatchSGM &operator=(const BatchSGM &) = delete;
 
     int devices() const { return (int)slots_.size(); }
+    // the value of an invalid pixel of every map: d + min_disp + 1
+    int invalid_disp() const { return invalid_disp_; }
 
     // process(left[k], right[k]) for every pair k (node.cpp:93); afterwards
-    // get_disp(k) is pair k's map (CV_32FC1, rows x cols, invalid = d+1).
+    // get_disp(k) is pair k's map (CV_32FC1, rows x cols, invalid = d+1, or
+    // d + min_disp + 1: invalid_disp()).
     void process(const std::vector<Mat> &left, const std::vector<Mat> &right) {
         check_batch(left, right, in_h_, in_w_);
         const size_t n = slots_.size();
@@ -194,6 +201,7 @@ private:
     float *h_stage_[2] = {nullptr, nullptr};
     hipEvent_t ev_copied_[2] = {nullptr, nullptr};
     int in_h_, in_w_, rows_ = 0, cols_ = 0;
+    int invalid_disp_;
     std::vector<Mat> disp_;
 
     size_t map_bytes() const { return (size_t)rows_ * cols_ * sizeof(float); }

@@ -40,6 +40,8 @@ namespace sgm_amd {
 class GPU_SGM : private HipSolver {
 public:
     explicit GPU_SGM(int h, int w, int s, int d) : HipSolver(h, w, s, d, SGM_SOLVER_SGM, 1) {}
+    // min_disp (not in the reference): disparities [min_disp, min_disp + d), sgm_set_min_disp
+    GPU_SGM(int h, int w, int s, int d, int min_disp) : HipSolver(h, w, s, d, SGM_SOLVER_SGM, 1, 8, min_disp) {}
     virtual ~GPU_SGM() = default;
 
     GPU_SGM(const GPU_SGM &) = delete;
@@ -50,7 +52,8 @@ public:
     virtual void show_disp(Mat &debug_view) {
         // left border invalid (SGM.cu:238-246): columns without a full
         // disparity range
-        const int cols = max_disp / scale < img_w ? max_disp / scale : img_w;
+        const int reach = (max_disp + min_disp) / scale;
+        const int cols = reach < img_w ? reach : img_w;
         for (int i = 0; i < filtered_disp.rows; ++i) {
             float *row = filtered_disp.template ptr<float>(i);
             for (int j = 0; j < cols; ++j) row[j] = (float)invalid_disp;
@@ -60,6 +63,7 @@ public:
     virtual const Mat &get_disp() const { return filtered_disp; }
 
     using HipSolver::handle;
+    using Solver::get_invalid_disp;
 };
 
 typedef std::shared_ptr<GPU_SGM> GSGMPtr;

@@ -23,7 +23,9 @@ namespace sgm_amd {
 
 class LKSubPixel {
 public:
-    explicit LKSubPixel(int h, int w, int s, int d) : h_(h), w_(w), s_(s), d_(d) {
+    // min_disp: the maps to refine come from handles created with it
+    // (sgm_set_min_disp): a disparity x is valid when 0 < x < d + min_disp
+    explicit LKSubPixel(int h, int w, int s, int d, int min_disp = 0) : h_(h), w_(w), s_(s), d_(d) {
         if (!(h > 0 && w > 0 && s > 0 && d > 0) || (s != 1 && s != 2) ||
             (d != 32 && d != 64 && d != 128 && d != 256))
             fail("LKSubPixel", "h,w,s,d > 0, s in {1,2}, d in {32,64,128,256} (LKSubPixel.cpp:5-12)");
@@ -33,6 +35,8 @@ public:
         const char *e = std::getenv("SGM_AMD_DEVICE");
         if (sgm_create(&p, e ? std::atoi(e) : 0, &handle_) != SGM_OK)
             fail("LKSubPixel", handle_ ? sgm_last_error(handle_) : "sgm_create failed");
+        if (min_disp != 0 && sgm_set_min_disp(handle_, min_disp) != SGM_OK)
+            fail("LKSubPixel", sgm_last_error(handle_));
     }
     virtual ~LKSubPixel() {
         if (handle_) sgm_destroy(handle_);
@@ -40,8 +44,8 @@ public:
     LKSubPixel(const LKSubPixel &) = delete;
     LKSubPixel &operator=(LKSubPixel &) = delete;
 
-    static std::shared_ptr<LKSubPixel> create(int h, int w, int s, int d) {
-        return std::make_shared<LKSubPixel>(h, w, s, d);
+    static std::shared_ptr<LKSubPixel> create(int h, int w, int s, int d, int min_disp = 0) {
+        return std::make_shared<LKSubPixel>(h, w, s, d, min_disp);
     }
 
     virtual void LKRefine(const Mat &img_l, const Mat &img_r, Mat &disp_float) {

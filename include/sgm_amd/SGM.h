@@ -10,6 +10,10 @@
  *   SGM(h, w, s, d)              Solver.cpp:4-16   (asserts: h,w,s,d > 0,
  *                                s in {1,2}, d in {32,64,128} -- widened to 256)
  *   SGM(h, w, s, d, paths)       inc/SGM.h:7        (paths = 4: USE_8_PATH = false; 8: as above)
+ *   SGM(h, w, s, d, paths, m)    (not in the reference) min_disp = m: disparities [m, m + d)
+ *                                are searched, get_disp() is in true disparity and
+ *                                invalid = d + m + 1 (get_invalid_disp()); a sky pixel
+ *                                reports m; BM takes no min_disp (sgm_set_min_disp)
  *   process(l, r)                SGM.cpp:32-826     (LR-checked, post-filtered)
  *   process(l, r, sky, sky_b)    SGM.cpp:829-834    (masks kept as members)
  *   BM(h, w, s, d)               BM.cpp:4-97        (filtered-cost WTA, post-filtered)
@@ -119,15 +123,19 @@ inline void fail(const char *what, const char *detail) {
 // Solver (inc/Solver.h:23-70): geometry, result maps and the device handle.
 class Solver {
 public:
-    explicit Solver(int h, int w, int s, int d) {
+    // m: the minimum disparity, sgm_set_min_disp (0: the reference's range [0, d))
+    explicit Solver(int h, int w, int s, int d, int m = 0) {
         if (!(h > 0 && w > 0 && s > 0 && d > 0) || !(s == 1 || s == 2) ||
             !(d == 32 || d == 64 || d == 128 || d == 256))
             fail("Solver", "h,w,s,d > 0, s in {1,2}, d in {32,64,128,256} (Solver.cpp:6-10)");
+        if (m < 0 || m % s != 0 || d + m + 1 > 65535)
+            fail("Solver", "min_disp must be >= 0, a multiple of s and d + min_disp + 1 <= 65535");
         img_h = h / s;
         img_w = w / s;
         scale = s;
         max_disp = d;
-        invalid_disp = d + 1;
+        min_disp = m;
+        invalid_disp = d + m + 1;
         in_h_ = h;
         in_w_ = w;
         filtered_disp.create(img_h, img_w, CV_32FC1);
@@ -157,11 +165,15 @@ public:
                         colored_disp.template ptr<Vec3b>(i), (size_t)img_w * 3);
     }
     virtual const Mat &get_disp() const { return filtered_disp; }
+    // the value of an invalid pixel of get_disp(): d + min_disp + 1 (Solver.cpp:21 with min_disp = 0)
+    int get_invalid_disp() const { return invalid_disp; }
+    int get_min_disp() const { return min_disp; }
 
 protected:
     int img_h, img_w;
     int scale;
     int max_disp, invalid_disp;
+    int min_disp;
     int in_h_, in_w_;
 
     Mat img_l, img_r;
@@ -169,11 +181,11 @@ protected:
     Mat colored_disp;
     Mat sky_mask, sky_mask_beta;
 
-    // Solver.cpp:652-707
+    // Solver.cpp:652-707 (on v - min_disp: the colours span the search range)
     void colormap() {
         for (int i = 0; i < img_h; ++i)
             for (int j = 0; j < img_w; ++j) {
-                float v = filtered_disp.template at<float>(i, j);
+                float v = filtered_disp.template at<float>(i, j) - (float)min_disp;
                 Vec3b &c = colored_disp.template at<Vec3b>(i, j);
                 if (v > max_disp - 1) {
                     c[0] = c[1] = c[2] = 0;
@@ -282,9 +294,11 @@ public:
 protected:
     // views = 1: the left view alone (BM; GPU_SGM, gpu_sgm/src/SGM.cu:105-232)
     // paths = 4: the reference built with USE_8_PATH = false (inc/SGM.h:7)
-    HipSolver(int h, int w, int s, int d, int solver, int views = 2, int paths = 8)
-        : Solver(h, w, s, d), bm_(solver == SGM_SOLVER_BM) {
+    // min_disp: the search range starts there (sgm_set_min_disp; BM: 0 only)
+    HipSolver(int h, int w, int s, int d, int solver, int views = 2, int paths = 8, int min_disp = 0)
+        : Solver(h, w, s, d, min_disp), bm_(solver == SGM_SOLVER_BM) {
         if (paths != 4 && paths != 8) fail("Solver", "paths must be 4 or 8 (USE_8_PATH, inc/SGM.h:7)");
+        if (bm_ && min_disp != 0) fail("Solver", "BM takes no min_disp");
         sgm_params p;
         if (sgm_default_params(&p, h, w, s, d) != SGM_OK) fail("Solver", "sgm_default_params");
         p.solver = solver;
@@ -293,6 +307,9 @@ protected:
         p.views = bm_ ? 1 : views;
         const int rc = sgm_create(&p, device(), &handle_);
         if (rc != SGM_OK) fail("sgm_create", handle_ ? sgm_last_error(handle_) : "no device");
+        if (min_disp != 0 && sgm_set_min_disp(handle_, min_disp) != SGM_OK)
+            fail("sgm_set_min_disp", sgm_last_error(handle_));
+        if (sgm_get_invalid_disp(handle_, &invalid_disp) != SGM_OK) fail("Solver", "sgm_get_invalid_disp");
     }
 
 private:
@@ -330,6 +347,9 @@ public:
     explicit SGM(int h, int w, int s, int d) : HipSolver(h, w, s, d, SGM_SOLVER_SGM) {}
     // paths = 4: the reference's USE_8_PATH = false (inc/SGM.h:7), S = ((L1+L2)+L3)+L4
     SGM(int h, int w, int s, int d, int paths) : HipSolver(h, w, s, d, SGM_SOLVER_SGM, 2, paths) {}
+    // min_disp = m: disparities [m, m + d), true-disparity maps, invalid = d + m + 1
+    SGM(int h, int w, int s, int d, int paths, int min_disp)
+        : HipSolver(h, w, s, d, SGM_SOLVER_SGM, 2, paths, min_disp) {}
     SGM(const SGM &) = delete;
     SGM &operator=(const SGM &) = delete;
 };

@@ -155,6 +155,35 @@ int sgm_destroy(sgm_handle *h);
 const char *sgm_last_error(const sgm_handle *h);
 /* Working (decimated) size: rows = height/scale, cols = width/scale. */
 int sgm_get_size(const sgm_handle *h, int *rows, int *cols, int *max_disp);
+/* ---- minimum disparity: search [m, m + D) instead of [0, D) ----
+ *
+ * A property of the handle (like sgm_set_confidence; sgm_params and
+ * SGM_HIP_VERSION are unchanged), normally set once, right after sgm_create;
+ * m = 0 is every handle's default and runs exactly as before (OpenCV SGBM's
+ * minDisparity).  With m set, index d of every cost volume stands for
+ * disparity m + d: the left view's DSI (Solver.cpp:143-194) reads
+ * ctR[i, max(j - (d+m)/s, 0)], the right view's (:197-248)
+ * ctL[i, min(j + (d+m)/s, W-1)]; filters, paths, aggregation, WTA,
+ * uniqueness, sub-pixel and the confidence quotient run unchanged on those
+ * volumes, and every map that leaves the library is in TRUE disparity: sub =
+ * index-space value + (float)m (one fp32 add, every pixel), raw = index + m,
+ * so the invalid marker is D + m + 1.  The LR check, post_filter, LKRefine,
+ * the confidence filter, the colormap and the point cloud (in frames and as
+ * device or stage calls on any handle set to the same m, aux_only included)
+ * work on such maps as the reference's functions do when called with D + m
+ * for D.  The sky override stays in index space: a sky pixel wins index 0
+ * and so reports disparity m, not 0.
+ * SGM_ERR_INVALID_ARG, with a message, for m < 0, m not a multiple of scale,
+ * D + m + 1 > 65535 (the raw u16 map), and any m != 0 on a BM handle (BM has
+ * no staged oracle to derive the definition from).  Allocates (m != 0) or
+ * frees (m = 0) two shifted census tables, 16 B per pixel together, counted in
+ * the handle's device bytes; a frame then runs one small launch more.
+ * Synchronises the handle's last work first; call it outside stream capture,
+ * and re-capture graphs afterwards. */
+int sgm_set_min_disp(sgm_handle *h, int m);
+/* The value that marks an invalid pixel in every float map of this handle:
+ * max_disp + min_disp + 1 (D + 1 by default, Solver.cpp:21). */
+int sgm_get_invalid_disp(const sgm_handle *h, int *invalid);
 /* Bytes of device memory the handle holds. */
 size_t sgm_device_bytes(const sgm_handle *h);
 /* The handle's own stream (a hipStream_t; what a NULL stream argument
@@ -172,7 +201,8 @@ void *sgm_get_stream(const sgm_handle *h);
  *   sky_l/sky_r: u8 masks on the working grid (rows x cols), 255 = sky; may be
  *                NULL (Solver.cpp:146)
  *   out        : f32 rows x cols, LR-checked sub-pixel disparity
- *                (filtered_disp after SGM.cpp:818), invalid = D+1; with
+ *                (filtered_disp after SGM.cpp:818), invalid = D+1 (true
+ *                disparity and D + min_disp + 1 with a minimum disparity set); with
  *                params.post_filter it is then post_filter()ed on the GPU
  *                (SGM.cpp:821, what get_disp() returns); with views == 1 it
  *                is the left sub-pixel map (SGM.cpp:443), or the right one
@@ -329,7 +359,8 @@ int sgm_sky_detect_device(sgm_handle *h, const uint8_t *d_img, int pitch, uint8_
 
 /* Solver::colormap (src/Solver.cpp:652-707) of a DEVICE working-grid map
  * (rows x cols f32, pitch in floats) into DEVICE BGR (rows x cols x 3 u8,
- * bgr_pitch bytes): the image show_disp publishes (Solver.cpp:55-93). */
+ * bgr_pitch bytes): the image show_disp publishes (Solver.cpp:55-93).  With
+ * a minimum disparity m set the colours are those of disp - (float)m over D. */
 int sgm_colormap_device(sgm_handle *h, const float *d_disp, int pitch, uint8_t *d_bgr,
                         int bgr_pitch, void *stream);
 
@@ -418,7 +449,9 @@ int sgm_get_profile(sgm_handle *h, sgm_kernel_stat *out, int max, int *count);
 int sgm_stage_census(sgm_handle *h, const uint8_t *img, int pitch, uint64_t *ct);
 /* build_dsi_from_table[_beta] + filters (Solver.cpp:143-248, 296-368).
  * view 0 = left, 1 = right; filters bit 1 = horizontal, bit 2 = vertical.
- * cost: rows x cols x D f32. */
+ * cost: rows x cols x D f32.  ctl/ctr are unshifted tables (sgm_stage_census):
+ * with a minimum disparity m set the stage applies its view's shift, so
+ * cost[.., d] is the cost of disparity m + d. */
 int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr,
                    const uint8_t *sky, int view, int filters, float *cost);
 /* One path DP over a cost volume (SGM.cpp:81-369): L (rows x cols x D) and
@@ -426,7 +459,8 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr,
  * returns SGM_ERR_INVALID_ARG for L5..L8. */
 int sgm_stage_path(sgm_handle *h, int dir, const float *cost, float *L, float *minL);
 /* 8 paths (4 with params.paths == 4: ((L1+L2)+L3)+L4) + aggregation + WTA +
- * uniqueness + sub-pixel (SGM.cpp:81-443). */
+ * uniqueness + sub-pixel (SGM.cpp:81-443).  disp and sub leave in true
+ * disparity (+ the handle's minimum disparity). */
 int sgm_stage_aggregate(sgm_handle *h, const float *cost, uint16_t *disp, float *sub);
 /* sgm_confidence_device with a HOST buffer: ratio rows x cols f32 (dense), the
  * map of `view` left by the last frame or sgm_stage_aggregate (view 0 of a

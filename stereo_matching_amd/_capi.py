@@ -39,6 +39,7 @@ EXPORTS = (
     "sgm_set_post_filter_launches", "sgm_post_filter_proved_at",
     "sgm_set_confidence", "sgm_confidence_device", "sgm_stage_confidence",
     "sgm_confidence_filter_device", "sgm_stage_confidence_filter",
+    "sgm_set_min_disp", "sgm_get_invalid_disp",
 )
 SGM_COMM_ID_BYTES = 128
 
@@ -150,6 +151,8 @@ def lib():
     L.sgm_last_error.argtypes = [P]
     L.sgm_last_error.restype = ctypes.c_char_p
     L.sgm_get_size.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)]
+    L.sgm_set_min_disp.argtypes = [P, I]
+    L.sgm_get_invalid_disp.argtypes = [P, ctypes.POINTER(I)]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

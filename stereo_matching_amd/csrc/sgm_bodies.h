@@ -493,7 +493,7 @@ __device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, 
             lds_barrier();
             for (int c = 0; c < nseg; ++c) {
                 wta_consume_chunk<V, K>(tb[c & 1], pb[c & 1], c == nseg - 1 ? r0 : K, lane,
-                                        g.D, a.uniq, a.disp, a.sub, a.ratio);
+                                        g.D, a.uniq, a.disp, a.sub, a.ratio, a.min_disp);
                 lds_barrier();
             }
             return;
@@ -1030,7 +1030,7 @@ __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g
             const long long row_top = H - c * K - (half + 1) * KP;
             wta_chunk_q<V, KP, QQ>(x, F->t[c & 1] + half * KP, row_top * W + path, o_off,
                                    a.sub_cm ? (long long)path * H + row_top : row_top * W + path,
-                                   s_off, cnt, lane, g.D, a.uniq, a.disp, a.sub, a.ratio);
+                                   s_off, cnt, lane, g.D, a.uniq, a.disp, a.sub, a.ratio, a.min_disp);
             bar();
         };
         if constexpr (NOT) {
@@ -1049,7 +1049,7 @@ __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g
                 const long long row_top = H - c * K - (half + 1) * KP;
                 wta_chunk_q<V, KP, QQ>(x, F->t[c & 1] + half * KP, row_top * W + path, o_off,
                                        a.sub_cm ? (long long)path * H + row_top : row_top * W + path,
-                                       s_off, cnt, lane, g.D, a.uniq, a.disp, a.sub, a.ratio);
+                                       s_off, cnt, lane, g.D, a.uniq, a.disp, a.sub, a.ratio, a.min_disp);
                 bar();
             };
             bar();

@@ -30,6 +30,9 @@ using sgm::SweepArgs;
 struct sgm_handle {
     sgm_params p;
     Geom g;
+    Geom gt;              // g with D + min_disp for D: the geometry of every stage that works on
+                          // true-disparity maps (LR check, post filter, LKRefine, confidence
+                          // filter, point cloud: valid <= D+m-1, invalid D+m+1)
     int device;
     int nviews;
     size_t bytes;
@@ -41,6 +44,10 @@ struct sgm_handle {
     uint8_t *d_in[2];     // full-size input staging (host API)
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
+    int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
+    uint64_t *d_cts[2];   // the tables shifted by min_disp / scale columns (launch_ct_shift):
+                          // [0] the left image's (the right view's DSI reads it), [1] the right
+                          // image's (the left view's); min_disp = 0: d_ct[0], d_ct[1] themselves
     float *d_ch[2];       // horizontally filtered cost; reused as the T chain
     float *d_ch_base[2];  // its allocation: d_ch is preceded by t_guard_rows rows (final pass)
     float *d_c[2];        // final cost volume (+ kVolGuard: row-walking prefetch rings)
@@ -229,7 +236,9 @@ int dalloc(sgm_handle *h, T **p, size_t count) {
 
 void free_all(sgm_handle *h) {
     for (int v = 0; v < 2; ++v) {
-        (void)hipFree(h->d_in[v]); (void)hipFree(h->d_sky[v]); (void)hipFree(h->d_ct[v]);
+        (void)hipFree(h->d_in[v]); (void)hipFree(h->d_sky[v]);
+        if (h->d_cts[v] != h->d_ct[v]) (void)hipFree(h->d_cts[v]);  // (min_disp = 0: an alias)
+        (void)hipFree(h->d_ct[v]);
         (void)hipFree(h->d_ch_base[v]); (void)hipFree(h->d_c[v]); (void)hipFree(h->d_s[v]);
         for (auto &c : h->d_carry[v]) (void)hipFree(c);
         (void)hipFree(h->d_l3[v]);
@@ -330,7 +339,23 @@ sgm::PairArgs pair_args(const sgm_handle *h) {
     a.p1 = (float)h->p.p1;
     a.p2 = (float)h->p.p2;
     a.uniq = h->p.uniqueness;
+    a.min_disp = h->min_disp;
     return a;
+}
+
+// the census table pair of a DSI (0: left view, 1: right view): the other
+// image's table is the min_disp-shifted one
+inline const uint64_t *ct_left(const sgm_handle *h, int dsi) { return dsi ? h->d_cts[0] : h->d_ct[0]; }
+inline const uint64_t *ct_right(const sgm_handle *h, int dsi) { return dsi ? h->d_ct[1] : h->d_cts[1]; }
+// The shifted tables after a census (or an upload) wrote d_ct; nothing at min_disp = 0
+int shift_tables(sgm_handle *h, bool left, bool right, hipStream_t st) {
+    if (h->min_disp == 0) return SGM_OK;
+    HIPCHK(h, timed(h, "ct_shift", (double)((left ? 1 : 0) + (right ? 1 : 0)) * h->g.H * h->g.W, st, [&] {
+               return sgm::launch_ct_shift(h->d_ct[0], h->d_ct[1], left ? h->d_cts[0] : nullptr,
+                                           right ? h->d_cts[1] : nullptr, h->min_disp / h->g.scale,
+                                           h->g, st);
+           }));
+    return SGM_OK;
 }
 
 hipError_t pair_fwd(sgm_handle *h, int fam, const sgm::PairArgs &a, hipStream_t st) {
@@ -631,8 +656,8 @@ int cost_view(sgm_handle *h, int view, int dsi, const uint8_t *sky, int sky_pitc
               bool vfwd = true) {
     const double elems = (double)h->g.H * h->g.W * h->g.D;
     HIPCHK(h, timed(h, "cost_h", elems, st, [&] {
-               return sgm::launch_cost_h(h->d_ct[0], h->d_ct[1], sky, sky_pitch, dsi, 1, h->g,
-                                         h->d_ch[view], st);
+               return sgm::launch_cost_h(ct_left(h, dsi), ct_right(h, dsi), sky, sky_pitch, dsi, 1,
+                                         h->g, h->d_ch[view], st);
            }));
     return vfwd ? vfwd_view(h, view, st) : SGM_OK;
 }
@@ -754,6 +779,7 @@ int slant_views(sgm_handle *h, float *sub0, uint16_t *raw, hipStream_t st, bool 
     sa.p1 = (float)h->p.p1;
     sa.p2 = (float)h->p.p2;
     sa.uniq = h->p.uniqueness;
+    sa.min_disp = h->min_disp;
     sa.nviews = nv;
     sa.err_host = h->d_slant_err;
 #ifdef SGM_SLANT_DEBUG
@@ -842,6 +868,9 @@ int run_frame(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int 
                return sgm::launch_census(d_left, pitch, g, h->p.blur, h->d_ct[0], st, false,
                                          d_right, h->d_ct[1]);
            }));
+    // min_disp: the shifted table(s) the views' DSIs read (the left view the
+    // right image's, the right view the left image's)
+    if ((rc = shift_tables(h, h->nviews == 2 || right_only, !right_only, st)) != SGM_OK) return rc;
     // two views: both DSIs + horizontal IIRs in one launch (a view's H*D
     // serial chains alone leave most SIMDs idle at KITTI sizes)
     const bool both_h = h->nviews == 2 && (d_sky_l == nullptr) == (d_sky_r == nullptr) &&
@@ -861,12 +890,15 @@ int run_frame(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int 
     if (vstrip) {
         const int dsi0 = right_only ? 1 : 0;
         HIPCHK(h, timed(h, "cost_ck", h->nviews * npx * g.D, st, [&] {
-                   return sgm::launch_cost_ck(h->d_ct[0], h->d_ct[1], sky0, d_sky_r, sky_pitch, dsi0, 1,
-                                              h->nviews, g, h->d_ch[0], h->d_ch[1], st);
+                   return sgm::launch_cost_ck(h->d_ct[0], h->d_ct[1], h->d_cts[0], h->d_cts[1], sky0,
+                                              d_sky_r, sky_pitch, dsi0, 1, h->nviews, g, h->d_ch[0],
+                                              h->d_ch[1], st);
                }));
         sgm::VStripArgs va{};
         va.ctl = h->d_ct[0];
         va.ctr = h->d_ct[1];
+        va.ctl_s = h->d_cts[0];
+        va.ctr_s = h->d_cts[1];
         if (sky0) {
             const uint8_t *skm[2] = {sky0, d_sky_r};
             uint64_t *skw[2] = {nullptr, nullptr};
@@ -893,8 +925,8 @@ int run_frame(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int 
                         [&] { return sgm::launch_vstrip(va, h->nviews, g, st); }));
     } else if (both_h) {
         HIPCHK(h, timed(h, "cost_h", 2.0 * npx * g.D, st, [&] {
-                   return sgm::launch_cost_h2(h->d_ct[0], h->d_ct[1], d_sky_l, d_sky_r, sky_pitch, g,
-                                              h->d_ch[0], h->d_ch[1], st);
+                   return sgm::launch_cost_h2(h->d_ct[0], h->d_ct[1], h->d_cts[0], h->d_cts[1], d_sky_l,
+                                              d_sky_r, sky_pitch, g, h->d_ch[0], h->d_ch[1], st);
                }));
         if (vfwd_here) {
             // both views' vertical passes in one launch: W chains per view
@@ -971,10 +1003,11 @@ int run_frame(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int 
     }
     if (h->nviews == 2) {
         HIPCHK(h, timed(h, "lr", npx, st, [&] {
+                   // (true-disparity maps: the invalid marker is D + min_disp + 1)
                    return cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], d_out, out_pitch,
-                                                 h->p.lr_max_diff, g, st)
+                                                 h->p.lr_max_diff, h->gt, st)
                              : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, d_out, out_pitch,
-                                              h->p.lr_max_diff, g, st);
+                                              h->p.lr_max_diff, h->gt, st);
                }));
     } else if (!direct_out) {
         HIPCHK(h, hipMemcpy2DAsync(d_out, (size_t)out_pitch * sizeof(float), h->d_sub[0],
@@ -1039,7 +1072,7 @@ void pack_rows(uint8_t *dst, const uint8_t *src, size_t row_bytes, int rows, siz
 // to_lk: write the filtered map to d_lk_in (contiguous) instead of d_map, for
 // lk_refine(..., staged = true) to read.
 int post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_lk) {
-    const Geom g = h->g;
+    const Geom g = h->gt;  // (a true-disparity map: valid <= D + min_disp - 1)
     const int budget = h->pf_launches;
     // The number of median-fill launches depends on a counter read back to
     // the host each round; under stream capture that copy never runs, so a
@@ -1125,7 +1158,7 @@ int post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_
 // staged: d_lk_in already holds the map (post_filter(..., to_lk = true))
 int lk_refine(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int pitch,
               float *d_map, int map_pitch, hipStream_t st, bool staged) {
-    const Geom g = h->g;
+    const Geom g = h->gt;  // (DispValid: 0 < d < D + min_disp)
     const size_t row = (size_t)g.W * sizeof(float);
     if (!staged)
         HIPCHK(h, hipMemcpy2DAsync(h->d_lk_in, row, d_map, (size_t)map_pitch * sizeof(float), row,
@@ -1184,6 +1217,7 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
     h->g.H = p->height / p->scale;
     h->g.W = p->width / p->scale;
     h->g.D = p->max_disp;
+    h->gt = h->g;  // (min_disp = 0 until sgm_set_min_disp)
     h->nviews = p->views;
     const size_t npx = (size_t)h->g.H * h->g.W;
     const size_t nvol = npx * h->g.D;
@@ -1221,6 +1255,7 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
             if ((rc = dalloc(h, &h->d_in[v], nin))) break;
             if ((rc = dalloc(h, &h->d_sky[v], npx))) break;
             if ((rc = dalloc(h, &h->d_ct[v], npx))) break;
+            h->d_cts[v] = h->d_ct[v];  // (min_disp = 0: the tables themselves)
         }
         for (int v = 0; v < (p->aux_only ? 0 : h->nviews) && !rc; ++v) {
             // the final pass addresses T (which reuses d_ch) in chunks from
@@ -1438,6 +1473,59 @@ static int view_slot(const sgm_handle *h, int view) {
     return view == h->p.view ? 0 : -1;  // (a right-view handle runs in slot 0)
 }
 
+int sgm_set_min_disp(sgm_handle *h, int m) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    // The shifted census tables move by whole working-grid columns, and the
+    // raw u16 map must hold the invalid marker D + m + 1
+    if (m < 0) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_min_disp: min_disp must be >= 0, got %d", m);
+    if (m % h->g.scale != 0)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_min_disp: min_disp must be a multiple of scale (the tables shift by "
+                       "min_disp / scale columns)");
+    if ((long long)h->g.D + m + 1 > 65535)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_min_disp: max_disp + min_disp + 1 must fit the raw u16 map (<= 65535)");
+    if (h->p.solver == SGM_SOLVER_BM && m != 0)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_min_disp: not supported by the BM solver");
+    DeviceGuard guard(h->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_min_disp: call it outside stream capture");
+    if (m == h->min_disp) return SGM_OK;
+    // frames in flight still read the tables and the handle's geometry
+    if (int rc = wait_last(h)) return rc;
+    const size_t npx = (size_t)h->g.H * h->g.W;
+    // each image's shifted table (16 B per pixel for both; frames write the
+    // ones their views read, sgm_stage_cost its view's); at 0 the tables
+    // themselves, nothing allocated.  (aux_only handles compute no cost.)
+    const bool want = m != 0 && !h->p.aux_only, have = h->d_cts[0] != h->d_ct[0];
+    if (want && !have) {
+        uint64_t *t[2] = {nullptr, nullptr};
+        int rc = dalloc(h, &t[0], npx);
+        if (!rc) rc = dalloc(h, &t[1], npx);
+        if (rc) {
+            for (auto q : t)
+                if (q) {
+                    (void)hipFree(q);
+                    h->bytes -= npx * sizeof(uint64_t);
+                }
+            return rc;
+        }
+        h->d_cts[0] = t[0];
+        h->d_cts[1] = t[1];
+    } else if (!want && have) {
+        for (int v = 0; v < 2; ++v) {
+            (void)hipFree(h->d_cts[v]);
+            h->bytes -= npx * sizeof(uint64_t);
+            h->d_cts[v] = h->d_ct[v];
+        }
+    }
+    h->min_disp = m;
+    h->gt.D = h->g.D + m;
+    return SGM_OK;
+}
+
 int sgm_set_confidence(sgm_handle *h, int enable) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
@@ -1517,7 +1605,7 @@ int sgm_confidence_filter_device(sgm_handle *h, float *d_disp, int pitch, const 
     StreamScope scope(h, stream);
     hipStream_t st = scope.st;
     HIPCHK(h, timed(h, "confidence_filter", (double)h->g.H * h->g.W, st, [&] {
-               return sgm::launch_confidence_filter(d_disp, pitch, d_ratio, ratio_pitch, max_ratio, h->g,
+               return sgm::launch_confidence_filter(d_disp, pitch, d_ratio, ratio_pitch, max_ratio, h->gt,
                                                     st);
            }));
     return SGM_OK;
@@ -1530,7 +1618,7 @@ int sgm_stage_confidence_filter(sgm_handle *h, float *disp, const float *ratio, 
     const size_t npx = (size_t)h->g.H * h->g.W;
     HIPCHK(h, hipMemcpyAsync(h->d_out, disp, npx * 4, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, hipMemcpyAsync(h->d_pf_work, ratio, npx * 4, hipMemcpyHostToDevice, h->st));
-    HIPCHK(h, sgm::launch_confidence_filter(h->d_out, h->g.W, h->d_pf_work, h->g.W, max_ratio, h->g,
+    HIPCHK(h, sgm::launch_confidence_filter(h->d_out, h->g.W, h->d_pf_work, h->g.W, max_ratio, h->gt,
                                             h->st));
     HIPCHK(h, hipMemcpyAsync(disp, h->d_out, npx * 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
@@ -1681,6 +1769,12 @@ int sgm_stage_census(sgm_handle *h, const uint8_t *img, int pitch, uint64_t *ct)
     return SGM_OK;
 }
 
+int sgm_get_invalid_disp(const sgm_handle *h, int *invalid) {
+    if (!h || !invalid) return SGM_ERR_INVALID_ARG;
+    *invalid = h->gt.D + 1;
+    return SGM_OK;
+}
+
 int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,
                    int view, int filters, float *cost) {
     if (!h || !ctl || !ctr || !cost || (view != 0 && view != 1)) return SGM_ERR_INVALID_ARG;
@@ -1691,8 +1785,10 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, cons
     HIPCHK(h, hipMemcpyAsync(h->d_ct[0], ctl, npx * 8, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, hipMemcpyAsync(h->d_ct[1], ctr, npx * 8, hipMemcpyHostToDevice, h->st));
     if (sky) HIPCHK(h, hipMemcpyAsync(h->d_sky[0], sky, npx, hipMemcpyHostToDevice, h->st));
-    HIPCHK(h, sgm::launch_cost_h(h->d_ct[0], h->d_ct[1], sky ? h->d_sky[0] : nullptr, h->g.W, view,
-                                 filters & 1, h->g, h->d_ch[0], h->st));
+    // (min_disp: the view's shift applied to the tables as handed in)
+    if (int rc = shift_tables(h, view == 1, view == 0, h->st)) return rc;
+    HIPCHK(h, sgm::launch_cost_h(ct_left(h, view), ct_right(h, view), sky ? h->d_sky[0] : nullptr,
+                                 h->g.W, view, filters & 1, h->g, h->d_ch[0], h->st));
     const float *res = h->d_ch[0];
     if (filters & 2) {  // the frame's own vfwd, in place when the frames run it so
         sgm::PairArgs pa = pair_args(h);
@@ -1763,7 +1859,7 @@ int sgm_lr_check_device(sgm_handle *h, const float *d_fl, int fl_pitch, const fl
     hipStream_t st = scope.st;
     HIPCHK(h, timed(h, "lr", (double)h->g.H * W, st, [&] {
                return sgm::launch_lr(d_fl, fl_pitch, d_fr, fr_pitch, d_out, out_pitch,
-                                     h->p.lr_max_diff, h->g, st);
+                                     h->p.lr_max_diff, h->gt, st);
            }));
     return SGM_OK;
 }
@@ -1841,7 +1937,7 @@ int sgm_colormap_device(sgm_handle *h, const float *d_disp, int pitch, uint8_t *
     StreamScope scope(h, stream);
     hipStream_t st = scope.st;
     HIPCHK(h, timed(h, "colormap", (double)h->g.H * h->g.W, st, [&] {
-               return sgm::launch_colormap(d_disp, pitch, d_bgr, bgr_pitch, h->g, st);
+               return sgm::launch_colormap(d_disp, pitch, d_bgr, bgr_pitch, h->min_disp, h->g, st);
            }));
     return SGM_OK;
 }
@@ -1859,7 +1955,7 @@ int sgm_point_cloud_device(sgm_handle *h, const float *d_disp, int pitch, const 
     HIPCHK(h, timed(h, "point_cloud", (double)h->g.H * h->g.W, st, [&] {
                return sgm::launch_point_cloud(d_disp, pitch, d_img, img_pitch, cam->fx, cam->fy,
                                               cam->cx, cam->cy, cam->baseline, cam->max_range,
-                                              h->d_cloud_counts, d_xyz, d_pixel, d_count, h->g,
+                                              h->d_cloud_counts, d_xyz, d_pixel, d_count, h->gt,
                                               st);
            }));
     return SGM_OK;
@@ -1940,7 +2036,7 @@ int sgm_stage_lr(sgm_handle *h, const float *fl, const float *fr, float *out) {
     HIPCHK(h, hipMemcpyAsync(h->d_sub[0], fl, npx * 4, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, hipMemcpyAsync(h->d_sub[1], fr, npx * 4, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, sgm::launch_lr(h->d_sub[0], h->g.W, h->d_sub[1], h->g.W, h->d_out, h->g.W,
-                             h->p.lr_max_diff, h->g, h->st));
+                             h->p.lr_max_diff, h->gt, h->st));
     HIPCHK(h, hipMemcpyAsync(out, h->d_out, npx * 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
     return SGM_OK;

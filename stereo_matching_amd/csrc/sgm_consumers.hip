@@ -12,11 +12,12 @@ namespace sgm {
 namespace {
 
 __global__ __launch_bounds__(256) void colormap_kernel(const float *__restrict__ disp, int pitch,
-                                                      int H, int W, int D,
+                                                      int H, int W, int D, float off,
                                                       uint8_t *__restrict__ bgr, int bgr_pitch) {
     const int j = bid_x() * 64 + (tid_x() & 63), i = bid_y() * 4 + (tid_x() >> 6);
     if (i >= H || j >= W) return;
-    float v = disp[(size_t)i * pitch + j];
+    // (off = min_disp: back to index space, where the invalid marker is D + 1 again)
+    float v = disp[(size_t)i * pitch + j] - off;
     uint8_t b = 0, g = 0, r = 0;
     if (!(v > D - 1)) {
         v *= (256 / D);  // integer 256 / max_disp (:666)
@@ -126,10 +127,10 @@ __global__ __launch_bounds__(64) void cloud_write_kernel(const float *__restrict
 
 }  // namespace
 
-hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, Geom g,
-                           hipStream_t st) {
+hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,
+                           Geom g, hipStream_t st) {
     hipLaunchKernelGGL(colormap_kernel, dim3((g.W + 63) / 64, (g.H + 3) / 4), dim3(256), 0, st,
-                       disp, pitch, g.H, g.W, g.D, bgr, bgr_pitch);
+                       disp, pitch, g.H, g.W, g.D, (float)min_disp, bgr, bgr_pitch);
     return hipGetLastError();
 }
 

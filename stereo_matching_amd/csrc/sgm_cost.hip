@@ -157,6 +157,37 @@ hipError_t launch_census(const uint8_t *src, int pitch, Geom g, int blur, uint64
     return hipGetLastError();
 }
 
+// ------------------------------------------ shifted tables (min_disp)
+
+// sgm_set_min_disp(h, m) searches disparities [m, m + D): with k = m / scale,
+// the left view's DSI is today's [0, D) DSI of (ctl, ctr_s), ctr_s[i, x] =
+// ctr[i, max(x - k, 0)], and the right view's that of (ctl_s, ctr), ctl_s[i, x]
+// = ctl[i, min(x + k, W-1)] (max(x - k - ds, 0) = max(max(x - k, 0) - ds, 0) and
+// the same for min), so the cost kernels' staging and padding stay as they
+// are.  One word per lane, 256 consecutive words of a row per workgroup: the
+// stores are whole cache lines, the loads the same lines k words aside (or the
+// row's edge word).  Workgroup z selects the table; a null output is skipped.
+__global__ __launch_bounds__(256) void ct_shift_kernel(const uint64_t *__restrict__ ctl,
+                                                       const uint64_t *__restrict__ ctr,
+                                                       uint64_t *__restrict__ ctl_s,
+                                                       uint64_t *__restrict__ ctr_s, int W, int k) {
+    const bool right = __builtin_amdgcn_workgroup_id_z() != 0;
+    const uint64_t *__restrict__ src = right ? ctr : ctl;
+    uint64_t *__restrict__ dst = right ? ctr_s : ctl_s;
+    const int x = bid_x() * 256 + tid_x();
+    if (dst == nullptr || x >= W) return;
+    const size_t row = (size_t)bid_y() * W;
+    const int xs = right ? (x - k > 0 ? x - k : 0) : (x + k < W - 1 ? x + k : W - 1);
+    dst[row + x] = src[row + xs];
+}
+
+hipError_t launch_ct_shift(const uint64_t *ctl, const uint64_t *ctr, uint64_t *ctl_s, uint64_t *ctr_s,
+                           int k, Geom g, hipStream_t st) {
+    // (k can exceed W: x - k and x + k stay far inside int for every accepted min_disp)
+    ct_shift_kernel<<<dim3((g.W + 255) / 256, g.H, 2), 256, 0, st>>>(ctl, ctr, ctl_s, ctr_s, g.W, k);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------ DSI + horizontal IIR
 
 // One thread per (row, d) chain, R rows per block (R*D threads).  The census
@@ -343,10 +374,14 @@ __global__ __launch_bounds__(256) void cost_h_kernel(const uint64_t *__restrict_
 // Both views in one launch (workgroup z = view): the DSI of
 // build_dsi_from_table into out0 and of build_dsi_from_table_beta into out1,
 // each with its own sky mask.  A view's H*D chains fill less than the chip at
-// KITTI sizes, so the two views' chains run side by side.
+// KITTI sizes, so the two views' chains run side by side.  Each view reads its
+// own table pair: view 0 (ctl, ctr_s), view 1 (ctl_s, ctr) (launch_ct_shift;
+// the same two tables when min_disp = 0).
 template <int WIN, bool SKY, bool FILTER, bool UNI, int DC>
 __global__ __launch_bounds__(256) void cost_h2_kernel(const uint64_t *__restrict__ ctl,
                                                       const uint64_t *__restrict__ ctr,
+                                                      const uint64_t *__restrict__ ctl_s,
+                                                      const uint64_t *__restrict__ ctr_s,
                                                       const uint8_t *__restrict__ sky0,
                                                       const uint8_t *__restrict__ sky1,
                                                       int sky_pitch, int H, int W, int D, int scale,
@@ -354,10 +389,10 @@ __global__ __launch_bounds__(256) void cost_h2_kernel(const uint64_t *__restrict
                                                       float *__restrict__ out1) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (__builtin_amdgcn_workgroup_id_z() == 0)
-        cost_h_body<0, WIN, SKY, FILTER, UNI, DC>(ctl, ctr, sky0, sky_pitch, H, W, D, scale, R, out0,
+        cost_h_body<0, WIN, SKY, FILTER, UNI, DC>(ctl, ctr_s, sky0, sky_pitch, H, W, D, scale, R, out0,
                                               bid_x(), smem);
     else
-        cost_h_body<1, WIN, SKY, FILTER, UNI, DC>(ctl, ctr, sky1, sky_pitch, H, W, D, scale, R, out1,
+        cost_h_body<1, WIN, SKY, FILTER, UNI, DC>(ctl_s, ctr, sky1, sky_pitch, H, W, D, scale, R, out1,
                                               bid_x(), smem);
 }
 
@@ -463,9 +498,9 @@ static void launch_cost_h_w(const uint64_t *ctl, const uint64_t *ctr, const uint
 }
 
 template <int WIN, bool SKY, bool FILTER>
-static hipError_t launch_cost_h2_t(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky0,
-                                   const uint8_t *sky1, int sky_pitch, Geom g, float *out0,
-                                   float *out1, hipStream_t st) {
+static hipError_t launch_cost_h2_t(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
+                                   const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
+                                   int sky_pitch, Geom g, float *out0, float *out1, hipStream_t st) {
     bool uni;
     int R;
     size_t smem;
@@ -474,13 +509,13 @@ static hipError_t launch_cost_h2_t(const uint64_t *ctl, const uint64_t *ctr, con
     const dim3 grid((g.H + R - 1) / R, 1, 2);
     if (uni)
         cost_h2_kernel<WIN, SKY, FILTER, true, 0><<<grid, R * g.D, smem, st>>>(
-            ctl, ctr, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
+            ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
     else if (g.D == 128)
         cost_h2_kernel<WIN, SKY, FILTER, false, 128><<<grid, R * g.D, smem, st>>>(
-            ctl, ctr, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
+            ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
     else
         cost_h2_kernel<WIN, SKY, FILTER, false, 0><<<grid, R * g.D, smem, st>>>(
-            ctl, ctr, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
+            ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
     return hipGetLastError();
 }
 
@@ -492,16 +527,16 @@ bool cost_h2_supported(Geom g, bool sky) {
     return R >= 1;
 }
 
-hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky0,
-                          const uint8_t *sky1, int sky_pitch, Geom g, float *out0, float *out1,
-                          hipStream_t st) {
+hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
+                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
+                          int sky_pitch, Geom g, float *out0, float *out1, hipStream_t st) {
     if ((sky0 == nullptr) != (sky1 == nullptr)) return hipErrorInvalidValue;
     if (sky0) {
-        if (g.scale == 1) return launch_cost_h2_t<5, true, true>(ctl, ctr, sky0, sky1, sky_pitch, g, out0, out1, st);
-        return launch_cost_h2_t<2, true, true>(ctl, ctr, sky0, sky1, sky_pitch, g, out0, out1, st);
+        if (g.scale == 1) return launch_cost_h2_t<5, true, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
+        return launch_cost_h2_t<2, true, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
     }
-    if (g.scale == 1) return launch_cost_h2_t<5, false, true>(ctl, ctr, sky0, sky1, sky_pitch, g, out0, out1, st);
-    return launch_cost_h2_t<2, false, true>(ctl, ctr, sky0, sky1, sky_pitch, g, out0, out1, st);
+    if (g.scale == 1) return launch_cost_h2_t<5, false, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
+    return launch_cost_h2_t<2, false, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
 }
 
 // The checkpoint pass's chain (sgm_vstrip.hip): cost_h_body's horizontal IIR
@@ -612,10 +647,13 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
 
 // The strip schedule's checkpoint pass (sgm_vstrip.hip): each view slot's
 // horizontal IIR state at every strip edge, both slots in one launch
-// (workgroup z = slot; dsi0/dsi1: the slot's DSI, 0 left view, 1 right).
+// (workgroup z = slot; dsi0/dsi1: the slot's DSI, 0 left view, 1 right: it
+// reads (ctl, ctr_s) or (ctl_s, ctr), as cost_h2_kernel's views).
 template <bool SKY, bool UNI, int DC>
 __global__ __launch_bounds__(256) void cost_ck_kernel(const uint64_t *__restrict__ ctl,
                                                       const uint64_t *__restrict__ ctr,
+                                                      const uint64_t *__restrict__ ctl_s,
+                                                      const uint64_t *__restrict__ ctr_s,
                                                       const uint8_t *__restrict__ sky0,
                                                       const uint8_t *__restrict__ sky1, int sky_pitch,
                                                       int H, int W, int D, int R, float *__restrict__ out0,
@@ -623,21 +661,22 @@ __global__ __launch_bounds__(256) void cost_ck_kernel(const uint64_t *__restrict
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const bool z = __builtin_amdgcn_workgroup_id_z() != 0;
     if constexpr (!SKY) {
-        if ((z ? dsi1 : dsi0) == 0) cost_ck_body<0, UNI>(ctl, ctr, H, W, D, R, z ? out1 : out0, bid_x(), smem, ns);
-        else cost_ck_body<1, UNI>(ctl, ctr, H, W, D, R, z ? out1 : out0, bid_x(), smem, ns);
+        if ((z ? dsi1 : dsi0) == 0) cost_ck_body<0, UNI>(ctl, ctr_s, H, W, D, R, z ? out1 : out0, bid_x(), smem, ns);
+        else cost_ck_body<1, UNI>(ctl_s, ctr, H, W, D, R, z ? out1 : out0, bid_x(), smem, ns);
     } else if ((z ? dsi1 : dsi0) == 0) {
-        cost_h_body<0, 5, SKY, true, UNI, DC, kVStripNC>(ctl, ctr, z ? sky1 : sky0, sky_pitch, H, W, D, 1, R,
+        cost_h_body<0, 5, SKY, true, UNI, DC, kVStripNC>(ctl, ctr_s, z ? sky1 : sky0, sky_pitch, H, W, D, 1, R,
                                                          z ? out1 : out0, bid_x(), smem, ns);
     } else {
-        cost_h_body<1, 5, SKY, true, UNI, DC, kVStripNC>(ctl, ctr, z ? sky1 : sky0, sky_pitch, H, W, D, 1, R,
+        cost_h_body<1, 5, SKY, true, UNI, DC, kVStripNC>(ctl_s, ctr, z ? sky1 : sky0, sky_pitch, H, W, D, 1, R,
                                                          z ? out1 : out0, bid_x(), smem, ns);
     }
 }
 
 template <bool SKY>
-static hipError_t launch_cost_ck_t(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky0,
-                                   const uint8_t *sky1, int sky_pitch, int dsi0, int dsi1, int nviews,
-                                   Geom g, float *ck0, float *ck1, hipStream_t st) {
+static hipError_t launch_cost_ck_t(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
+                                   const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
+                                   int sky_pitch, int dsi0, int dsi1, int nviews, Geom g, float *ck0,
+                                   float *ck1, hipStream_t st) {
     bool uni;
     int R;
     size_t smem;
@@ -649,7 +688,7 @@ static hipError_t launch_cost_ck_t(const uint64_t *ctl, const uint64_t *ctr, con
     // rows measured slower: HD256 610 vs 317 us, 4K256 2.33 vs 1.82 ms; one
     // row per block, for more waves per CU, changed nothing:
     // profiles/r06_experiments/r06q_vstrip.txt)
-#define CK_ARGS ctl, ctr, sky0, sky1, sky_pitch, g.H, g.W, g.D, R, ck0, ck1, dsi0, dsi1, ns
+#define CK_ARGS ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, R, ck0, ck1, dsi0, dsi1, ns
     if (uni) cost_ck_kernel<SKY, true, 0><<<grid, R * g.D, smem, st>>>(CK_ARGS);
     else if (g.D == 128) cost_ck_kernel<SKY, false, 128><<<grid, R * g.D, smem, st>>>(CK_ARGS);
     else cost_ck_kernel<SKY, false, 0><<<grid, R * g.D, smem, st>>>(CK_ARGS);
@@ -657,12 +696,13 @@ static hipError_t launch_cost_ck_t(const uint64_t *ctl, const uint64_t *ctr, con
     return hipGetLastError();
 }
 
-hipError_t launch_cost_ck(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky0,
-                          const uint8_t *sky1, int sky_pitch, int dsi0, int dsi1, int nviews, Geom g,
-                          float *ck0, float *ck1, hipStream_t st) {
+hipError_t launch_cost_ck(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
+                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
+                          int sky_pitch, int dsi0, int dsi1, int nviews, Geom g, float *ck0,
+                          float *ck1, hipStream_t st) {
     if (nviews == 2 && (sky0 == nullptr) != (sky1 == nullptr)) return hipErrorInvalidValue;
-    if (sky0) return launch_cost_ck_t<true>(ctl, ctr, sky0, sky1, sky_pitch, dsi0, dsi1, nviews, g, ck0, ck1, st);
-    return launch_cost_ck_t<false>(ctl, ctr, sky0, sky1, sky_pitch, dsi0, dsi1, nviews, g, ck0, ck1, st);
+    if (sky0) return launch_cost_ck_t<true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, dsi0, dsi1, nviews, g, ck0, ck1, st);
+    return launch_cost_ck_t<false>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, dsi0, dsi1, nviews, g, ck0, ck1, st);
 }
 
 hipError_t launch_cost_h(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,

@@ -581,7 +581,7 @@ __device__ __forceinline__ void wta_consume_chunk_at(const float (*tb)[tbuf_stri
                                                      long long pix0, long long pix_step, int cnt,
                                                      int lane, int Dn, float uniq,
                                                      uint16_t *disp, float *sub,
-                                                     float *ratio = nullptr) {
+                                                     float *ratio = nullptr, int moff = 0) {
     constexpr int LPP = 64 / PF;  // lanes per pixel
     const int Q = Dn / LPP;       // disparities per lane (>= 8)
     const int px = lane / LPP, q = lane - px * LPP;
@@ -625,8 +625,10 @@ __device__ __forceinline__ void wta_consume_chunk_at(const float (*tb)[tbuf_stri
     }
     if (q == 0 && px < cnt) {
         const long long pix = pix0 + px * pix_step;
-        disp[pix] = (uint16_t)d;
-        sub[pix] = f;
+        // (moff = min_disp, wave-uniform: index space -> true disparity, one add
+        // on the stored values; 0 leaves them as they are)
+        disp[pix] = (uint16_t)(d + moff);
+        sub[pix] = f + (float)moff;
         if (ratio) ratio[pix] = wta_ratio(w.m, w.s);
     }
 }
@@ -670,12 +672,16 @@ __device__ __forceinline__ int group_min_i(int x) {
 // address arithmetic.
 // sub goes to sub_top + sub_off (its own layout: column-major maps of the
 // two-view frames), disp to pix_top + pix_off (row-major); ratio (optional:
-// min / second-min, wta_ratio) goes where sub goes.
+// min / second-min, wta_ratio) goes where sub goes.  moff (wave-uniform,
+// sgm_set_min_disp) is what index 0 stands for: the stored values are
+// f + (float)moff (every pixel, so the invalid marker leaves as D + moff + 1)
+// and d + moff; adding 0.0f is exact, so moff = 0 stores today's values.
 template <int V, int PF, int QQ>
 __device__ __forceinline__ void wta_chunk_q(const float (&x)[QQ], const float (*tb)[tbuf_stride<V>()],
                                             long long pix_top, unsigned pix_off, long long sub_top,
                                             unsigned sub_off, int cnt, int lane, int Dn, float uniq,
-                                            uint16_t *disp, float *sub, float *ratio) {
+                                            uint16_t *disp, float *sub, float *ratio,
+                                            int moff = 0) {
     constexpr int LPP = 64 / PF;  // lanes per pixel
     static_assert(QQ % 4 == 0 && LPP <= 32, "QQ a multiple of 4, at most 32 lanes per pixel");
     const int px = lane / LPP, q = lane - px * LPP;
@@ -719,8 +725,8 @@ __device__ __forceinline__ void wta_chunk_q(const float (&x)[QQ], const float (*
         // disp: only when the frame hands out its raw WTA map (else null:
         // these one-pixel-per-row stores are partial cache lines, ~5% of the
         // final pass at K128 for both maps, profiles/r03_experiments/final_stores.txt)
-        if (disp) (disp + pix_top)[pix_off] = (uint16_t)d;
-        (sub + sub_top)[sub_off] = f;
+        if (disp) (disp + pix_top)[pix_off] = (uint16_t)(d + moff);
+        (sub + sub_top)[sub_off] = f + (float)moff;
         // the match confidence, in sub's layout (null, wave-uniform: not wanted)
         if (ratio) (ratio + sub_top)[sub_off] = wta_ratio(m, sec);
     }
@@ -730,10 +736,11 @@ template <int V, int PF>
 __device__ __forceinline__ void wta_consume_chunk(const float (*tb)[tbuf_stride<V>()],
                                                   const long long *pb, int cnt, int lane,
                                                   int Dn, float uniq, uint16_t *disp,
-                                                  float *sub, float *ratio = nullptr) {
+                                                  float *sub, float *ratio = nullptr,
+                                                  int moff = 0) {
     // pixels of a chunk are equally spaced along the scanline
     const long long step = cnt > 1 ? pb[1] - pb[0] : 0;
-    wta_consume_chunk_at<V, PF>(tb, pb[0], step, cnt, lane, Dn, uniq, disp, sub, ratio);
+    wta_consume_chunk_at<V, PF>(tb, pb[0], step, cnt, lane, Dn, uniq, disp, sub, ratio, moff);
 }
 
 }  // namespace sgm

@@ -95,6 +95,8 @@ struct PairArgs {
     int sub_cm;          // 1: sub[col * H + row] (two-view frames: lr_cm_kernel reads it)
     float *ratio;        // FINAL: match confidence min / second-min, in sub's layout
                          // (null: not wanted; sgm_set_confidence)
+    int min_disp;        // FINAL: what index 0 stands for (sgm_set_min_disp): the maps
+                         // leave as sub + (float)min_disp and disp + min_disp
     const float *zero;   // >= 256 zero floats: the cost of the virtual positions
                          // that align forward passes with their checkpoints
     float p1, p2, uniq;
@@ -186,6 +188,7 @@ struct SlantArgs {
     const float *zero;  // >= 256 zero floats
     float *dummy;       // >= 259 words: the target of inactive steps' stores
     float p1, p2, uniq;
+    int min_disp;       // the bottom-up pass's maps leave as sub + (float)min_disp, disp + min_disp
     int nviews;
     int ntiles, grid;   // set by the launcher
     int max_grid;       // workgroups at most (0: one per CU)
@@ -212,12 +215,20 @@ hipError_t launch_census(const uint8_t *src, int pitch, Geom g, int blur, uint64
 // BM's WTA (BM.cpp:53-85) over the filtered cost: raw disparity + its float copy
 hipError_t launch_bm_wta(const float *cost, float uniq, uint16_t *disp, float *out, int out_pitch,
                          Geom g, hipStream_t st);
-// both views' DSI + horizontal IIR in one launch (both sky masks or neither);
+// The census tables shifted by k = min_disp / scale columns (sgm_set_min_disp):
+// ctl_s[i, x] = ctl[i, min(x + k, W-1)], ctr_s[i, x] = ctr[i, max(x - k, 0)], one
+// launch for both (a null output is skipped).  The left view's DSI of the
+// search range [m, m + D) is the [0, D) DSI of (ctl, ctr_s), the right view's
+// that of (ctl_s, ctr); with min_disp = 0 the shifted tables are the tables.
+hipError_t launch_ct_shift(const uint64_t *ctl, const uint64_t *ctr, uint64_t *ctl_s, uint64_t *ctr_s,
+                           int k, Geom g, hipStream_t st);
+// both views' DSI + horizontal IIR in one launch (both sky masks or neither):
+// view 0 from (ctl, ctr_s), view 1 from (ctl_s, ctr);
 // cost_h2_supported: false when rows do not fit the staged kernel
 bool cost_h2_supported(Geom g, bool sky);
-hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky0,
-                          const uint8_t *sky1, int sky_pitch, Geom g, float *out0, float *out1,
-                          hipStream_t st);
+hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
+                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
+                          int sky_pitch, Geom g, float *out0, float *out1, hipStream_t st);
 hipError_t launch_cost_h(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,
                          int sky_pitch, int view, int filter, Geom g, float *out,
                          hipStream_t st);
@@ -231,6 +242,7 @@ hipError_t launch_cost_h(const uint64_t *ctl, const uint64_t *ctr, const uint8_t
 constexpr int kVStripNC = VSTRIP_NC;
 struct VStripArgs {
     const uint64_t *ctl, *ctr;  // census words (left, right image)
+    const uint64_t *ctl_s, *ctr_s;  // the shifted tables (launch_ct_shift; = ctl, ctr at min_disp 0)
     const uint64_t *skw0, *skw1; // per view slot: sky flags, one word per pixel (null: no mask)
     int dsi0, dsi1;             // slot's DSI: 0 left view, 1 right view
     const float *ck0, *ck1;     // checkpoints (launch_cost_ck)
@@ -242,9 +254,11 @@ struct VStripArgs {
 size_t vstrip_strips(Geom g);
 size_t vstrip_ck_floats(Geom g);
 bool vstrip_supported(Geom g, bool sky);
-hipError_t launch_cost_ck(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky0,
-                          const uint8_t *sky1, int sky_pitch, int dsi0, int dsi1, int nviews, Geom g,
-                          float *ck0, float *ck1, hipStream_t st);
+// (a slot with DSI 0 reads (ctl, ctr_s), one with DSI 1 (ctl_s, ctr))
+hipError_t launch_cost_ck(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
+                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
+                          int sky_pitch, int dsi0, int dsi1, int nviews, Geom g, float *ck0,
+                          float *ck1, hipStream_t st);
 hipError_t launch_vstrip(const VStripArgs &a, int nviews, Geom g, hipStream_t st);
 // the sky mask as 0/1 words (the strip pass stages 8-byte words only), kept
 // in the Ch buffer after the checkpoints (offset in floats)
@@ -278,8 +292,9 @@ size_t sky_scratch_bytes(Geom g);
 hipError_t launch_sky_detect(const uint8_t *const *img, int pitch, uint8_t *const *mask,
                              int mask_pitch, void *scratch, int nviews, Geom g, hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
-hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, Geom g,
-                           hipStream_t st);
+// (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
+hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,
+                           Geom g, hipStream_t st);
 hipError_t launch_point_cloud(const float *disp, int pitch, const uint8_t *img, int img_pitch,
                               float fx, float fy, float cx, float cy, double baseline,
                               float max_range, int *counts, double *xyz, uint8_t *pixel,

@@ -570,10 +570,11 @@ __global__ __launch_bounds__(64 * (NW + 1)) void slant_kernel(SlantArgs a, Geom 
             const bool act = ps >= 0 && j >= 0 && j < W;
             const long long pix = (long long)(H - 1 - ps) * W + j;
             float *fs = act ? sv.sub + pix : a.dummy + 256;
-            if (lane == 0) *fs = f;
+            // (index space -> true disparity: sgm_set_min_disp, 0 changes nothing)
+            if (lane == 0) *fs = f + (float)a.min_disp;
             if (sv.disp) {
                 uint16_t *ds = act ? sv.disp + pix : reinterpret_cast<uint16_t *>(a.dummy + 257);
-                if (lane == 0) *ds = (uint16_t)d;
+                if (lane == 0) *ds = (uint16_t)(d + a.min_disp);
             }
             if (sv.ratio) {
                 float *rs = act ? sv.ratio + pix : a.dummy + 258;

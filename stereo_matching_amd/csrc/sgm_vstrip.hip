@@ -86,7 +86,8 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
     // hipcc scheduled right after its issue, waited for every load in flight.
     const int nsh = NC + 2 + D;
     const int sbase = dsi == 0 ? j0 - D + 1 : j0;
-    const uint64_t *shimg = dsi == 0 ? a.ctr : a.ctl, *unimg = dsi == 0 ? a.ctl : a.ctr;
+    // (the shifted image's table is the min_disp-shifted one: VStripArgs::ctl_s, ctr_s)
+    const uint64_t *shimg = dsi == 0 ? a.ctr_s : a.ctl_s, *unimg = dsi == 0 ? a.ctl : a.ctr;
     using SG = VStripStage<V, NC>;
     const int x = tid_x();
     const uint64_t *skw = slot ? a.skw1 : a.skw0;

@@ -53,7 +53,7 @@ class SGM:
                  uniqueness: float = 0.7, lr_max_diff: float = 1.0, post_filter: bool = False,
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
-                 post_filter_launches: int = 0, confidence: bool = False,
+                 post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
                  _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
@@ -85,10 +85,23 @@ class SGM:
         self.params = p
         self.h, self.w, self.scale, self.max_disp = h, w, s, d
         self.rows, self.cols = h // s, w // s
-        self.invalid_disp = d + 1
+        self.min_disp = int(min_disp)
         handle = ctypes.c_void_p()
         check(self._lib.sgm_create(ctypes.byref(p), device, ctypes.byref(handle)))
         self._h = handle
+        # min_disp (sgm_set_min_disp): search disparities [min_disp, min_disp + d)
+        # instead of [0, d).  Every map is in true disparity, invalid = d +
+        # min_disp + 1 (invalid_disp); a sky pixel reports min_disp.  A multiple
+        # of s, >= 0; side-stage handles (aux_only) of such maps take the same value
+        try:
+            if self.min_disp:
+                check(self._lib.sgm_set_min_disp(handle, self.min_disp), handle)
+            inv = ctypes.c_int()
+            check(self._lib.sgm_get_invalid_disp(handle, ctypes.byref(inv)), handle)
+        except Exception:
+            self.close()
+            raise
+        self.invalid_disp = inv.value  # d + min_disp + 1
         self.device = device
         self._lr = np.full((self.rows, self.cols), self.invalid_disp, np.float32)
         self._raw = np.zeros((self.rows, self.cols), np.uint16)
@@ -422,6 +435,6 @@ class GPU_SGM(SGM):
     approximations."""
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
-                 post_filter_launches: int = 0):
+                 post_filter_launches: int = 0, min_disp: int = 0):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
-                         post_filter_launches=post_filter_launches)
+                         post_filter_launches=post_filter_launches, min_disp=min_disp)

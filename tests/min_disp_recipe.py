@@ -1,0 +1,119 @@
+"""Expected maps of a frame with a minimum disparity m (sgm_set_min_disp: the
+search range is disparities [m, m + D) instead of [0, D)), composed from the
+oracle's stage functions.
+
+The oracle has no minimum disparity.  With k = m / s the left view's cost
+volume C[i, j, d] = ham(ctL[i, j], ctR[i, max(j - (d + m)/s, 0)]) is the
+oracle's own volume of (ctL, ctR'), ctR'[i, x] = ctR[i, max(x - k, 0)], and the
+right view's, ham(ctL[i, min(j + (d + m)/s, W-1)], ctR[i, j]), that of (ctL',
+ctR), ctL'[i, x] = ctL[i, min(x + k, W-1)] (m is a multiple of s, so (d + m)/s
+= d/s + k; tests/test_min_disp_cpu.py checks both against the formulas).
+Filters, paths, aggregation, WTA, uniqueness and sub-pixel run on those
+volumes in index space exactly as oracle.process runs them; the maps then
+leave in true disparity by one float32 add, sub = f + float32(m), disp = d + m,
+and the LR check, post_filter and LKRefine are the oracle's functions called
+with D + m for D (they use D only as the valid bound and the invalid marker).
+With m = 0 the recipe is oracle.process, bit for bit.
+
+TEST INFRASTRUCTURE ONLY.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+import oracle
+from confidence_recipe import ratio_of
+from paths4_recipe import aggregate, assert_bits_equal, census, cost_volume  # noqa: F401
+from stereo_matching_amd import synthetic
+
+# (h, w, D, m, s, kind, sky)
+SHAPES = [
+    (9, 20, 32, 48, 1, "noise", False),     # shift >= W: every lookup clamps
+    (19, 70, 32, 16, 1, "noise", False),    # ties and rejections
+    (37, 150, 32, 16, 1, "road", False),    # the recovery condition's pair
+    (40, 200, 32, 32, 2, "road", False),    # scale 2, m / s = 16
+    (24, 330, 128, 96, 1, "road", True),    # sky pixels must report m
+    (33, 300, 64, 64, 1, "road", False),    # m equal to D
+    (33, 270, 256, 64, 1, "road", False),   # D + m > 256
+]
+# strip edges under the forced slanted schedule: widths 16k + {1, 2, 3, 4}
+STRIP_SHAPES = [(33, w, 64, 16, 1, "road", False) for w in (33, 35, 67, 68)]
+
+
+def shape_id(shape):
+    h, w, D, m, s, kind, sky = shape
+    return f"{h}x{w}_D{D}_m{m}_s{s}_{kind}{'_sky' if sky else ''}"
+
+
+IDS = [shape_id(x) for x in SHAPES]
+STRIP_IDS = [shape_id(x) for x in STRIP_SHAPES]
+RECOVERY = SHAPES[2]
+
+
+def make_inputs(shape):
+    """(left, right, mask): the pair is generated for 2 D disparities, so true
+    disparities lie inside and outside the window [m, m + D)."""
+    h, w, D, m, s, kind, sky = shape
+    left, right = synthetic.stereo_pair(h, w, 2 * D, pair_index=3, kind=kind)
+    mask = synthetic.sky_mask(h // s, w // s) if sky else None
+    return left, right, mask
+
+
+def shift_tables(ctl, ctr, k):
+    """(ctL', ctR'): ctL'[i, x] = ctL[i, min(x + k, W-1)], ctR'[i, x] = ctR[i, max(x - k, 0)]."""
+    W = ctl.shape[1]
+    x = np.arange(W)
+    return (np.ascontiguousarray(ctl[:, np.minimum(x + k, W - 1)]),
+            np.ascontiguousarray(ctr[:, np.maximum(x - k, 0)]))
+
+
+def view_volumes(left, right, D, m, s, sky, paths):
+    """The aggregated index-space volumes (S_left, S_right)."""
+    assert m % s == 0
+    ctl, ctr = census(left, s), census(right, s)
+    ctl_s, ctr_s = shift_tables(ctl, ctr, m // s)
+    return (aggregate(cost_volume(ctl, ctr_s, D, s, 0, sky), paths),
+            aggregate(cost_volume(ctl_s, ctr, D, s, 1, sky), paths))
+
+
+def recipe(left, right, D, m, s=1, sky=None, paths=8, lk=False):
+    """The maps of oracle.process (same keys) in true disparity, plus "ratio" /
+    "ratio_beta" (the confidence quotient) and, with lk, "lk" (LKRefine of
+    "final"); the same sky mask serves both views."""
+    out = {}
+    for S, sfx in zip(view_volumes(left, right, D, m, s, sky, paths), ("", "_beta")):
+        d = oracle.wta(S)
+        f = oracle.subpixel(d, S)
+        out["disp" + sfx] = d + m
+        out["sub" + sfx] = (f + np.float32(m)).astype(np.float32)
+        out["ratio" + sfx] = ratio_of(S)
+    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
+    out["final"] = oracle.post_filter(out["lr"], D + m, s)
+    if lk:
+        out["lk"] = oracle.lk_refine(left[::s, ::s], right[::s, ::s], out["final"], D + m)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def expected(shape, paths=8, lk=False):
+    """recipe() of a shape, computed once per session; read-only."""
+    h, w, D, m, s, kind, sky = shape
+    left, right, mask = make_inputs(shape)
+    out = recipe(left, right, D, m, s, mask, paths, lk)
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def recovery_figures(lr, shape=RECOVERY):
+    """(valid fraction, median |lr - gt| over the valid pixels) on the rows whose
+    ground truth lies inside the search window."""
+    h, w, D, m, s, kind, sky = shape
+    gt = synthetic.ground_truth(h, 2 * D)
+    rows = np.flatnonzero((gt >= m) & (gt < m + D))
+    sel = lr[rows]
+    valid = sel <= D + m - 1
+    err = np.abs(sel - gt[rows, None].astype(np.float32))[valid]
+    return float(valid.mean()), float(np.median(err))
