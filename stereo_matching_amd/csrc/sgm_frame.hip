@@ -1,0 +1,733 @@
+// sgm_frame.hip -- everything that enqueues a frame: the cost stage, the six
+// aggregation schedules (enum Schedule, sgm_handle.h; DESIGN.md "Frame
+// schedule"), the LR check, post_filter and LKRefine, and the choices by frame
+// size that sgm_create makes for them (slant_default, band_rows_for).
+// Concurrency between independent roles comes from sharing a launch (stage
+// A/B), not from streams (the runtime may map streams onto one hardware
+// queue): a frame runs on one stream, at 73.5 B of HBM traffic per
+// pixel-disparity in the per-view schedule (whole_view).
+#include "sgm_handle.h"
+
+#include <stdlib.h>
+
+using sgm::PairArgs;
+
+// The shifted tables after a census (or an upload) wrote d_ct; nothing at min_disp = 0
+int sgm::shift_tables(sgm_handle *h, bool left, bool right, hipStream_t st) {
+    if (h->min_disp == 0) return SGM_OK;
+    HIPCHK(h, timed(h, "ct_shift", (double)((left ? 1 : 0) + (right ? 1 : 0)) * h->g.H * h->g.W, st, [&] {
+               return sgm::launch_ct_shift(h->d_ct[0], h->d_ct[1], left ? h->d_cts[0] : nullptr,
+                                           right ? h->d_cts[1] : nullptr, h->min_disp / h->g.scale,
+                                           h->g, st);
+           }));
+    return SGM_OK;
+}
+
+// The slanted-tile schedule replaces the bands (above the Infinity Cache)
+// where it was measured faster (tools/slant_sizes.py,
+// profiles/r04_experiments/slant.txt, with the H pair beside the top-down
+// pass): at D = 256 once views * W >= 0.5 * NW * CUs, i.e. half a full-height
+// tile of work per workgroup (round 6; 0.7 before), at D = 128 from 0.9
+// (round 4 at 0.7: HD256 two views -18.6%, 4K256 one view -20%,
+// two views -24%, 720p D = 256 two views -9.4%, HD128 two views -9.6%,
+// 4K128 two views -18.8%; HD256 one view +2.0%, HD128 one view +24.9%,
+// 1056x512 D = 128 two views +10.3%); never at D = 64 (HD64 two views
+// +16.8%, 4K64 +4.2%; round 5: +11.4%, +2.2%).  Below that the tile-to-tile
+// hand-off chain, not the bytes, sets the passes' time.  At D = 128 the
+// threshold is 0.9 tiles per workgroup (below).
+bool sgm::slant_default(Geom g, int nviews) {
+    if (vol_elems(g) * sizeof(float) <= 256.0 * 1024 * 1024 || g.D < 128) return false;
+    const int cus = slant_cus();
+    // round 5 re-sweep with the prioritised receiver (profiles/r05_experiments/
+    // r05m_slant_sizes.txt): 720p D = 256 two views (0.71 tiles per
+    // workgroup) -6.2%, but 720p D = 128 two views (0.71) +7.7%: at D = 128
+    // the crossover lies between 0.71 and HD128's 1.07 (-9.6%).  Round 6's
+    // dataflow passes (profiles/r06_experiments/r06c_sizes_sweep.txt,
+    // r06f_share_order_sweep.txt) moved D = 256 down: HD256 one view (0.54)
+    // -5.0..-9.7%; at D = 128, 720p two views (0.71) stays +5.3%, HD128 one
+    // view (0.54) +24%
+    return 10LL * nviews * g.W >= (g.D >= 256 ? 5LL : 9LL) * sgm::kSlantNW * cus;
+}
+
+// Rows per band of the backward phase (stage B's diagonal pair, the L8
+// sweep, the final pass) for cost volumes above the 256 MB Infinity Cache:
+// about 192 MB of cost volume per band, so that a band's C and T stay in the
+// cache from one pass to the next (tools/band_probe.hip: 1.27-1.35x for the
+// three passes' streams alone; in the frame HD256 -3.5%, 4K256 -5%; 94-126 MB
+// bands gain less).  A volume the cache already holds (K128) loses by it.
+// Band edges sit on multiples of 16 rows from the bottom: whole segments of
+// every pair family.
+// SGM_BAND_ROWS overrides (0: whole-volume passes).
+int sgm::band_rows_for(Geom g) {
+    const char *e = getenv("SGM_BAND_ROWS");
+    const double row_bytes = (double)g.W * g.D * sizeof(float);
+    int rows;
+    if (e && *e) {
+        rows = atoi(e);
+    } else {
+#ifdef SGM_NO_BANDS
+        return 0;
+#endif
+        if (row_bytes * g.H <= 256.0 * 1024 * 1024) return 0;
+        rows = (int)(192.0 * 1024 * 1024 / row_bytes);
+    }
+    rows -= rows % 16;
+    return rows <= 0 || rows >= g.H ? 0 : rows;
+}
+
+int sgm::slant_cus() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        cus = 256;
+    return cus;
+}
+
+namespace {
+
+// What the aggregation launches of one view take, role by role: the H pair
+// (h1 forward, h2 backward), the diagonal pair (d6, d7), the L5 and L8 sweeps
+// and the final pass.
+struct ViewRoles {
+    PairArgs h1, h2, d6, d7, fin;
+    SweepArgs l5, l8;
+};
+
+// The one place that wires the roles to a view's buffers: C (cost_buf), S12
+// (d_s), T (t_buf) and the checkpoints of each pair family.  disp, sub: where
+// the final pass leaves its maps; sub_cm: sub and the confidence map beside it
+// column-major.  A schedule that has no use for a role ignores it: the 4-path
+// passes have no diagonal checkpoints and their final pass reads no acc_in
+// (pair_split_body's NOT, sgm_bodies.h); the slanted passes take the pointers
+// only.  nt_cost stays 0: only whole_view's own final launch sets it.
+ViewRoles view_roles(sgm_handle *h, int view, uint16_t *disp, float *sub, int sub_cm) {
+    float **ck = h->d_ck[view];
+    float *T = t_buf(h, view);
+    ViewRoles r{};
+    PairArgs pa = pair_args(h);
+    pa.cost = cost_buf(h, view);
+    r.h1 = pa;
+    r.h1.ckpt = ck[sgm::PAIR_H];
+    r.h2 = r.h1;
+    r.h2.out = h->d_s[view];
+    r.d6 = pa;
+    r.d6.ckpt = ck[sgm::PAIR_D2];
+    r.d7 = r.d6;
+    r.d7.acc_in = T;
+    r.d7.out = T;
+    r.l5 = sweep_args(h);
+    r.l5.cost = pa.cost;
+    r.l5.acc_out = T;
+    r.l8 = r.l5;
+    r.l8.acc_in = T;
+    r.fin = pa;
+    r.fin.ckpt = ck[sgm::PAIR_V];
+    r.fin.s_in = h->d_s[view];
+    r.fin.acc_in = T;
+    r.fin.disp = disp;
+    r.fin.sub = sub;
+    r.fin.sub_cm = sub_cm;
+    r.fin.ratio = h->d_ratio[view];  // (null: confidence off)
+    h->ratio_cm[view] = sub_cm != 0;
+    return r;
+}
+
+// The 8-path aggregation of one view, given the final cost volume and the L3
+// checkpoints (written by vfwd, or by stage_aggregate's PAIR_V forward pass),
+// as three launches on one stream:
+//   stage A: L1 fwd (ckpt) | L5 -> T5 | L6 fwd (ckpt)
+//   stage B: L2 bwd: S12 = L1 + L2 | L7 bwd: T = (T5 + L6) + L7
+//   L8:      T += L8
+//   final:   L4 bwd recomputing L3: total = ((S12 + L3) + L4) + T -> WTA
+// (the reference's order, SGM.cpp:386-390).  T may alias the dead
+// horizontally filtered volume.
+// final = false: the caller launches this view's final pass with the other
+// view's.
+int whole_view(sgm_handle *h, const ViewRoles &r, hipStream_t st, bool final) {
+    const Geom g = h->g;
+    const double elems = vol_elems(g);
+    HIPCHK(h, timed(h, "stage_a", elems, st, [&] { return sgm::launch_stage_a(r.h1, r.l5, r.d6, g, st); }));
+    HIPCHK(h, timed(h, "stage_b", elems, st, [&] { return sgm::launch_stage_b(r.h2, r.d7, g, st); }));
+    HIPCHK(h, timed(h, "sweep_L8_acc", elems, st,
+                    [&] { return sgm::launch_sweep(SGM_DIR_L8, sgm::SWEEP_ACC, r.l8, g, st); }));
+    if (!final) return SGM_OK;
+    // two views: each final pass is the last read of its view's C, and the
+    // other view's volume follows it into the Infinity Cache, so C goes by
+    // non-temporal loads (K128 two views -1.0% paired).  With one view the
+    // next frame's stage A loses what the final pass gains, with one C buffer
+    // or two used alternately (profiles/r06_experiments/r06aa_final_nt.txt,
+    // r06bb_c_alternate.txt), so one-view frames keep default loads
+    PairArgs fin = r.fin;
+    fin.nt_cost = h->nviews == 2;
+    HIPCHK(h, timed(h, "pair_bwd_L4_final", elems, st,
+                    [&] { return sgm::launch_pair_bwd(sgm::PAIR_V, sgm::PAIR_FINAL, fin, g, st); }));
+    return SGM_OK;
+}
+
+// Banded frames (cost volumes above the Infinity Cache): the view's vertical
+// filter + L3 forward pass (vfwd, from the horizontally filtered volume T)
+// and stage A's diagonal roles run in forward bands first, top band first, so
+// that each band's final cost stays in the Infinity Cache from vfwd to L5 and
+// L6; the whole H pair follows as its own launch (run_frame: both views' at
+// once); then the backward bands (DESIGN.md "Bands").
+int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
+    const Geom g = h->g;
+    const double elems = vol_elems(g);
+    PairArgs va = vfwd_args(h, view), d6 = r.d6;
+    SweepArgs l5 = r.l5;
+    // band edges at H - m*BR (multiples of 16 rows from the bottom, as
+    // the backward bands): whole segments of every family
+    const int H = g.H, FR = h->band_rows;
+    const int nb = (H + FR - 1) / FR;
+    for (int m = nb - 1; m >= 0; --m) {
+        const int rb = H - (m + 1) * FR > 0 ? H - (m + 1) * FR : 0, re = H - m * FR;
+        const double be = (double)(re - rb) / H * elems;
+        va.band = {rb, re, h->d_carry[view][2]};
+        HIPCHK(h, timed(h, "vfwd", be, st, [&] {
+                   return sgm::launch_vfwd(h->d_ch[view], cost_buf(h, view), va, g, st);
+               }));
+        l5.band = {rb, re, h->d_carry[view][0]};
+        d6.band = {rb, re, h->d_carry[view][1]};
+        HIPCHK(h, timed(h, "stage_a_d", be, st, [&] { return sgm::launch_stage_a_band(l5, d6, g, st); }));
+    }
+    return SGM_OK;
+}
+
+int backward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
+    const Geom g = h->g;
+    const double elems = vol_elems(g);
+    PairArgs d7 = r.d7, fin = r.fin;
+    SweepArgs l8 = r.l8;
+    const int H = g.H, BR = h->band_rows;
+    // bottom band first: the backward passes walk up
+    for (int kb = 0; kb < H; kb += BR) {
+        const int ke = kb + BR < H ? kb + BR : H;
+        const double be = (double)(ke - kb) / H * elems;
+        d7.band = {kb, ke, h->d_carry[view][0]};
+        HIPCHK(h, timed(h, "stage_b_d2", be, st, [&] { return sgm::launch_stage_b(r.h2, d7, g, st); }));
+        l8.band = {kb, ke, h->d_carry[view][1]};
+        fin.band = {kb, ke, h->d_carry[view][2]};
+        HIPCHK(h, timed(h, "sweep_L8_acc", be, st,
+                        [&] { return sgm::launch_sweep(SGM_DIR_L8, sgm::SWEEP_ACC, l8, g, st); }));
+        HIPCHK(h, timed(h, "pair_bwd_L4_final", be, st, [&] {
+                   return sgm::launch_pair_bwd(sgm::PAIR_V, sgm::PAIR_FINAL, fin, g, st);
+               }));
+    }
+    return SGM_OK;
+}
+
+// Both views' aggregation as joint launches (grid.y = view): stage A, stage
+// B, the L8 sweep and the final pass each take both views at once.  For frames
+// whose two cost volumes fit the 256 MB Infinity Cache together (K64: 2 x 119
+// MB), where one view's launches hold too few chains to fill the chip (the
+// reference runs the views back to back, SGM.cpp:32-801; the results are the
+// same per view).
+int aggregate_joint(sgm_handle *h, const ViewRoles *r, hipStream_t st) {
+    const Geom g = h->g;
+    const double elems2 = 2.0 * vol_elems(g);
+    const PairArgs h1[2] = {r[0].h1, r[1].h1}, h2[2] = {r[0].h2, r[1].h2};
+    const PairArgs d6[2] = {r[0].d6, r[1].d6}, d7[2] = {r[0].d7, r[1].d7};
+    const SweepArgs l5[2] = {r[0].l5, r[1].l5};
+    HIPCHK(h, timed(h, "stage_a", elems2, st, [&] { return sgm::launch_stage_a2(h1, l5, d6, g, st); }));
+    HIPCHK(h, timed(h, "stage_b", elems2, st, [&] { return sgm::launch_stage_b2(h2, d7, g, st); }));
+    HIPCHK(h, timed(h, "sweep_L8_acc", elems2, st,
+                    [&] { return sgm::launch_sweep2_l8(r[0].l8, r[1].l8, g, st); }));
+    HIPCHK(h, timed(h, "pair_bwd_L4_final", elems2, st,
+                    [&] { return sgm::launch_final2(r[0].fin, r[1].fin, g, st); }));
+    return SGM_OK;
+}
+
+// The 4-path aggregation (params.paths == 4: the reference's USE_8_PATH off,
+// inc/SGM.h:7, SGM.cpp:387-390) of nv views, given each view's final cost
+// volume and L3 checkpoints, as whole-volume passes at every size (DESIGN.md
+// 5g):
+//   H pair: L1 fwd (ckpt), L2 bwd: S12 = L1 + L2
+//   final:  L4 bwd recomputing L3: total = (S12 + L3) + L4 -> WTA, sub-pixel
+// each with both views in one launch (per-view vfwd and final launches
+// measured +5.4% at K128, +7.5% at K64, +2.2% at HD256 on the frame).  No T
+// chain, no diagonal checkpoints, no bands, no slanted tiles.
+int aggregate4(sgm_handle *h, int nv, const ViewRoles *r, hipStream_t st) {
+    const Geom g = h->g;
+    const double elems = vol_elems(g);
+    const ViewRoles &r1 = r[nv - 1];  // (one view: the second slot repeats the first, unused)
+    const PairArgs h1[2] = {r[0].h1, r1.h1}, h2[2] = {r[0].h2, r1.h2}, fin[2] = {r[0].fin, r1.fin};
+    if (h->p4_split) {
+        HIPCHK(h, timed(h, "hpair4_fwd", nv * elems, st,
+                        [&] { return sgm::launch_h_fwd4(h1, nv, g, st); }));
+        HIPCHK(h, timed(h, "hpair4_bwd", nv * elems, st,
+                        [&] { return sgm::launch_h_bwd4(h2, nv, g, st); }));
+    } else {
+        HIPCHK(h, timed(h, "hpair4", nv * elems, st,
+                        [&] { return sgm::launch_hpair4(h1, h2, nv, g, st); }));
+    }
+    HIPCHK(h, timed(h, "final4", nv * elems, st, [&] { return sgm::launch_final4(fin, nv, g, st); }));
+    return SGM_OK;
+}
+
+// build_dsi_from_table[_beta] (dsi 0 / 1) + horizontal IIR (cost_h), then
+// the vertical IIR fused with the L3 forward pass (vfwd), into view slot
+// `view`'s buffers.
+int cost_view(sgm_handle *h, int view, int dsi, const uint8_t *sky, int sky_pitch, hipStream_t st,
+              bool vfwd = true) {
+    const double elems = vol_elems(h->g);
+    HIPCHK(h, timed(h, "cost_h", elems, st, [&] {
+               return sgm::launch_cost_h(ct_left(h, dsi), ct_right(h, dsi), sky, sky_pitch, dsi, 1,
+                                         h->g, h->d_ch[view], st);
+           }));
+    if (!vfwd) return SGM_OK;
+    const PairArgs pa = vfwd_args(h, view);
+    HIPCHK(h, timed(h, "vfwd", elems, st, [&] {
+               return sgm::launch_vfwd(h->d_ch[view], cost_buf(h, view), pa, h->g, st);
+           }));
+    return SGM_OK;
+}
+
+// BM::process (src/BM.cpp:9-97): census with BM's row decimation, the left
+// DSI + both cost filters (the vertical filter's fused L3 checkpoints are
+// simply not used), the filtered-cost WTA, then post_filter (:88).
+int bm_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
+    const Geom g = h->g;
+    const double npx = (double)g.H * g.W;
+    if (h->p.sky_detect) {
+        HIPCHK(h, timed(h, "sky_detect", npx, st, [&] {
+                   return sgm::launch_sky_detect(&f.left, f.pitch, h->d_sky, g.W, h->d_sky_scratch, 1,
+                                                 g, st);
+               }));
+        f.sky_l = h->d_sky[0];
+        f.sky_pitch = g.W;
+    }
+    HIPCHK(h, timed(h, "census", 2 * npx, st, [&] {
+               return sgm::launch_census(f.left, f.pitch, g, h->p.blur, h->d_ct[0], st, true, f.right,
+                                         h->d_ct[1]);
+           }));
+    int rc;
+    if ((rc = cost_view(h, 0, 0, f.sky_l, f.sky_pitch, st)) != SGM_OK) return rc;
+    HIPCHK(h, timed(h, "bm_wta", vol_elems(g), st, [&] {
+               return sgm::launch_bm_wta(cost_buf(h, 0), h->p.uniqueness, h->d_disp[0], f.out,
+                                         f.out_pitch, g, st);
+           }));
+    if (f.raw && f.raw != h->d_disp[0])  // (the host API passes d_disp[0] itself)
+        HIPCHK(h, hipMemcpyAsync(f.raw, h->d_disp[0], (size_t)g.H * g.W * sizeof(uint16_t),
+                                 hipMemcpyDeviceToDevice, st));
+    if (h->p.post_filter) return sgm::post_filter(h, f.out, f.out_pitch, st);
+    return SGM_OK;
+}
+
+// The slanted-tile schedule of the aggregation (DESIGN.md "Slanted tiles"),
+// after the cost stage left each view's horizontally filtered volume in d_ch:
+//   vfwd_l3 (per view): vertical IIR -> C, and the full L3 volume
+//   slant_down (both views): T56 = L5 + L6 (SGM.cpp:389's first association)
+//     into the dead horizontally filtered volume
+//   H pair (both views): S12 = L1 + L2
+//   slant_up (both views): L4, L7, L8 walking up, total
+//     ((S12 + L3) + L4) + ((T56 + L7) + L8), WTA, sub-pixel (row-major maps)
+// the top-down pass's share of the CUs (eighths) while the H pair runs
+// beside it.  Round 6 (dataflow passes, profiles/r06_experiments/
+// r06f_share_order_sweep.txt, best of 3): the top-down pass alone now takes
+// 1.9 ms at HD256 (it took the whole 4.7 ms region before), so the share
+// that balances the two moved: 4/8 for D = 256 frames below 2e9 elements
+// (HD256 V=2 10.83 ms vs 11.12 at 8/8, HD256 V=1, 720p256 V=2), the whole
+// chip otherwise (4K256 V=1/V=2, HD128 and 4K128 V=2 within 0.5% of their
+// best at 8/8).  Launching the H pair first was no better at any share.
+int slant_down_grid_eighths(Geom g, int nviews) {
+#ifdef SGM_SLANT_DEBUG
+    if (const char *e = getenv("SGM_SLANT_DOWN_EIGHTHS"))  // share sweeps (tools/slant_share.sh)
+        if (atoi(e) >= 1 && atoi(e) <= 8) return atoi(e);
+#endif
+    const double elems = (double)nviews * g.H * g.W * g.D;
+    return g.D >= 256 && elems < 2e9 ? 4 : 8;
+}
+
+// have_c: the strip pass already wrote C and the L3 volumes (cost_stage)
+int slant_views(sgm_handle *h, const ViewRoles *r, hipStream_t st, bool have_c) {
+    const Geom g = h->g;
+    const int nv = h->nviews;
+    const double elems = vol_elems(g);
+    const PairArgs hp1[2] = {r[0].h1, r[nv - 1].h1}, hp2[2] = {r[0].h2, r[nv - 1].h2};
+    sgm::SlantArgs sa{};
+    if (have_c) {
+    } else if (nv == 2) {  // both views in one launch
+        const sgm::PairArgs pa[2] = {pair_args(h), pair_args(h)};
+        const float *in[2] = {h->d_ch[0], h->d_ch[1]};
+        float *out[2] = {h->d_c[0], h->d_c[1]}, *l3[2] = {h->d_l3[0], h->d_l3[1]};
+        HIPCHK(h, timed(h, "vfwd_l3", 2 * elems, st, [&] { return sgm::launch_vfwd2_l3(in, out, l3, pa, g, st); }));
+    } else {
+        const sgm::PairArgs pa = pair_args(h);
+        HIPCHK(h, timed(h, "vfwd_l3", elems, st, [&] {
+                   return sgm::launch_vfwd_l3(h->d_ch[0], h->d_c[0], h->d_l3[0], pa, g, st);
+               }));
+    }
+    for (int v = 0; v < nv; ++v) {
+        const PairArgs &fin = r[v].fin;
+        sa.v[v] = {fin.cost, fin.s_in, h->d_l3[v], fin.acc_in, r[v].d7.out,
+                   fin.sub, fin.disp, h->d_gran, fin.ratio};
+    }
+    sa.ctl = h->d_slant_ctl;
+    sa.zero = h->d_zero;
+    sa.dummy = h->d_slant_dummy;
+    sa.p1 = (float)h->p.p1;
+    sa.p2 = (float)h->p.p2;
+    sa.uniq = h->p.uniqueness;
+    sa.min_disp = h->min_disp;
+    sa.nviews = nv;
+    sa.err_host = h->d_slant_err;
+#ifdef SGM_SLANT_DEBUG
+    if (getenv("SGM_SLANT_T56SWEEP")) {  // T56 by the two diagonal sweeps instead
+        for (int v = 0; v < nv; ++v) {
+            // (L6 accumulates into T5 as the L8 role does: acc_in = acc_out = T)
+            HIPCHK(h, sgm::launch_sweep(SGM_DIR_L5, sgm::SWEEP_INIT, r[v].l5, g, st));
+            HIPCHK(h, sgm::launch_sweep(SGM_DIR_L6, sgm::SWEEP_ACC, r[v].l8, g, st));
+        }
+    } else
+#endif
+    // The H pair and the top-down pass both only read C: the H pair runs on
+    // its own stream beside the top-down pass, which keeps half of the CUs
+    // (its workgroups are persistent and claim tiles in order, so any grid
+    // is correct).  Each is bound by latency as much as by bytes (long H
+    // chains; the tile-to-tile hand-off chain), so together they fill the
+    // memory system better than one after the other: HD256 13.44 -> 12.72,
+    // 4K256 48.03 -> 46.31 ms per frame (profiles/r04_experiments/slant.txt).
+    // (profiled as one more entry, "slant_down_hpair": fork to join on the
+    // frame's stream, the pair's wall time; the two launches' own entries
+    // overlap in time)
+    sa.max_grid = slant_down_grid_eighths(g, nv) * sgm::slant_cus() / 8;
+#ifdef SGM_SLANT_DEBUG
+    // timing probes (wrong maps): SGM_SLANT_SOLO=down|hpair runs that launch
+    // alone on all CUs; =seq runs both, one after the other
+    if (const char *solo = getenv("SGM_SLANT_SOLO")) {
+        sa.max_grid = 0;
+        if (strcmp(solo, "hpair") != 0)
+            HIPCHK(h, timed(h, "slant_down", nv * elems, st, [&] { return sgm::launch_slant_down(sa, g, st); }));
+        if (strcmp(solo, "down") != 0)
+            HIPCHK(h, timed(h, "stage_a_h", nv * elems, st,
+                            [&] { return sgm::launch_stage_a_hpair(hp1, hp2, nv, g, st); }));
+        HIPCHK(h, timed(h, "slant_up", nv * elems, st, [&] { return sgm::launch_slant_up(sa, g, st); }));
+        return SGM_OK;
+    }
+#endif
+    HIPCHK(h, timed(h, "slant_down_hpair", nv * elems, st, [&] {
+        hipError_t e = hipEventRecord(h->ev_fork, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->st_h, h->ev_fork, 0);
+        if (e == hipSuccess)
+            e = timed(h, "slant_down", nv * elems, st, [&] { return sgm::launch_slant_down(sa, g, st); });
+        if (e == hipSuccess)
+            e = timed(h, "stage_a_h", nv * elems, h->st_h,
+                      [&] { return sgm::launch_stage_a_hpair(hp1, hp2, nv, g, h->st_h); });
+        if (e == hipSuccess) e = hipEventRecord(h->ev_join, h->st_h);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_join, 0);
+        return e;
+    }));
+    sa.max_grid = 0;
+    HIPCHK(h, timed(h, "slant_up", nv * elems, st, [&] { return sgm::launch_slant_up(sa, g, st); }));
+    return SGM_OK;
+}
+
+// The cost stage of an SGM frame: the sky masks (sky_detect handles), the
+// census of both images, then each view's DSI and its two cost filters, as far
+// as the schedule's aggregation expects them: C and the L3 checkpoints
+// (whole-volume schedules), the horizontally filtered volumes (bands and the
+// slanted tiles run their own vertical pass), or C and the L3 volumes
+// (*have_c: the slanted schedule's strip pass).
+int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
+    const Geom g = h->g;
+    int rc;
+    const uint8_t *d_sky_l = f.sky_l, *d_sky_r = f.sky_r;
+    int sky_pitch = f.sky_pitch;
+    const double npx = (double)g.H * g.W;
+    // a right-view handle (SGM_VIEW_RIGHT) runs the right view in slot 0
+    const bool right_only = h->p.view == SGM_VIEW_RIGHT;
+    if (h->p.sky_detect) {  // node.cpp:80-93: detect on both inputs, then process with the masks
+        const uint8_t *imgs[2] = {right_only ? f.right : f.left, f.right};
+        HIPCHK(h, timed(h, "sky_detect", npx, st, [&] {
+                   return sgm::launch_sky_detect(imgs, f.pitch, h->d_sky, g.W, h->d_sky_scratch,
+                                                 h->nviews, g, st);
+               }));
+        d_sky_l = h->d_sky[0];
+        d_sky_r = right_only ? h->d_sky[0] : h->nviews == 2 ? h->d_sky[1] : nullptr;
+        sky_pitch = g.W;
+    }
+    HIPCHK(h, timed(h, "census", 2 * npx, st, [&] {  // both images, one launch
+               return sgm::launch_census(f.left, f.pitch, g, h->p.blur, h->d_ct[0], st, false,
+                                         f.right, h->d_ct[1]);
+           }));
+    // min_disp: the shifted table(s) the views' DSIs read (the left view the
+    // right image's, the right view the left image's)
+    if ((rc = sgm::shift_tables(h, h->nviews == 2 || right_only, !right_only, st)) != SGM_OK) return rc;
+    // two views: both DSIs + horizontal IIRs in one launch (a view's H*D
+    // serial chains alone leave most SIMDs idle at KITTI sizes)
+    const bool both_h = h->nviews == 2 && (d_sky_l == nullptr) == (d_sky_r == nullptr) &&
+                        sgm::cost_h2_supported(g, d_sky_l != nullptr);
+    // banded frames run vfwd in forward bands (forward_bands); the slanted
+    // schedule runs its own vertical pass
+    const bool vfwd_here = h->sched != SCHED_BANDS && h->sched != SCHED_SLANT;
+    // the slanted schedule's cost stage as checkpoints + strips (sgm_vstrip.hip):
+    // C and the L3 volumes in one pass, 9 B per element instead of cost_h's
+    // 4 and vfwd_l3's 12
+    const uint8_t *sky0 = right_only ? d_sky_r : d_sky_l;
+    const bool vstrip = h->slant && h->vstrip && sgm::vstrip_supported(g, sky0 != nullptr) &&
+                        (h->nviews == 1 || (sky0 == nullptr) == (d_sky_r == nullptr));
+    // (a masked frame's sky flags go to the strip pass as words, after the
+    // checkpoints in the Ch buffer: 3/16 + 2/D of its floats at most)
+    if (vstrip) {
+        const int dsi0 = right_only ? 1 : 0;
+        HIPCHK(h, timed(h, "cost_ck", h->nviews * npx * g.D, st, [&] {
+                   return sgm::launch_cost_ck(h->d_ct[0], h->d_ct[1], h->d_cts[0], h->d_cts[1], sky0,
+                                              d_sky_r, sky_pitch, dsi0, 1, h->nviews, g, h->d_ch[0],
+                                              h->d_ch[1], st);
+               }));
+        sgm::VStripArgs va{};
+        va.ctl = h->d_ct[0];
+        va.ctr = h->d_ct[1];
+        va.ctl_s = h->d_cts[0];
+        va.ctr_s = h->d_cts[1];
+        if (sky0) {
+            const uint8_t *skm[2] = {sky0, d_sky_r};
+            uint64_t *skw[2] = {nullptr, nullptr};
+            for (int v = 0; v < h->nviews; ++v) {
+                skw[v] = reinterpret_cast<uint64_t *>(h->d_ch[v] + sgm::vstrip_sky_words_offset(g));
+                HIPCHK(h, timed(h, "sky_words", npx, st,
+                                [&] { return sgm::launch_sky_words(skm[v], sky_pitch, g, skw[v], st); }));
+            }
+            va.skw0 = skw[0];
+            va.skw1 = skw[1];
+        }
+        va.dsi0 = dsi0;
+        va.dsi1 = 1;
+        va.ck0 = h->d_ch[0];  // (the checkpoints sit in the dead Ch volumes)
+        va.ck1 = h->d_ch[1];
+        va.c0 = h->d_c[0];
+        va.c1 = h->d_c[1];
+        va.l30 = h->d_l3[0];
+        va.l31 = h->d_l3[1];
+        va.dummy = h->d_slant_dummy;
+        va.p1 = (float)h->p.p1;
+        va.p2 = (float)h->p.p2;
+        HIPCHK(h, timed(h, "vstrip", h->nviews * npx * g.D, st,
+                        [&] { return sgm::launch_vstrip(va, h->nviews, g, st); }));
+    } else if (both_h) {
+        HIPCHK(h, timed(h, "cost_h", 2.0 * npx * g.D, st, [&] {
+                   return sgm::launch_cost_h2(h->d_ct[0], h->d_ct[1], h->d_cts[0], h->d_cts[1], d_sky_l,
+                                              d_sky_r, sky_pitch, g, h->d_ch[0], h->d_ch[1], st);
+               }));
+        if (vfwd_here) {
+            // both views' vertical passes in one launch: W chains per view
+            // leave the CUs under-filled at KITTI (K64 2 x 69.7 -> 90.7 us,
+            // frame -3.9%; K128 two views 177 -> 166 us)
+            // (view 1's columns first, view 0's last, as the per-view passes
+            // ran: stage A then finds more of view 0 in the cache, K64 stage
+            // A -3 us, profiles/r05_experiments/r05s_ab_vfwd2.txt)
+            const int v0 = 1, v1 = 0;
+            const PairArgs pa[2] = {vfwd_args(h, v0), vfwd_args(h, v1)};
+            const float *in[2] = {h->d_ch[v0], h->d_ch[v1]};
+            float *out[2] = {cost_buf(h, v0), cost_buf(h, v1)};
+            HIPCHK(h, timed(h, "vfwd", 2.0 * npx * g.D, st, [&] { return sgm::launch_vfwd2(in, out, pa, g, st); }));
+        }
+    } else {
+        if (h->nviews == 2 && (rc = cost_view(h, 1, 1, d_sky_r, sky_pitch, st, vfwd_here)) != SGM_OK)
+            return rc;
+        if ((rc = cost_view(h, 0, right_only ? 1 : 0, right_only ? d_sky_r : d_sky_l, sky_pitch,
+                            st, vfwd_here)) != SGM_OK)
+            return rc;
+    }
+    *have_c = vstrip;
+    return SGM_OK;
+}
+
+// post_filter and LKRefine at the end of a frame (SGM.cpp:821-824)
+int finish_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
+    int rc;
+    // with LKRefine next, the post filter's last kernel writes LKRefine's
+    // input copy instead of the map (no device copy in between)
+    const bool pf_to_lk = h->p.post_filter && h->p.lk_refine;
+    if (h->p.post_filter && (rc = sgm::post_filter(h, f.out, f.out_pitch, st, pf_to_lk)))  // SGM.cpp:821
+        return rc;
+    if (h->p.lk_refine)  // SGM.cpp:824
+        return sgm::lk_refine(h, f.left, f.right, f.pitch, f.out, f.out_pitch, st, pf_to_lk);
+    return SGM_OK;
+}
+
+}  // namespace
+
+int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
+    const ViewRoles r = view_roles(h, 0, h->d_disp[0], h->d_sub[0], 0);
+    // the L3 checkpoints from the final volume (frames get them from vfwd)
+    HIPCHK(h, timed(h, "pair_fwd_L3", vol_elems(h->g), st,
+                    [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r.fin, h->g, st); }));
+    return h->paths4 ? aggregate4(h, 1, &r, st) : whole_view(h, r, st, true);
+}
+
+int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
+    const Geom g = h->g;
+    const int nv = h->nviews;
+    const double elems = vol_elems(g);
+    int rc;
+    // Everything runs on one stream.  Two-view frames keep each view's cost
+    // volume resident in the 256 MB Infinity Cache through its readers by
+    // running the views' aggregation back to back (K128: 238.5 MB per view;
+    // concurrent views measured 1.627 vs 1.589 ms per pair), unless both
+    // volumes fit together (K64: joint launches) or neither fits (HD/4K:
+    // bands, or the slanted schedule).
+    if (h->p.solver == SGM_SOLVER_BM) return bm_frame(h, f, st);
+    bool have_c = false;
+    if ((rc = cost_stage(h, f, st, &have_c)) != SGM_OK) return rc;
+    // one view with a dense output map: the final pass writes the sub-pixel
+    // map straight into it (no device copy after the frame)
+    const bool direct_out = nv == 1 && f.out_pitch == g.W;
+    // (the raw WTA map, when asked for, is written straight into f.raw by the
+    // left view's final pass; the right view's is never written)
+    ViewRoles r[2] = {};
+    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
+    if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    switch (h->sched) {
+    case SCHED_PATHS4: rc = aggregate4(h, nv, r, st); break;
+    case SCHED_SLANT: rc = slant_views(h, r, st, have_c); break;
+    case SCHED_JOINT: rc = aggregate_joint(h, r, st); break;
+    case SCHED_BANDS: {
+        // the views' forward bands, then their H pairs in one launch, then
+        // each view's backward bands
+        for (int v = 0; v < nv; ++v)
+            if ((rc = forward_bands(h, v, r[v], st)) != SGM_OK) return rc;
+        const PairArgs h1[2] = {r[0].h1, r[nv - 1].h1}, h2[2] = {r[0].h2, r[nv - 1].h2};
+        HIPCHK(h, timed(h, "stage_a_h", nv * elems, st,
+                        [&] { return sgm::launch_stage_a_hpair(h1, h2, nv, g, st); }));
+        for (int v = 0; v < nv; ++v)
+            if ((rc = backward_bands(h, v, r[v], st)) != SGM_OK) return rc;
+        break;
+    }
+    case SCHED_WHOLE_FINAL2:
+        // whole-volume passes above the Infinity Cache (SGM_BAND_ROWS=0):
+        // nothing is gained by finishing the left view first, so both
+        // views' final passes run as one launch (fewer workgroup rounds)
+        for (int v = 0; v < 2; ++v)
+            if ((rc = whole_view(h, r[v], st, false)) != SGM_OK) return rc;
+        HIPCHK(h, timed(h, "pair_bwd_L4_final", 2.0 * elems, st,
+                        [&] { return sgm::launch_final2(r[0].fin, r[1].fin, g, st); }));
+        break;
+    case SCHED_PER_VIEW:
+        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = whole_view(h, r[v], st, true);
+        break;
+    }
+    if (rc != SGM_OK) return rc;
+    if (nv == 2) {
+        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
+                   // (true-disparity maps: the invalid marker is D + min_disp + 1)
+                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
+                                                        h->p.lr_max_diff, h->gt, st)
+                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, f.out,
+                                                     f.out_pitch, h->p.lr_max_diff, h->gt, st);
+               }));
+    } else if (!direct_out) {
+        HIPCHK(h, hipMemcpy2DAsync(f.out, (size_t)f.out_pitch * sizeof(float), h->d_sub[0],
+                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
+                                   hipMemcpyDeviceToDevice, st));
+    }
+    return finish_frame(h, f, st);
+}
+
+// post_filter() (Solver.cpp:600-649) in place on a device map (sgm_post.hip):
+// median-fill launches until one changes nothing, then the speckle removal.
+// The fill works on a separate map and the component kernels write the
+// caller's map from it, so they are enqueued before the host reads the fill's
+// convergence counter (the GPU keeps working through that round trip); in the
+// rare case the fill had not converged, more fill launches run and the
+// component kernels are enqueued again.
+// to_lk: write the filtered map to d_lk_in (contiguous) instead of d_map, for
+// lk_refine(..., staged = true) to read.
+int sgm::post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_lk) {
+    const Geom g = h->gt;  // (a true-disparity map: valid <= D + min_disp - 1)
+    const int budget = h->pf_launches;
+    // The number of median-fill launches depends on a counter read back to
+    // the host each round; under stream capture that copy never runs, so a
+    // captured graph would replay a fixed, possibly unconverged, fill.  (A
+    // launch budget fixes the count and has the device judge it: below.)
+    if (!budget) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIPCHK(h, hipStreamIsCapturing(st, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return set_err(h, SGM_ERR_INVALID_ARG,
+                           "post_filter cannot be captured into a HIP graph (its median-fill launch "
+                           "count is read back to the host); capture frames with post_filter = 0 or "
+                           "set a launch budget (sgm_set_post_filter_launches)");
+    }
+    const double dnpx = (double)g.H * g.W;
+    float *F = h->d_pf_work;
+    HIPCHK(h, timed(h, "post_prep", dnpx, st, [&] {
+               return sgm::launch_pf_prep(d_map, pitch, h->d_pf_orig, F, h->d_pf_changes,
+                                          kMedianMaxLaunches, g, st);
+           }));
+    auto components = [&]() -> int {
+        HIPCHK(h, timed(h, "post_cc_local", dnpx, st, [&] {
+                   return sgm::launch_cc_local(F, h->d_pf_label, h->d_pf_count, h->d_pf_area, g, st);
+               }));
+        HIPCHK(h, timed(h, "post_cc_merge", dnpx, st,
+                        [&] { return sgm::launch_cc_merge(F, h->d_pf_label, g, st); }));
+        HIPCHK(h, timed(h, "post_cc_count", dnpx, st, [&] {
+                   return sgm::launch_cc_count(h->d_pf_label, h->d_pf_count, h->d_pf_area, 1000 / g.scale,
+                                               g, st);
+               }));
+        // speckle_filter_new(filtered_disp, invalid_disp, SPECKLE_SIZE/scale, SPECKLE_DIS), :645
+        HIPCHK(h, timed(h, "post_cc_apply", dnpx, st, [&] {
+                   return sgm::launch_cc_apply(F, h->d_pf_label, h->d_pf_area, 1000 / g.scale,
+                                               (float)(g.D + 1), to_lk ? h->d_lk_in : d_map,
+                                               to_lk ? g.W : pitch, g, st);
+               }));
+        return SGM_OK;
+    };
+    int k = 0, rc;
+    if (budget) {
+        // Fixed budget: exactly `budget` fill launches (those after the proof
+        // return at their first instruction), the device's verdict on the
+        // last counter, the component kernels once.  Nothing is read back and
+        // nothing waits: the call returns after enqueueing and can be captured.
+        // (with profiling on, one event pair around the whole sequence: a
+        // budget of thousands must not take thousands of pooled events)
+        HIPCHK(h, timed(h, "post_median", dnpx, st, [&] {
+                   hipError_t e = hipSuccess;
+                   for (; k < budget && e == hipSuccess; ++k)
+                       e = sgm::launch_median_fill(h->d_pf_orig, F, k, h->d_pf_snap,
+                                                   h->d_pf_changes, h->mf_rows, g, st);
+                   if (e == hipSuccess)
+                       e = sgm::launch_pf_verdict(h->d_pf_changes, budget, h->d_pf_err, st);
+                   return e;
+               }));
+        h->pf_iters = k;
+        return components();
+    }
+    for (;;) {
+        // a fill usually settles in 2 launches and the 3rd proves it
+        const int batch = k == 0 ? 3 : 2;
+        for (int b = 0; b < batch; ++b, ++k)
+            HIPCHK(h, timed(h, "post_median", dnpx, st, [&] {
+                       return sgm::launch_median_fill(h->d_pf_orig, F, k, h->d_pf_snap,
+                                                      h->d_pf_changes, h->mf_rows, g, st);
+                   }));
+        HIPCHK(h, hipMemcpyAsync(h->h_pf_changes, h->d_pf_changes + k - 1, sizeof(int),
+                                 hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipEventRecord(h->ev_pf, st));
+        if ((rc = components())) return rc;
+        HIPCHK(h, hipEventSynchronize(h->ev_pf));
+        if (*h->h_pf_changes == 0) break;
+        if (k + 2 > kMedianMaxLaunches)
+            return set_err(h, SGM_ERR_HIP, "post_filter: median fill did not converge in %d launches",
+                           k);
+    }
+    h->pf_iters = k;
+    return SGM_OK;
+}
+
+// LKRefine (sgm_lk.hip) in place on a device map: the kernel reads a
+// contiguous copy of the map and writes the refined values back.
+// staged: d_lk_in already holds the map (post_filter(..., to_lk = true))
+int sgm::lk_refine(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int pitch,
+                   float *d_map, int map_pitch, hipStream_t st, bool staged) {
+    const Geom g = h->gt;  // (DispValid: 0 < d < D + min_disp)
+    const size_t row = (size_t)g.W * sizeof(float);
+    if (!staged)
+        HIPCHK(h, hipMemcpy2DAsync(h->d_lk_in, row, d_map, (size_t)map_pitch * sizeof(float), row,
+                                   g.H, hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, timed(h, "lk_refine", (double)g.H * g.W, st, [&] {
+               return sgm::launch_lk_refine(d_left, d_right, pitch, h->d_lk_in, d_map, map_pitch, g,
+                                            st);
+           }));
+    return SGM_OK;
+}

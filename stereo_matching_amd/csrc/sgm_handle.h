@@ -1,0 +1,296 @@
+// sgm_handle.h -- the handle behind include/sgm_hip.h and the host helpers
+// every function that works on it uses: shared by the C-ABI (sgm_capi.hip) and
+// the frame schedules (sgm_frame.hip).  Host-only; not part of the public
+// interface.
+#pragma once
+
+#include "../../include/sgm_hip.h"
+#include "sgm_internal.h"
+
+#include <algorithm>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+
+using sgm::Geom;
+using sgm::SweepArgs;
+
+// How run_frame aggregates (DESIGN.md "Frame schedule"): fixed at sgm_create by
+// the handle's paths, views, volume size and the SGM_SLANT / SGM_BAND_ROWS
+// switches.
+enum Schedule {
+    SCHED_PATHS4,        // the 4-path passes, both views per launch
+    SCHED_SLANT,         // the slanted tiles
+    SCHED_JOINT,         // two views whose volumes fit the Infinity Cache together: joint launches
+    SCHED_BANDS,         // forward bands, the H pair, backward bands (volumes above the cache)
+    SCHED_WHOLE_FINAL2,  // two views above the cache, unbanded: whole-volume passes, one final launch
+    SCHED_PER_VIEW       // whole-volume passes, view after view
+};
+
+struct sgm_handle {
+    sgm_params p;
+    Geom g;
+    Geom gt;              // g with D + min_disp for D: the geometry of every stage that works on
+                          // true-disparity maps (LR check, post filter, LKRefine, confidence
+                          // filter, point cloud: valid <= D+m-1, invalid D+m+1)
+    int device;
+    int nviews;
+    size_t bytes;         // of the device allocations below
+    std::vector<void *> allocs;  // every live dalloc (free_all frees these; dfree removes one)
+    hipStream_t st;      // the handle's own stream (host API, stages)
+    hipEvent_t ev_pf;     // the post filter's convergence readback
+    hipEvent_t ev_last;   // the end of the last call's work on last_st (StreamScope)
+    hipStream_t last_st;  // the stream of the last entry point's work (null: none yet)
+    bool last_recorded;   // ev_last was recorded at the end of that call (a caller's stream)
+    uint8_t *d_in[2];     // full-size input staging (host API)
+    uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
+    uint64_t *d_ct[2];    // census words
+    int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
+    uint64_t *d_cts[2];   // the tables shifted by min_disp / scale columns (launch_ct_shift):
+                          // [0] the left image's (the right view's DSI reads it), [1] the right
+                          // image's (the left view's); min_disp = 0: d_ct[0], d_ct[1] themselves
+    float *d_ch[2];       // horizontally filtered cost; reused as the T chain
+    float *d_ch_base[2];  // its allocation: d_ch is preceded by t_guard_rows rows (final pass)
+    float *d_c[2];        // final cost volume (+ kVolGuard: row-walking prefetch rings)
+    float *d_s[2];        // S chain
+    uint16_t *d_disp[2];  // WTA disparity
+    float *d_sub[2];      // sub-pixel disparity
+    float *d_ratio[2];    // match confidence min / second-min (sgm_set_confidence; null: off)
+    bool ratio_cm[2];     //   the last final pass stored it column-major (as its sub-pixel map)
+    float *d_out;         // LR-checked output (host API)
+    float *d_min;         // minL (stage_path)
+    float *d_zero;        // 256 zero floats (PairArgs::zero)
+    float *d_ck[2][3];    // checkpoints per view and pair family (H, V, D2)
+    float *d_carry[2][3]; // banded backward passes: chain state at band edges (L7, L8, L4)
+    bool slant;           // the slanted-tile schedule (sgm_slant.hip, DESIGN.md "Slanted tiles")
+    bool vstrip;          //   its cost stage as checkpoints + strips (sgm_vstrip.hip; SGM_VSTRIP=0: off)
+    float *d_l3[2];       // slant: the full L3 volume per view
+    unsigned long long *d_gran;  // slant: hand-off granules (both views)
+    sgm::SlantCtl *d_slant_ctl;  // slant: launch bookkeeping of the passes
+    float *d_slant_dummy;        // slant: the target of inactive lanes' stores
+    bool paths4;          // params.paths == 4: the 4-path schedule (aggregate4; no bands, no slant)
+    bool p4_split;        //   its H pair as forward + two-wave backward launches (SGM_P4_HPAIR)
+    int band_rows;        // rows per band of the backward phase (0: whole volume)
+    Schedule sched;       // the aggregation's schedule
+    int sub_cm;           // 1: the final passes store column-major sub-pixel maps (two views; the
+                          // LR check reads them through LDS tiles); the slanted pass stores row-major
+    int mf_rows;          // median fill tile rows (4 or 8 by frame size; SGM_MF_ROWS)
+    // post_filter scratch (sgm_post.hip)
+    float *d_pf_orig;     // the map as it entered the median fill
+    float *d_pf_work;     // contiguous working map (pitched callers)
+    int *d_pf_label;      // union-find parents
+    int *d_pf_count;      // pixels under each tile-local root
+    int *d_pf_area;       // component sizes
+    float *d_pf_snap;     // per median tile: the working-map cells it last read
+    int *d_pf_changes;    // per median launch: tiles that changed a pixel
+    int *h_pf_changes;    // pinned readback of one counter
+    unsigned *h_pf_err;   // host-mapped word: the budget of a fixed-budget fill that was not proven (0: none)
+    unsigned *d_pf_err;   //   its device-side address (pf_verdict_kernel)
+    int pf_launches;      // sgm_set_post_filter_launches: 0 = adaptive, else the fixed budget
+    unsigned *h_slant_err;  // slant: host-mapped hang-guard word (SlantArgs::err_host)
+    hipStream_t st_h;       // slant: the H pair's stream, beside the top-down pass
+    hipEvent_t ev_fork, ev_join;  //   its fork from / join into the frame's stream
+    unsigned *d_slant_err;  //   its device-side address
+    int pf_iters;         // median launches of the last post filter
+    float *d_lk_in;       // LKRefine input copy (the kernel refines the map in place)
+    uint8_t *d_sky_scratch;  // sky detector scratch (sgm_sky.hip)
+    int *d_cloud_counts;  // point cloud: per-row counts -> offsets, then the total
+    uint8_t *h_pin;       // pinned host staging for sgm_process (allocated on first use)
+    size_t h_pin_bytes;
+    char err[512];
+    // profiling (sgm_set_profiling)
+    int profiling;
+    std::vector<hipEvent_t> ev_pool;
+    struct Pending { int cls; double elems; hipEvent_t a, b; };
+    std::vector<Pending> pending;
+    std::vector<sgm_kernel_stat> stats;
+    std::vector<double> stat_elems;  // elements of the class's launches since the last readout
+};
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// Every entry point's work shares the handle's scratch (cost volumes,
+// checkpoints, post-filter and LKRefine buffers), whichever stream the caller
+// passes.
+// Orders calls on different streams (they share the handle's scratch).  A
+// call on a CALLER's stream records ev_last on that stream as it returns,
+// while the stream certainly exists (a rocprof trace shows the record as a
+// ~5 us gap before the next kernel; frame loops can run on the handle's own
+// stream, sgm_get_stream, instead); a call on the handle's own stream
+// records nothing (the same-stream path stays free of event records) and a later
+// call on another stream records ev_last on the handle's stream, which the
+// handle owns.  So no stream handle of the caller is kept past the call that
+// used it.  Entry points construct the scope after their argument checks, so
+// a call rejected before enqueueing anything leaves the state untouched.
+struct StreamScope {
+    sgm_handle *h;
+    hipStream_t st;
+    StreamScope(sgm_handle *handle, void *stream)
+        : h(handle), st(stream ? (hipStream_t)stream : handle->st) {
+        if (h->last_st && h->last_st != st) {
+            if (h->last_recorded)
+                (void)hipStreamWaitEvent(st, h->ev_last, 0);
+            else if (hipEventRecord(h->ev_last, h->last_st) == hipSuccess)
+                (void)hipStreamWaitEvent(st, h->ev_last, 0);
+        }
+    }
+    ~StreamScope() {
+        h->last_st = st;
+        h->last_recorded = st != h->st && hipEventRecord(h->ev_last, st) == hipSuccess;
+    }
+};
+
+inline int set_err(sgm_handle *h, int code, const char *fmt, ...) {
+    if (h) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(h->err, sizeof(h->err), fmt, ap);
+        va_end(ap);
+    }
+    return code;
+}
+
+#define HIPCHK(h, expr)                                                                      \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return set_err((h), e_ == hipErrorOutOfMemory ? SGM_ERR_OUT_OF_MEMORY : SGM_ERR_HIP, \
+                           "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,   \
+                           __LINE__);                                                        \
+    } while (0)
+
+template <typename T>
+int dalloc(sgm_handle *h, T **p, size_t count) {
+    *p = nullptr;
+    if (count == 0) return SGM_OK;
+    HIPCHK(h, hipMalloc((void **)p, count * sizeof(T)));
+    h->bytes += count * sizeof(T);
+    h->allocs.push_back(*p);
+    return SGM_OK;
+}
+
+// Frees a dalloc of `count` elements and nulls the pointer (null: nothing).
+template <typename T>
+void dfree(sgm_handle *h, T **p, size_t count) {
+    if (!*p) return;
+    (void)hipFree(*p);
+    auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
+    if (it != h->allocs.end()) h->allocs.erase(it);
+    h->bytes -= count * sizeof(T);
+    *p = nullptr;
+}
+
+// elements of one view's cost volume
+inline double vol_elems(Geom g) { return (double)g.H * g.W * g.D; }
+
+inline hipEvent_t pool_event(sgm_handle *h) {
+    if (!h->ev_pool.empty()) {
+        hipEvent_t e = h->ev_pool.back();
+        h->ev_pool.pop_back();
+        return e;
+    }
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+    return e;
+}
+
+inline int stat_class(sgm_handle *h, const char *name, double elems) {
+    for (size_t k = 0; k < h->stats.size(); ++k)
+        if (!strncmp(h->stats[k].name, name, sizeof(h->stats[k].name))) return (int)k;
+    sgm_kernel_stat st{};
+    snprintf(st.name, sizeof(st.name), "%s", name);
+    st.elems = elems;
+    h->stats.push_back(st);
+    h->stat_elems.push_back(0.0);
+    return (int)h->stats.size() - 1;
+}
+
+// Launch `fn` on `st`; with profiling on, bracket it with pooled events.
+template <typename F>
+hipError_t timed(sgm_handle *h, const char *name, double elems, hipStream_t st, F &&fn) {
+    if (!h->profiling) return fn();
+    hipEvent_t a = pool_event(h), b = pool_event(h);
+    if (!a || !b) return hipErrorOutOfMemory;
+    hipError_t e = hipEventRecord(a, st);
+    if (e == hipSuccess) e = fn();
+    if (e == hipSuccess) e = hipEventRecord(b, st);
+    h->pending.push_back({stat_class(h, name, elems), elems, a, b});
+    return e;
+}
+
+// Upper bound on median-fill launches of one post filter: the fill reaches its
+// fixed point in 2-3 launches on stereo output; the bound only stops a runaway.
+constexpr int kMedianMaxLaunches = 4096;
+
+inline SweepArgs sweep_args(const sgm_handle *h) {
+    SweepArgs a{};
+    a.p1 = (float)h->p.p1;
+    a.p2 = (float)h->p.p2;
+    a.uniq = h->p.uniqueness;
+    return a;
+}
+
+inline sgm::PairArgs pair_args(const sgm_handle *h) {
+    sgm::PairArgs a{};
+    a.zero = h->d_zero;
+    a.p1 = (float)h->p.p1;
+    a.p2 = (float)h->p.p2;
+    a.uniq = h->p.uniqueness;
+    a.min_disp = h->min_disp;
+    return a;
+}
+
+// vfwd's arguments for a view: the L3 checkpoints it writes
+inline sgm::PairArgs vfwd_args(const sgm_handle *h, int view) {
+    sgm::PairArgs a = pair_args(h);
+    a.ckpt = h->d_ck[view][sgm::PAIR_V];
+    return a;
+}
+
+// the census table pair of a DSI (0: left view, 1: right view): the other
+// image's table is the min_disp-shifted one
+inline const uint64_t *ct_left(const sgm_handle *h, int dsi) { return dsi ? h->d_cts[0] : h->d_ct[0]; }
+inline const uint64_t *ct_right(const sgm_handle *h, int dsi) { return dsi ? h->d_ct[1] : h->d_cts[1]; }
+
+// the view's final cost volume C and its T chain (T reuses the horizontally
+// filtered volume, dead once vfwd has read it; an in-place vfwd with T in the
+// second volume measured no faster, profiles/r03_experiments/inplace_c.txt)
+inline float *cost_buf(sgm_handle *h, int v) { return h->d_c[v]; }
+inline float *t_buf(sgm_handle *h, int v) { return h->d_ch[v]; }
+
+// One frame's device buffers, as sgm_process_device takes them.
+struct FrameIO {
+    const uint8_t *left, *right;  // full-size images
+    int pitch;
+    const uint8_t *sky_l, *sky_r;  // working-grid sky masks (null: none)
+    int sky_pitch;
+    float *out;                   // the frame's map
+    int out_pitch;
+    uint16_t *raw;                // the left view's raw WTA map (null: not wanted)
+};
+
+// sgm_frame.hip: what the C-ABI calls into it
+namespace sgm {
+int run_frame(sgm_handle *h, FrameIO f, hipStream_t st);
+int post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_lk = false);
+int lk_refine(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int pitch,
+              float *d_map, int map_pitch, hipStream_t st, bool staged = false);
+int shift_tables(sgm_handle *h, bool left, bool right, hipStream_t st);
+// sgm_stage_aggregate: view 0's aggregation from the final cost volume in
+// d_c[0], whole-volume passes on every handle, into d_disp[0] and d_sub[0]
+int stage_aggregate(sgm_handle *h, hipStream_t st);
+bool slant_default(Geom g, int nviews);
+int band_rows_for(Geom g);
+int slant_cus();
+}  // namespace sgm

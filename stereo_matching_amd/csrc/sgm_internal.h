@@ -1,5 +1,5 @@
-// sgm_internal.h -- kernel launchers shared by the C-ABI (sgm_capi.hip) and
-// the kernels (sgm_kernels.hip).  Not part of the public interface.
+// sgm_internal.h -- kernel launchers shared by the host side (sgm_capi.hip,
+// sgm_frame.hip) and the kernel files.  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -68,7 +68,7 @@ def test_gpus_must_match_world_size():
     assert not [x for x in r.stdout.splitlines() if x.startswith("{")]
 
 
-# kernel families the frame schedules launch (sgm_capi.hip run_frame): every
+# kernel families the frame schedules launch (sgm_frame.hip run_frame): every
 # instantiation the library holds must map to a profiler name, so that the PMC
 # passes (tools/pmc_reduce.py) and the timer check see each launch of a frame
 FRAME_KERNELS = ("census_kernel<", "cost_h_kernel<", "cost_h2_kernel<", "cost_h_global_kernel<",

@@ -1,6 +1,6 @@
 """The frame schedules give the same maps bit for bit.
 
-run_frame (sgm_capi.hip) picks the schedule by volume size: joint two-view
+run_frame (sgm_frame.hip) runs the schedule picked at sgm_create by volume size: joint two-view
 launches when both cost volumes fit the 256 MB Infinity Cache together,
 per-view whole-volume passes below 256 MB per view, bands above it
 (SGM_BAND_ROWS overrides the band size, 0 = whole-volume passes and the joint
@@ -131,7 +131,7 @@ def test_calls_on_different_streams_are_ordered():
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("views", [2, 1])
 def test_slant_default_by_size(views, monkeypatch):
-    # sgm_capi.hip slant_default: at D = 256 above the Infinity Cache the
+    # sgm_frame.hip slant_default: at D = 256 above the Infinity Cache the
     # slanted passes run once every workgroup gets 0.5 full-height tiles of
     # work (views x W >= 0.5 x 14 x CUs; on a 256-CU MI355X HD256 with two
     # views, 3840 >= 1792, and with one view, 1920: both slanted since round

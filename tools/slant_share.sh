@@ -1,5 +1,5 @@
 #!/bin/bash
-# The top-down slanted pass's share of the CUs beside the H pair (sgm_capi.hip
+# The top-down slanted pass's share of the CUs beside the H pair (sgm_frame.hip
 # slant_down_grid_eighths), swept on the debug build (SGM_SLANT_DOWN_EIGHTHS).
 # Usage (GPU box): bash tools/slant_share.sh CONFIG REPS "EIGHTHS..."
 set -o pipefail

@@ -1,6 +1,6 @@
 """Frame time of the slanted-tile schedule (at several top-down CU shares)
 against the default non-slanted schedule (bands above the Infinity Cache,
-whole-volume pairs below it), per frame size: sets sgm_capi.hip
+whole-volume pairs below it), per frame size: sets sgm_frame.hip
 slant_default and slant_down_grid_eighths.  Runs the -DSGM_SLANT_DEBUG build
 (SGM_SLANT_DOWN_EIGHTHS); each size: one handle per variant, 2 warm-up frames,
 6 timed frames on device-resident inputs, alternated REPS times, best kept.
