@@ -19,6 +19,33 @@ constexpr int pair_kv() { return seg_k_v(V); }
 template <int FAM, int V>
 constexpr int family_k() { return FAM == PAIR_V ? pair_kv<V>() : pair_k<V>(); }
 
+// The launchers' one map from a frame's D to the kernels' compile-time width:
+// f(V, FULL) with V = vals_per_lane(D) values per lane and FULL = all 64 lanes
+// hold data (D >= 64), as std::integral_constant tags.  The tags convert to
+// their values in constant expressions, so f (a generic lambda) names them
+// as template arguments: K<V, FULL, ...><<<...>>>(...).  D = 32, 64 and 128
+// are matched exactly and every other D runs as 256 (sgm_create admits
+// only these four).
+template <int D, class F>
+inline void call_width(F &f) {
+    f(std::integral_constant<int, vals_per_lane(D)>{}, std::bool_constant<(D >= 64)>{});
+}
+template <class F>
+inline void for_width(int D, F &&f) {
+    if (D == 32) call_width<32>(f);
+    else if (D == 64) call_width<64>(f);
+    else if (D == 128) call_width<128>(f);
+    else call_width<256>(f);
+}
+
+// Depth PF of the cost prefetch rings (steps of loads in flight) by values
+// per lane: the rows' chains (few, long, latency-bound) run twice as deep as
+// the columns' and diagonals'; four values per lane halve both (registers).
+template <int V>
+constexpr int pf_rows() { return V >= 4 ? 16 : 32; }
+template <int V>
+constexpr int pf_cols() { return V >= 4 ? 8 : 16; }
+
 template <int V>
 __device__ __forceinline__ float lane_min(const float (&x)[V]) {
     float m = x[0];
@@ -32,8 +59,8 @@ __device__ __forceinline__ float lane_min(const float (&x)[V]) {
 // One direction over one path, one wavefront; lane l holds disparities
 // l*V .. l*V+V-1 (FULL: all 64 lanes hold data, i.e. D >= 64; D = 32 uses
 // lanes 0..31 and +inf above).  Loads run PF steps ahead of the DP through a
-// register ring.  Modes STORE_L / INIT / ACC (the final sweep has its own
-// two-wave kernel).
+// register ring.  Modes STORE_L / INIT / ACC (the final pass is
+// pair_final_kernel, sgm_pair.hip).
 #ifdef SGM_STAMPS
 // per role (0-2 final producer/consumer/WTA, 3-4 H producer/consumer):
 // work cycles, barrier-wait cycles, waves
@@ -51,7 +78,6 @@ __device__ __forceinline__ void stamp_flush(int role, long long t0) {
 // backward bands, L5 (DIR 4) of the forward bands)
 template <int DIR, int V, int MODE, bool FULL, int PF, bool BAND = false>
 __device__ __forceinline__ void sweep_body(const SweepArgs &a, const Geom &g, int path) {
-    static_assert(MODE != SWEEP_FINAL, "the final pass is pair_final_kernel");
 #ifdef SGM_STAMPS
     const long long st_t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -454,22 +480,17 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs &a, const Geom &g, 
 
 // ------------------------------------------------------- backward pass
 
-// tb/pb: the FINAL mode's LDS ring (two chunks of K total-cost rows and
-// pixel positions), unused otherwise.
+// MODE INIT2 or ACC, stored to a.out (the final pass is pair_split_body's).
 template <int FAM, int V, bool FULL, int MODE, bool BAND = false, bool NTC = false>
-__device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, int path,
-                                              float (*tb)[family_k<FAM, V>()][tbuf_stride<V>()],
-                                              long long (*pb)[family_k<FAM, V>()]) {
+__device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, int path) {
+    static_assert(MODE == PAIR_INIT2 || MODE == PAIR_ACC, "the final pass is pair_split_body");
 #ifdef SGM_STAMPS
     const long long st_t0 = __builtin_amdgcn_s_memtime();
 #endif
     constexpr int FD = FAM == PAIR_H ? 0 : (FAM == PAIR_V ? 2 : 5);
     constexpr int BD = FAM == PAIR_H ? 1 : (FAM == PAIR_V ? 3 : 6);
     constexpr int K = family_k<FAM, V>();
-    constexpr bool FINAL = MODE == PAIR_FINAL;
-    constexpr bool NEED_ACC = MODE != PAIR_INIT2;
-    constexpr bool NEED_S = FINAL;
-    const int wave = wave_id();
+    constexpr bool NEED_ACC = MODE == PAIR_ACC;
     const float p2v = to_vgpr(a.p2);  // dp_step's P2 operand
     const int lane = tid_x() & 63;
     const int H = g.H, W = g.W;
@@ -488,18 +509,6 @@ __device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, 
     const int ke = BANDED && a.band.ke > 0 ? a.band.ke : n;
     const int s_hi = nseg - 1 - kb / K, s_lo = nseg - (ke + K - 1) / K;
 
-    if constexpr (FINAL) {
-        if (wave == 1) {  // WTA consumer, one chunk per segment
-            lds_barrier();
-            for (int c = 0; c < nseg; ++c) {
-                wta_consume_chunk<V, K>(tb[c & 1], pb[c & 1], c == nseg - 1 ? r0 : K, lane,
-                                        g.D, a.uniq, a.disp, a.sub, a.ratio, a.min_disp);
-                lds_barrier();
-            }
-            return;
-        }
-    }
-
     // the backward direction walks the same chain in reverse: for the wrapped
     // anti-diagonals chain g of L6 is chain (g - (H-1)) mod W of L7
     const int bpath = FAM == PAIR_D2 ? uniform(((path - (H - 1)) % W + W) % W) : path;
@@ -513,11 +522,10 @@ __device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, 
         bc.init(bpath, H, W, g.D);
         pc.init(bpath, H, W, g.D);
     }
-    float ab[K][V], sb[K][V];
+    float ab[K][V];
 #pragma unroll
     for (int u = 0; u < K; ++u) {
         if (NEED_ACC) load_v_nt<V>(ab[u], a.acc_in + pc.off + e0, active);
-        if (NEED_S) load_v_nt<V>(sb[u], a.s_in + pc.off + e0, active);
         pc.advance_upto(ke, W, D, WD);
     }
 
@@ -587,7 +595,6 @@ __device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, 
             }
         }
         // 2) backward direction over the segment, combined on the fly
-        const int buf = (nseg - 1 - s) & 1;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
             const int kk = K - 1 - r;
@@ -603,28 +610,20 @@ __device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, 
 #pragma unroll
                     for (int v = 0; v < V; ++v) o[v] = lf[kk][v] + L[v];
                     store_v_nt<V>(a.out + bc.off + e0, o, active);
-                } else if constexpr (MODE == PAIR_ACC) {
+                } else {
                     float o[V];
 #pragma unroll
                     for (int v = 0; v < V; ++v) o[v] = (ab[r][v] + lf[kk][v]) + L[v];
                     store_v_nt<V>(a.out + bc.off + e0, o, active);
-                } else if constexpr (FINAL) {
-                    float tot[V];
-#pragma unroll
-                    for (int v = 0; v < V; ++v) tot[v] = ((sb[r][v] + lf[kk][v]) + L[v]) + ab[r][v];
-                    store_lds_v<V>(&tb[buf][r][e0], tot);
-                    if (lane == 0) pb[buf][r] = (long long)bc.i * W + bc.j;
                 }
 #pragma unroll
                 for (int v = 0; v < V; ++v) prevb[v] = L[v];
                 pminb = nmin;
                 bc.advance(W, D, WD);
                 if (NEED_ACC) load_v_nt<V>(ab[r], a.acc_in + pc.off + e0, active);
-                if (NEED_S) load_v_nt<V>(sb[r], a.s_in + pc.off + e0, active);
                 pc.advance_upto(ke, W, D, WD);
             }
         }
-        if (FINAL) lds_barrier();
     };
 
     // Full segments two at a time (branch-free bodies keep the wait counts
@@ -653,7 +652,6 @@ __device__ __forceinline__ void pair_bwd_body(const PairArgs &a, const Geom &g, 
         last(c0);
     }
     if (BANDED && ke < n) store_v<V>(a.band.carry + (size_t)path * g.D + e0, prevb, active);
-    if (FINAL) lds_barrier();
 #ifdef SGM_STAMPS
     stamp_flush(FAM == PAIR_D2 ? 11 : (FAM == PAIR_H ? 13 : 14), st_t0);
 #endif
@@ -715,7 +713,7 @@ __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g
     static_assert(!NOT || (MODE == PAIR_FINAL && !BAND), "4-path final pass: whole-volume only");
     static_assert(RH == 1 || RH == 2, "consumer ring halves");
     // the final pass's WTA loads reach K-1 rows above row 0 of T: the guard
-    // allocated before T (t_guard_rows, sgm_capi.hip) must cover them
+    // allocated before T (t_guard_rows, sgm_internal.h) must cover them
     static_assert(MODE != PAIR_FINAL || K - 1 <= t_guard_rows(V == 4 ? 256 : (V == 2 ? 128 : 64)),
                   "T guard rows");
     constexpr int FD = FAM == PAIR_H ? 0 : (FAM == PAIR_V ? 2 : 5);
@@ -989,7 +987,7 @@ __device__ __forceinline__ void pair_split_body(const PairArgs &a, const Geom &g
         // T rows of chunk c: slot r is row H-1 - (cK + r).  Addressed from the
         // chunk's top row (slot K-1; a wave-uniform pointer) plus this lane's
         // constant byte offset; the partial last chunk's unused slots point
-        // into the volume's leading guard (kTGuardRows rows, never consumed).
+        // into the volume's leading guard (t_guard_rows rows, never consumed).
         const unsigned t_off = (unsigned)((((size_t)(K - 1 - slot) * W) * D + d0) * sizeof(float));
         auto tload = [&](float (&t)[QQ], int c) {
             const long long top = (long long)(H - K - c * K) * W + path;

@@ -55,10 +55,6 @@ __device__ __forceinline__ float dppf(float old, float src) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src),
                                                       CTRL, ROW_MASK, BANK_MASK, false));
 }
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
-__device__ __forceinline__ int dppi(int old, int src) {
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
-}
 
 // DPP controls (GFX9 encoding, valid on gfx950).
 constexpr int DPP_QP_1032 = 0xB1;   // quad_perm [1,0,3,2]
@@ -174,16 +170,6 @@ __device__ __forceinline__ float nbmin_self(float x) {
     else
         asm("s_nop 1\n\tv_min_f32_dpp %0, %0, %0 wave_shl:1 row_mask:0xf bank_mask:0xf" : "+v"(x));
     return x;
-}
-
-__device__ __forceinline__ int wave_min_i(int x) {
-    x = min(x, movdpp<DPP_QP_1032>(x));
-    x = min(x, movdpp<DPP_QP_2301>(x));
-    x = min(x, movdpp<DPP_HALF_MIRROR>(x));
-    x = min(x, movdpp<DPP_MIRROR>(x));
-    x = min(x, movdpp<DPP_BCAST15, 0xA>(x));
-    x = min(x, movdpp<DPP_BCAST31, 0xC>(x));
-    return __builtin_amdgcn_readlane(x, 63);
 }
 
 __device__ __forceinline__ float readlane_f(float x, int lane) {
@@ -423,9 +409,9 @@ __device__ __forceinline__ void dp_step(const float (&prev)[V], float pmin, cons
 
 // x[d] of a wave-spread vector (lane d / V, slot d % V) for a wave-uniform d:
 // V readlanes and scalar selects.  (A select chain on the slot in VALU
-// registers, pick() below, is lowered by hipcc to a dynamically indexed
-// private array: scratch stores and loads, whose vmcnt waits then also wait
-// for every prefetch load in flight.)
+// registers is lowered by hipcc to a dynamically indexed private array:
+// scratch stores and loads, whose vmcnt waits then also wait for every
+// prefetch load in flight.)
 template <int V>
 __device__ __forceinline__ float wave_pick(const float (&x)[V], int d) {
     const int l = d / V, v = d - l * V;
@@ -435,14 +421,6 @@ __device__ __forceinline__ float wave_pick(const float (&x)[V], int d) {
         const float t = readlane_f(x[k], l);
         r = v == k ? t : r;
     }
-    return r;
-}
-
-template <int V>
-__device__ __forceinline__ float pick(const float (&x)[V], int v) {
-    float r = x[0];
-#pragma unroll
-    for (int k = 1; k < V; ++k) r = v == k ? x[k] : r;
     return r;
 }
 
@@ -520,118 +498,10 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Partial WTA state over a set of disparities: the minimum m and the first
-// index i holding it, and the smallest value s != m with its first index si
-// (SGM.cpp:383-408: min_cost/min_d, sec_min_cost/sec_min_d).
-struct Wta {
-    float m, s;
-    int i, si;
-};
-
-// Combine two disjoint partial states (ties go to the lower index, so the
-// merge is symmetric and any lane pairing may be used).
-__device__ __forceinline__ Wta wta_merge(const Wta &A, const Wta &B) {
-    // branch-free selects (a pointer-select here made hipcc spill to scratch)
-    const bool a_lt = A.m < B.m, b_lt = B.m < A.m;
-    Wta r;
-    r.m = fminf(A.m, B.m);
-    r.i = a_lt ? A.i : (b_lt ? B.i : min(A.i, B.i));
-    const float c1 = b_lt ? B.s : A.s;
-    const int j1 = b_lt ? B.si : A.si;
-    const float c2 = a_lt ? B.m : (b_lt ? A.m : B.s);
-    const int j2 = a_lt ? B.i : (b_lt ? A.i : B.si);
-    r.s = fminf(c1, c2);
-    r.si = c1 < c2 ? j1 : (c2 < c1 ? j2 : min(j1, j2));
-    return r;
-}
-
-template <int CTRL>
-__device__ __forceinline__ Wta wta_dpp(const Wta &x) {
-    Wta y;
-    y.m = movdppf<CTRL>(x.m);
-    y.s = movdppf<CTRL>(x.s);
-    y.i = movdpp<CTRL>(x.i);
-    y.si = movdpp<CTRL>(x.si);
-    return wta_merge(x, y);
-}
-
-// Merge with the lane 16 apart inside each 32-lane half (ds_swizzle bit mode,
-// xor_mask 0x10): the cross-row step when a pixel spans 32 lanes.
-__device__ __forceinline__ Wta wta_swz16(const Wta &x) {
-    constexpr int PAT = 0x1F | (0x10 << 10);
-    Wta y;
-    y.m = __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x.m), PAT));
-    y.s = __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x.s), PAT));
-    y.i = __builtin_amdgcn_ds_swizzle(x.i, PAT);
-    y.si = __builtin_amdgcn_ds_swizzle(x.si, PAT);
-    return wta_merge(x, y);
-}
-
 // LDS image of one chunk: PF pixels x D total costs, rows padded by 16 bytes
 // so the consumer's per-pixel reads spread over all banks.
 template <int V>
 constexpr int tbuf_stride() { return 64 * V + 4; }
-
-// WTA + uniqueness + sub-pixel (SGM.cpp:376-418, Solver.cpp:577-593) for
-// `cnt` <= PF pixels whose total cost vectors sit in LDS rows tb[0..cnt), all
-// at once: 64/PF lanes per pixel, each scanning D*PF/64 costs in ascending d,
-// the partial states merged with DPP.  Pixel positions come from pb.
-template <int V, int PF>
-__device__ __forceinline__ void wta_consume_chunk_at(const float (*tb)[tbuf_stride<V>()],
-                                                     long long pix0, long long pix_step, int cnt,
-                                                     int lane, int Dn, float uniq,
-                                                     uint16_t *disp, float *sub,
-                                                     float *ratio = nullptr, int moff = 0) {
-    constexpr int LPP = 64 / PF;  // lanes per pixel
-    const int Q = Dn / LPP;       // disparities per lane (>= 8)
-    const int px = lane / LPP, q = lane - px * LPP;
-    const int d0 = q * Q;
-    const float *row = tb[px < cnt ? px : 0];
-    Wta w;
-    w.m = SGM_INF; w.s = SGM_INF; w.i = INT_MAX; w.si = INT_MAX;
-    for (int k = 0; k < Q; k += 4) {
-        const float4 x4 = *reinterpret_cast<const float4 *>(row + d0 + k);
-        const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float x = xs[e];
-            const int d = d0 + k + e;
-            const bool lt = x < w.m;
-            const bool sec = !lt && x != w.m && x < w.s;
-            w.s = lt ? w.m : (sec ? x : w.s);
-            w.si = lt ? w.i : (sec ? d : w.si);
-            w.m = lt ? x : w.m;
-            w.i = lt ? d : w.i;
-        }
-    }
-    w = wta_dpp<DPP_QP_1032>(w);
-    w = wta_dpp<DPP_QP_2301>(w);
-    if (LPP >= 8) w = wta_dpp<DPP_HALF_MIRROR>(w);
-    if (LPP >= 16) w = wta_dpp<DPP_MIRROR>(w);
-    if (LPP >= 32) w = wta_swz16(w);
-    static_assert(LPP <= 32, "a pixel spans at most 32 lanes");
-    int d = w.i;
-    if (w.s != SGM_INF && w.m / w.s > uniq && abs(w.i - w.si) > 1) d = Dn + 1;
-    float f;
-    if (d > Dn - 1) {
-        f = (float)(Dn + 1);
-    } else if (d == 0 || d == Dn - 1) {
-        f = (float)d;
-    } else {
-        const float av = row[d - 1], bv = row[d + 1], cv = row[d];
-        const float x = d + (av - bv) / (2 * (av + bv - 2 * cv));
-        const float lim = (Dn - 1) * 1.f;
-        f = (lim < x) ? lim : x;  // std::min(x, lim)
-    }
-    if (q == 0 && px < cnt) {
-        const long long pix = pix0 + px * pix_step;
-        // (moff = min_disp, wave-uniform: index space -> true disparity, one add
-        // on the stored values; 0 leaves them as they are)
-        disp[pix] = (uint16_t)(d + moff);
-        sub[pix] = f + (float)moff;
-        if (ratio) ratio[pix] = wta_ratio(w.m, w.s);
-    }
-}
 
 // Minimum over an LPP-lane group (LPP = 4..32 consecutive lanes), in every
 // lane of the group: quad, half-row and row mirrors, then the 16-apart
@@ -656,8 +526,9 @@ __device__ __forceinline__ int group_min_i(int x) {
     return x;
 }
 
-// The same WTA + uniqueness + sub-pixel for `cnt` <= PF pixels of a chunk,
-// with the disparities per lane (QQ) known at compile time: instead of a
+// WTA + uniqueness + sub-pixel (SGM.cpp:376-418, Solver.cpp:577-593) for
+// `cnt` <= PF pixels of a chunk at once: 64/PF lanes per pixel, each holding
+// QQ = D*PF/64 consecutive disparities (known at compile time).  Rather than a
 // running (min, index, second, index) state merged across lanes (about 15
 // VALU ops per disparity and per merge step), two group minima of the values
 // and two of the first indices holding them:
@@ -730,17 +601,6 @@ __device__ __forceinline__ void wta_chunk_q(const float (&x)[QQ], const float (*
         // the match confidence, in sub's layout (null, wave-uniform: not wanted)
         if (ratio) (ratio + sub_top)[sub_off] = wta_ratio(m, sec);
     }
-}
-
-template <int V, int PF>
-__device__ __forceinline__ void wta_consume_chunk(const float (*tb)[tbuf_stride<V>()],
-                                                  const long long *pb, int cnt, int lane,
-                                                  int Dn, float uniq, uint16_t *disp,
-                                                  float *sub, float *ratio = nullptr,
-                                                  int moff = 0) {
-    // pixels of a chunk are equally spaced along the scanline
-    const long long step = cnt > 1 ? pb[1] - pb[0] : 0;
-    wta_consume_chunk_at<V, PF>(tb, pb[0], step, cnt, lane, Dn, uniq, disp, sub, ratio, moff);
 }
 
 }  // namespace sgm

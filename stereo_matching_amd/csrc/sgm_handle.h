@@ -237,7 +237,6 @@ inline SweepArgs sweep_args(const sgm_handle *h) {
     SweepArgs a{};
     a.p1 = (float)h->p.p1;
     a.p2 = (float)h->p.p2;
-    a.uniq = h->p.uniqueness;
     return a;
 }
 

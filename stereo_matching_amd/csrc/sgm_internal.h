@@ -39,8 +39,7 @@ struct Geom {
 enum SweepMode {
     SWEEP_STORE_L = 0,  // write L_r and minL_r (parity tests)
     SWEEP_INIT = 1,     // acc_out = L_r
-    SWEEP_ACC = 2,      // acc_out = acc_in + L_r   (acc_in may alias acc_out)
-    SWEEP_FINAL = 3     // (retired: the final pass is the PAIR_V backward kernel)
+    SWEEP_ACC = 2       // acc_out = acc_in + L_r   (acc_in may alias acc_out)
 };
 
 // A band of a backward pass: chain steps [kb, ke) of every chain (the rows
@@ -59,13 +58,10 @@ struct Band {
 
 struct SweepArgs {
     const float *cost;   // HWD
-    const float *acc_in; // HWD (ACC: chain state; FINAL: T chain)
+    const float *acc_in; // HWD (ACC: chain state)
     float *acc_out;      // HWD (STORE_L: L_r)
-    const float *s_in;   // HWD (FINAL: S chain)
     float *min_out;      // HW  (STORE_L: minL_r)
-    uint16_t *disp;      // HW  (FINAL)
-    float *sub;          // HW  (FINAL)
-    float p1, p2, uniq;
+    float p1, p2;
     Band band;           // backward diagonal sweeps (DIR 6, 7: the L8 pass)
 };
 
@@ -82,6 +78,7 @@ enum PairMode {
     PAIR_INIT2 = 0,  // out = Lf + Lb                         (S12 = L1 + L2)
     PAIR_ACC = 1,    // out = (acc_in + Lf) + Lb              (T = (T5 + L6) + L7)
     PAIR_FINAL = 2   // total = ((s_in + Lf) + Lb) + acc_in   (S + T) -> WTA, sub-pixel
+                     // (PAIR_V only: the three-wave final kernels)
 };
 
 struct PairArgs {
@@ -116,9 +113,6 @@ hipError_t launch_vfwd2_l3(const float *const *in, float *const *out, float *con
 hipError_t launch_vfwd2(const float *const *in, float *const *out, const PairArgs *a, Geom g, hipStream_t st);
 // the PAIR_V/PAIR_FINAL pass of two views in one launch
 hipError_t launch_final2(const PairArgs &a0, const PairArgs &a1, Geom g, hipStream_t st);
-// cost_vertical_filter (Solver.cpp:333-368) fused with the L3 forward pass:
-// in = horizontally filtered volume, out = final cost volume, a.ckpt = L3
-// checkpoints.
 // Multi-role launches of the frame schedule (sgm_pair.hip); banded stage B
 // launches (d7.band) run no H rows (the banded schedule's H pair is its own
 // launch)
@@ -146,6 +140,9 @@ hipError_t launch_hpair4(const PairArgs *h1, const PairArgs *h2, int nviews, Geo
 hipError_t launch_h_fwd4(const PairArgs *h1, int nviews, Geom g, hipStream_t st);
 hipError_t launch_h_bwd4(const PairArgs *h2, int nviews, Geom g, hipStream_t st);
 hipError_t launch_final4(const PairArgs *a, int nviews, Geom g, hipStream_t st);
+// cost_vertical_filter (Solver.cpp:333-368) fused with the L3 forward pass:
+// in = horizontally filtered volume, out = final cost volume, a.ckpt = L3
+// checkpoints.
 hipError_t launch_vfwd(const float *in, float *out, const PairArgs &a, Geom g, hipStream_t st);
 // the same vertical IIR + L3, writing every row's L3 to the volume l3 (the
 // slanted schedule's bottom-up pass reads it) instead of checkpoints

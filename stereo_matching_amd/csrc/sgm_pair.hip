@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void pair_fwd_kernel(PairArgs a, Geom g) {
 
 template <int FAM, int V, bool FULL, int MODE>
 __global__ __launch_bounds__(64) void pair_bwd_kernel(PairArgs a, Geom g) {
-    pair_bwd_body<FAM, V, FULL, MODE>(a, g, bid_x(), nullptr, nullptr);
+    pair_bwd_body<FAM, V, FULL, MODE>(a, g, bid_x());
 }
 
 // The final pass of a view: PAIR_V backward (L4, recomputing L3) summed with
@@ -70,6 +70,9 @@ __global__ __launch_bounds__(64) void pair_bwd_kernel(PairArgs a, Geom g) {
 // D >= 64 run two WTA waves per column (each takes half of a chunk's pixels).
 template <int V, bool FULL>
 constexpr int final_nwta() { return FULL ? 2 : 1; }
+// threads of a final kernel's workgroup: recompute, backward and WTA waves
+template <int V, bool FULL>
+constexpr int final_block() { return 64 * (2 + final_nwta<V, FULL>()); }
 
 // BAND: one band of the banded backward phase (a.band).  NTC: C by
 // non-temporal loads (a.nt_cost: two-view frames, whose views' cost volumes
@@ -115,7 +118,7 @@ __global__ __launch_bounds__(256) void pair_final2_kernel(PairArgs a0, PairArgs 
 template <int V, bool FULL, int ROLES = 0>
 __global__ __launch_bounds__(64) void stage_a_kernel(PairArgs h1, SweepArgs l5, PairArgs d6,
                                                      Geom g) {
-    constexpr int PFH = V >= 4 ? 16 : 32, PFD = V >= 4 ? 8 : 16;
+    constexpr int PFH = pf_rows<V>(), PFD = pf_cols<V>();
     int b = bid_x();
     if constexpr (ROLES == 1) {
         if (b < g.W) sweep_body<4, V, SWEEP_INIT, FULL, PFD, true>(l5, g, b);
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(64) void hpair_kernel(PairArgs h1a, PairArgs h2a, P
 #ifdef SGM_HPF
     constexpr int PFH = V >= 4 ? SGM_HPF : 2 * SGM_HPF;
 #else
-    constexpr int PFH = V >= 4 ? 16 : 32;
+    constexpr int PFH = pf_rows<V>();
 #endif
     const bool vb = __builtin_amdgcn_workgroup_id_y() != 0;
     const PairArgs h1 = vb ? h1b : h1a;
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(64) void hpair_kernel(PairArgs h1a, PairArgs h2a, P
     // profiles/r06_experiments/r06x_hpair_nt.txt)
     pair_fwd_body<0, V, FULL, PFH, false, NTC>(h1, g, bid_x());
     __threadfence();  // this wave's checkpoint stores, before it reads them back
-    pair_bwd_body<PAIR_H, V, FULL, PAIR_INIT2, false, NTC>(h2, g, bid_x(), nullptr, nullptr);
+    pair_bwd_body<PAIR_H, V, FULL, PAIR_INIT2, false, NTC>(h2, g, bid_x());
 }
 
 // ---------------------------------------------------------- 4-path frames
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(64) void hpair_kernel(PairArgs h1a, PairArgs h2a, P
 // L1 forward with checkpoints, workgroup y = view ...
 template <int V, bool FULL>
 __global__ __launch_bounds__(64) void h_fwd2_kernel(PairArgs h1a, PairArgs h1b, Geom g) {
-    constexpr int PFH = V >= 4 ? 16 : 32;
+    constexpr int PFH = pf_rows<V>();
     const bool vb = __builtin_amdgcn_workgroup_id_y() != 0;
     pair_fwd_body<0, V, FULL, PFH>(vb ? h1b : h1a, g, bid_x());
 }
@@ -211,40 +214,36 @@ __global__ __launch_bounds__(256) void pair_final4_kernel(PairArgs a0, PairArgs 
 hipError_t launch_hpair4(const PairArgs *h1, const PairArgs *h2, int nviews, Geom g, hipStream_t st) {
     const dim3 grid(g.H, nviews);
     const PairArgs &b1 = h1[nviews - 1], &b2 = h2[nviews - 1];
-    if (g.D == 32) hpair_kernel<1, false, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
-    else if (g.D == 64) hpair_kernel<1, true, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
-    else if (g.D == 128) hpair_kernel<2, true, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
-    else hpair_kernel<4, true, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        hpair_kernel<V, FULL, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_h_fwd4(const PairArgs *h1, int nviews, Geom g, hipStream_t st) {
     const dim3 grid(g.H, nviews);
     const PairArgs &b = h1[nviews - 1];
-    if (g.D == 32) h_fwd2_kernel<1, false><<<grid, 64, 0, st>>>(h1[0], b, g);
-    else if (g.D == 64) h_fwd2_kernel<1, true><<<grid, 64, 0, st>>>(h1[0], b, g);
-    else if (g.D == 128) h_fwd2_kernel<2, true><<<grid, 64, 0, st>>>(h1[0], b, g);
-    else h_fwd2_kernel<4, true><<<grid, 64, 0, st>>>(h1[0], b, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        h_fwd2_kernel<V, FULL><<<grid, 64, 0, st>>>(h1[0], b, g);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_h_bwd4(const PairArgs *h2, int nviews, Geom g, hipStream_t st) {
     const dim3 grid(g.H, nviews);
     const PairArgs &b = h2[nviews - 1];
-    if (g.D == 32) h_bwd2_kernel<1, false><<<grid, 128, 0, st>>>(h2[0], b, g);
-    else if (g.D == 64) h_bwd2_kernel<1, true><<<grid, 128, 0, st>>>(h2[0], b, g);
-    else if (g.D == 128) h_bwd2_kernel<2, true><<<grid, 128, 0, st>>>(h2[0], b, g);
-    else h_bwd2_kernel<4, true><<<grid, 128, 0, st>>>(h2[0], b, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        h_bwd2_kernel<V, FULL><<<grid, 128, 0, st>>>(h2[0], b, g);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_final4(const PairArgs *a, int nviews, Geom g, hipStream_t st) {
     const dim3 grid(g.W, 1, nviews);
     const PairArgs &b = a[nviews - 1];
-    if (g.D == 32) pair_final4_kernel<1, false><<<grid, 64 * (2 + final_nwta<1, false>()), 0, st>>>(a[0], b, g);
-    else if (g.D == 64) pair_final4_kernel<1, true><<<grid, 64 * (2 + final_nwta<1, true>()), 0, st>>>(a[0], b, g);
-    else if (g.D == 128) pair_final4_kernel<2, true><<<grid, 64 * (2 + final_nwta<2, true>()), 0, st>>>(a[0], b, g);
-    else pair_final4_kernel<4, true><<<grid, 64 * (2 + final_nwta<4, true>()), 0, st>>>(a[0], b, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        pair_final4_kernel<V, FULL><<<grid, final_block<V, FULL>(), 0, st>>>(a[0], b, g);
+    });
     return hipGetLastError();
 }
 
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(128) void stage_b_kernel(PairArgs h2, PairArgs d7, 
         return;
     }
     const int path = 2 * (b - nh) + wave;
-    if (path < g.W) pair_bwd_body<PAIR_D2, V, FULL, PAIR_ACC, !HROWS>(d7, g, path, nullptr, nullptr);
+    if (path < g.W) pair_bwd_body<PAIR_D2, V, FULL, PAIR_ACC, !HROWS>(d7, g, path);
 }
 
 // Both views' stage A / stage B in one launch (workgroup y = view): frames
@@ -275,7 +274,7 @@ template <int V, bool FULL>
 __global__ __launch_bounds__(64) void stage_a2_kernel(PairArgs h1a, SweepArgs l5a, PairArgs d6a,
                                                       PairArgs h1b, SweepArgs l5b, PairArgs d6b,
                                                       Geom g) {
-    constexpr int PFH = V >= 4 ? 16 : 32, PFD = V >= 4 ? 8 : 16;
+    constexpr int PFH = pf_rows<V>(), PFD = pf_cols<V>();
     const bool vb = __builtin_amdgcn_workgroup_id_y() != 0;
     int b = bid_x();
     if (b < g.H) {
@@ -303,25 +302,23 @@ __global__ __launch_bounds__(128) void stage_b2_kernel(PairArgs h2a, PairArgs d7
         return;
     }
     const int path = 2 * (b - g.H) + wave;
-    if (path < g.W) pair_bwd_body<PAIR_D2, V, FULL, PAIR_ACC>(vb ? d7b : d7a, g, path, nullptr, nullptr);
+    if (path < g.W) pair_bwd_body<PAIR_D2, V, FULL, PAIR_ACC>(vb ? d7b : d7a, g, path);
 }
 
 hipError_t launch_stage_a2(const PairArgs *h1, const SweepArgs *l5, const PairArgs *d6, Geom g,
                            hipStream_t st) {
     const dim3 grid(g.H + 2 * g.W, 2);
-    if (g.D == 32) stage_a2_kernel<1, false><<<grid, 64, 0, st>>>(h1[0], l5[0], d6[0], h1[1], l5[1], d6[1], g);
-    else if (g.D == 64) stage_a2_kernel<1, true><<<grid, 64, 0, st>>>(h1[0], l5[0], d6[0], h1[1], l5[1], d6[1], g);
-    else if (g.D == 128) stage_a2_kernel<2, true><<<grid, 64, 0, st>>>(h1[0], l5[0], d6[0], h1[1], l5[1], d6[1], g);
-    else stage_a2_kernel<4, true><<<grid, 64, 0, st>>>(h1[0], l5[0], d6[0], h1[1], l5[1], d6[1], g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        stage_a2_kernel<V, FULL><<<grid, 64, 0, st>>>(h1[0], l5[0], d6[0], h1[1], l5[1], d6[1], g);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_stage_b2(const PairArgs *h2, const PairArgs *d7, Geom g, hipStream_t st) {
     const dim3 grid(g.H + (g.W + 1) / 2, 2);
-    if (g.D == 32) stage_b2_kernel<1, false><<<grid, 128, 0, st>>>(h2[0], d7[0], h2[1], d7[1], g);
-    else if (g.D == 64) stage_b2_kernel<1, true><<<grid, 128, 0, st>>>(h2[0], d7[0], h2[1], d7[1], g);
-    else if (g.D == 128) stage_b2_kernel<2, true><<<grid, 128, 0, st>>>(h2[0], d7[0], h2[1], d7[1], g);
-    else stage_b2_kernel<4, true><<<grid, 128, 0, st>>>(h2[0], d7[0], h2[1], d7[1], g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        stage_b2_kernel<V, FULL><<<grid, 128, 0, st>>>(h2[0], d7[0], h2[1], d7[1], g);
+    });
     return hipGetLastError();
 }
 
@@ -329,10 +326,9 @@ template <int ROLES = 0>
 static void launch_stage_a_t(const PairArgs &h1, const SweepArgs &l5, const PairArgs &d6, Geom g,
                              hipStream_t st, int nblk) {
     const dim3 grid(nblk);
-    if (g.D == 32) stage_a_kernel<1, false, ROLES><<<grid, 64, 0, st>>>(h1, l5, d6, g);
-    else if (g.D == 64) stage_a_kernel<1, true, ROLES><<<grid, 64, 0, st>>>(h1, l5, d6, g);
-    else if (g.D == 128) stage_a_kernel<2, true, ROLES><<<grid, 64, 0, st>>>(h1, l5, d6, g);
-    else stage_a_kernel<4, true, ROLES><<<grid, 64, 0, st>>>(h1, l5, d6, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        stage_a_kernel<V, FULL, ROLES><<<grid, 64, 0, st>>>(h1, l5, d6, g);
+    });
 }
 
 hipError_t launch_stage_a(const PairArgs &h1, const SweepArgs &l5, const PairArgs &d6, Geom g,
@@ -345,10 +341,9 @@ hipError_t launch_stage_a_hpair(const PairArgs *h1, const PairArgs *h2, int nvie
                                 hipStream_t st) {
     const dim3 grid(g.H, nviews);
     const PairArgs &b1 = h1[nviews - 1], &b2 = h2[nviews - 1];
-    if (g.D == 32) hpair_kernel<1, false><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
-    else if (g.D == 64) hpair_kernel<1, true><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
-    else if (g.D == 128) hpair_kernel<2, true><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
-    else hpair_kernel<4, true><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        hpair_kernel<V, FULL><<<grid, 64, 0, st>>>(h1[0], h2[0], b1, b2, g);
+    });
     return hipGetLastError();
 }
 
@@ -360,10 +355,9 @@ hipError_t launch_stage_a_band(const SweepArgs &l5, const PairArgs &d6, Geom g, 
 template <bool HROWS>
 static void launch_stage_b_t(const PairArgs &h2, const PairArgs &d7, Geom g, hipStream_t st) {
     const dim3 grid((HROWS ? g.H : 0) + (g.W + 1) / 2);
-    if (g.D == 32) stage_b_kernel<1, false, HROWS><<<grid, 128, 0, st>>>(h2, d7, g);
-    else if (g.D == 64) stage_b_kernel<1, true, HROWS><<<grid, 128, 0, st>>>(h2, d7, g);
-    else if (g.D == 128) stage_b_kernel<2, true, HROWS><<<grid, 128, 0, st>>>(h2, d7, g);
-    else stage_b_kernel<4, true, HROWS><<<grid, 128, 0, st>>>(h2, d7, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        stage_b_kernel<V, FULL, HROWS><<<grid, 128, 0, st>>>(h2, d7, g);
+    });
 }
 
 hipError_t launch_stage_b(const PairArgs &h2, const PairArgs &d7, Geom g, hipStream_t st) {
@@ -377,11 +371,10 @@ hipError_t launch_stage_b(const PairArgs &h2, const PairArgs &d7, Geom g, hipStr
 template <int FD>
 static void launch_fwd_t(const PairArgs &a, Geom g, hipStream_t st) {
     const dim3 grid(FD == 0 ? g.H : g.W);
-    constexpr int PF = FD == 0 ? 32 : 16;
-    if (g.D == 32) pair_fwd_kernel<FD, 1, false, PF><<<grid, 64, 0, st>>>(a, g);
-    else if (g.D == 64) pair_fwd_kernel<FD, 1, true, PF><<<grid, 64, 0, st>>>(a, g);
-    else if (g.D == 128) pair_fwd_kernel<FD, 2, true, PF><<<grid, 64, 0, st>>>(a, g);
-    else pair_fwd_kernel<FD, 4, true, PF / 2><<<grid, 64, 0, st>>>(a, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        constexpr int PF = FD == 0 ? pf_rows<V>() : pf_cols<V>();
+        pair_fwd_kernel<FD, V, FULL, PF><<<grid, 64, 0, st>>>(a, g);
+    });
 }
 
 hipError_t launch_pair_fwd(int family, const PairArgs &a, Geom g, hipStream_t st) {
@@ -396,10 +389,9 @@ hipError_t launch_pair_fwd(int family, const PairArgs &a, Geom g, hipStream_t st
 template <int WIN, bool BAND, bool L3OUT = false>
 static void launch_vfwd_t(const float *in, float *out, const PairArgs &a, Geom g, hipStream_t st) {
     const dim3 grid(g.W);
-    if (g.D == 32) vfwd_kernel<1, false, WIN, 16, BAND, L3OUT><<<grid, 64, 0, st>>>(in, out, a, g);
-    else if (g.D == 64) vfwd_kernel<1, true, WIN, 16, BAND, L3OUT><<<grid, 64, 0, st>>>(in, out, a, g);
-    else if (g.D == 128) vfwd_kernel<2, true, WIN, 16, BAND, L3OUT><<<grid, 64, 0, st>>>(in, out, a, g);
-    else vfwd_kernel<4, true, WIN, 8, BAND, L3OUT><<<grid, 64, 0, st>>>(in, out, a, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        vfwd_kernel<V, FULL, WIN, pf_cols<V>(), BAND, L3OUT><<<grid, 64, 0, st>>>(in, out, a, g);
+    });
 }
 
 hipError_t launch_vfwd(const float *in, float *out, const PairArgs &a, Geom g, hipStream_t st) {
@@ -418,19 +410,22 @@ hipError_t launch_vfwd_l3(const float *in, float *out, float *l3, const PairArgs
     return hipGetLastError();
 }
 
+// vfwd2's ring depth: the columns', but for the override of the slanted
+// schedule's (L3OUT) four-value kernel
+#ifndef VFWD2_PF4
+#define VFWD2_PF4 8
+#endif
+template <int V, bool L3OUT>
+constexpr int vfwd2_pf() { return V >= 4 && L3OUT ? VFWD2_PF4 : pf_cols<V>(); }
+
 template <int WIN, bool L3OUT>
 static void launch_vfwd2_t(const float *const *in, float *const *out, const PairArgs *b, Geom g,
                            hipStream_t st) {
     const dim3 grid(g.W, 2);
-#define VFWD2_ARGS in[0], out[0], b[0], in[1], out[1], b[1], g
-    if (g.D == 32) vfwd2_kernel<1, false, WIN, 16, L3OUT><<<grid, 64, 0, st>>>(VFWD2_ARGS);
-    else if (g.D == 64) vfwd2_kernel<1, true, WIN, 16, L3OUT><<<grid, 64, 0, st>>>(VFWD2_ARGS);
-    else if (g.D == 128) vfwd2_kernel<2, true, WIN, 16, L3OUT><<<grid, 64, 0, st>>>(VFWD2_ARGS);
-#ifndef VFWD2_PF4
-#define VFWD2_PF4 8
-#endif
-    else vfwd2_kernel<4, true, WIN, L3OUT ? VFWD2_PF4 : 8, L3OUT><<<grid, 64, 0, st>>>(VFWD2_ARGS);
-#undef VFWD2_ARGS
+    for_width(g.D, [&](auto V, auto FULL) {
+        vfwd2_kernel<V, FULL, WIN, vfwd2_pf<V, L3OUT>(), L3OUT><<<grid, 64, 0, st>>>(
+            in[0], out[0], b[0], in[1], out[1], b[1], g);
+    });
 }
 
 hipError_t launch_vfwd2_l3(const float *const *in, float *const *out, float *const *l3, const PairArgs *a,
@@ -452,19 +447,17 @@ hipError_t launch_vfwd2(const float *const *in, float *const *out, const PairArg
 template <int FAM, int MODE>
 static void launch_bwd_t(const PairArgs &a, Geom g, hipStream_t st) {
     const dim3 grid(FAM == PAIR_H ? g.H : g.W);
-    if (g.D == 32) pair_bwd_kernel<FAM, 1, false, MODE><<<grid, 64, 0, st>>>(a, g);
-    else if (g.D == 64) pair_bwd_kernel<FAM, 1, true, MODE><<<grid, 64, 0, st>>>(a, g);
-    else if (g.D == 128) pair_bwd_kernel<FAM, 2, true, MODE><<<grid, 64, 0, st>>>(a, g);
-    else pair_bwd_kernel<FAM, 4, true, MODE><<<grid, 64, 0, st>>>(a, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        pair_bwd_kernel<FAM, V, FULL, MODE><<<grid, 64, 0, st>>>(a, g);
+    });
 }
 
 template <bool BAND, bool NTC = false>
 static void launch_final_b(const PairArgs &a, Geom g, hipStream_t st) {
     const dim3 grid(g.W);
-    if (g.D == 32) pair_final_kernel<1, false, BAND, NTC><<<grid, 64 * (2 + final_nwta<1, false>()), 0, st>>>(a, g);
-    else if (g.D == 64) pair_final_kernel<1, true, BAND, NTC><<<grid, 64 * (2 + final_nwta<1, true>()), 0, st>>>(a, g);
-    else if (g.D == 128) pair_final_kernel<2, true, BAND, NTC><<<grid, 64 * (2 + final_nwta<2, true>()), 0, st>>>(a, g);
-    else pair_final_kernel<4, true, BAND, NTC><<<grid, 64 * (2 + final_nwta<4, true>()), 0, st>>>(a, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        pair_final_kernel<V, FULL, BAND, NTC><<<grid, final_block<V, FULL>(), 0, st>>>(a, g);
+    });
 }
 
 static void launch_final_t(const PairArgs &a, Geom g, hipStream_t st) {
@@ -475,10 +468,9 @@ static void launch_final_t(const PairArgs &a, Geom g, hipStream_t st) {
 
 hipError_t launch_final2(const PairArgs &a0, const PairArgs &a1, Geom g, hipStream_t st) {
     const dim3 grid(g.W, 1, 2);
-    if (g.D == 32) pair_final2_kernel<1, false><<<grid, 64 * (2 + final_nwta<1, false>()), 0, st>>>(a0, a1, g);
-    else if (g.D == 64) pair_final2_kernel<1, true><<<grid, 64 * (2 + final_nwta<1, true>()), 0, st>>>(a0, a1, g);
-    else if (g.D == 128) pair_final2_kernel<2, true><<<grid, 64 * (2 + final_nwta<2, true>()), 0, st>>>(a0, a1, g);
-    else pair_final2_kernel<4, true><<<grid, 64 * (2 + final_nwta<4, true>()), 0, st>>>(a0, a1, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        pair_final2_kernel<V, FULL><<<grid, final_block<V, FULL>(), 0, st>>>(a0, a1, g);
+    });
     return hipGetLastError();
 }
 

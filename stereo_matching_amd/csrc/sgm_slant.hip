@@ -733,6 +733,17 @@ size_t slant_gran_count(Geom g, int nviews) {
     return (size_t)nviews * slant_tiles(g, kSlantNW < kSlantNWUp ? kSlantNW : kSlantNWUp) * g.H * 3 * g.D;
 }
 
+// slant_kernel's CR argument by values per lane, and whether the launch
+// takes the debug build's dynamic LDS pad (SGM_SLANT_LDSPAD; never the
+// four-value kernel)
+#ifndef SLANT_CR4
+#define SLANT_CR4 1
+#endif
+template <int V>
+constexpr int slant_cr() { return V >= 4 ? SLANT_CR4 : (V == 2 ? 6 : 8); }
+template <int V>
+constexpr bool slant_takes_pad() { return V < 4; }
+
 template <bool UP>
 static hipError_t launch_slant_t(const SlantArgs &a0, Geom g, hipStream_t st) {
     SlantArgs a = a0;
@@ -762,7 +773,7 @@ static hipError_t launch_slant_t(const SlantArgs &a0, Geom g, hipStream_t st) {
     // (the hand-off loads of the receiver queue behind the compute waves'
     // stream loads in the CU's memory pipeline: deeper rings hide more
     // stream latency but lengthen every tile-to-tile hop)
-    constexpr int PF4 = UP ? SLANT_PF_UP4 : SLANT_PF_DN4, PF = UP ? 8 : 16;
+    constexpr int PF4 = UP ? SLANT_PF_UP4 : SLANT_PF_DN4, PF12 = UP ? 8 : 16;
     size_t pad = 0;
 #ifdef SGM_SLANT_DEBUG
     if (const char *e = getenv("SGM_SLANT_LDSPAD")) pad = (size_t)atoi(e) * 1024;
@@ -778,13 +789,10 @@ static hipError_t launch_slant_t(const SlantArgs &a0, Geom g, hipStream_t st) {
 #define SLANT_RING_DN 4
 #endif
     constexpr int R = UP ? SLANT_RING_UP : SLANT_RING_DN;
-    if (g.D == 32) slant_kernel<UP, 1, false, NW, PF, 8, R><<<grid, block, pad, st>>>(a, g);
-    else if (g.D == 64) slant_kernel<UP, 1, true, NW, PF, 8, R><<<grid, block, pad, st>>>(a, g);
-    else if (g.D == 128) slant_kernel<UP, 2, true, NW, PF, 6, R><<<grid, block, pad, st>>>(a, g);
-#ifndef SLANT_CR4
-#define SLANT_CR4 1
-#endif
-    else slant_kernel<UP, 4, true, NW, PF4, SLANT_CR4, R><<<grid, block, 0, st>>>(a, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        slant_kernel<UP, V, FULL, NW, V >= 4 ? PF4 : PF12, slant_cr<V>(), R>
+            <<<grid, block, slant_takes_pad<V>() ? pad : 0, st>>>(a, g);
+    });
     return hipGetLastError();
 }
 

@@ -36,11 +36,9 @@ __global__ __launch_bounds__(64) void sweep2_kernel(SweepArgs a0, SweepArgs a1, 
 
 hipError_t launch_sweep2_l8(const SweepArgs &a0, const SweepArgs &a1, Geom g, hipStream_t st) {
     const dim3 grid(g.W, 2);
-    constexpr int PF = 16;
-    if (g.D == 32) sweep2_kernel<7, 1, SWEEP_ACC, false, PF><<<grid, 64, 0, st>>>(a0, a1, g);
-    else if (g.D == 64) sweep2_kernel<7, 1, SWEEP_ACC, true, PF><<<grid, 64, 0, st>>>(a0, a1, g);
-    else if (g.D == 128) sweep2_kernel<7, 2, SWEEP_ACC, true, PF><<<grid, 64, 0, st>>>(a0, a1, g);
-    else sweep2_kernel<7, 4, SWEEP_ACC, true, PF / 2><<<grid, 64, 0, st>>>(a0, a1, g);
+    for_width(g.D, [&](auto V, auto FULL) {
+        sweep2_kernel<7, V, SWEEP_ACC, FULL, pf_cols<V>()><<<grid, 64, 0, st>>>(a0, a1, g);
+    });
     return hipGetLastError();
 }
 
@@ -64,47 +62,26 @@ static bool use_split_sweep(const Geom &g) {
 
 // Steps of loads kept in flight: horizontal paths (few, long, latency-bound)
 // need a deeper ring than the W column/diagonal paths.
-template <int DIR>
-constexpr int sweep_pf() { return DIR < 2 ? 32 : 16; }
+template <int DIR, int V>
+constexpr int sweep_pf() { return DIR < 2 ? pf_rows<V>() : pf_cols<V>(); }
 
 template <int DIR, int MODE>
 static void launch_sweep_v(const SweepArgs &a, Geom g, hipStream_t st) {
     const dim3 grid(DIR < 2 ? g.H : g.W);
-    if constexpr (DIR >= 4 && MODE != SWEEP_STORE_L) {
-        if (a.band.ke == 0 && use_split_sweep(g)) {  // (bands: the one-wave body, below)
-            if (g.D == 32)
-                sweep_split_kernel<DIR, 1, MODE, false><<<grid, 128, 0, st>>>(a, g);
-            else if (g.D == 64)
-                sweep_split_kernel<DIR, 1, MODE, true><<<grid, 128, 0, st>>>(a, g);
-            else if (g.D == 128)
-                sweep_split_kernel<DIR, 2, MODE, true><<<grid, 128, 0, st>>>(a, g);
-            else
-                sweep_split_kernel<DIR, 4, MODE, true><<<grid, 128, 0, st>>>(a, g);
-            return;
+    for_width(g.D, [&](auto V, auto FULL) {
+        constexpr int PF = sweep_pf<DIR, V>();
+        if constexpr (DIR >= 4 && MODE != SWEEP_STORE_L) {
+            if (a.band.ke == 0 && use_split_sweep(g)) {  // (bands: the one-wave body, below)
+                sweep_split_kernel<DIR, V, MODE, FULL><<<grid, 128, 0, st>>>(a, g);
+                return;
+            }
+            if (a.band.ke > 0) {  // one band (L7/L8: backward bands; L5/L6: forward bands)
+                sweep_kernel<DIR, V, MODE, FULL, PF, true><<<grid, 64, 0, st>>>(a, g);
+                return;
+            }
         }
-    }
-    constexpr int PF = sweep_pf<DIR>();
-    if constexpr (DIR >= 4 && MODE != SWEEP_STORE_L) {
-        if (a.band.ke > 0) {  // one band (L7/L8: backward bands; L5/L6: forward bands)
-            if (g.D == 32)
-                sweep_kernel<DIR, 1, MODE, false, PF, true><<<grid, 64, 0, st>>>(a, g);
-            else if (g.D == 64)
-                sweep_kernel<DIR, 1, MODE, true, PF, true><<<grid, 64, 0, st>>>(a, g);
-            else if (g.D == 128)
-                sweep_kernel<DIR, 2, MODE, true, PF, true><<<grid, 64, 0, st>>>(a, g);
-            else
-                sweep_kernel<DIR, 4, MODE, true, PF / 2, true><<<grid, 64, 0, st>>>(a, g);
-            return;
-        }
-    }
-    if (g.D == 32)
-        sweep_kernel<DIR, 1, MODE, false, PF><<<grid, 64, 0, st>>>(a, g);
-    else if (g.D == 64)
-        sweep_kernel<DIR, 1, MODE, true, PF><<<grid, 64, 0, st>>>(a, g);
-    else if (g.D == 128)
-        sweep_kernel<DIR, 2, MODE, true, PF><<<grid, 64, 0, st>>>(a, g);
-    else
-        sweep_kernel<DIR, 4, MODE, true, PF / 2><<<grid, 64, 0, st>>>(a, g);
+        sweep_kernel<DIR, V, MODE, FULL, PF><<<grid, 64, 0, st>>>(a, g);
+    });
 }
 
 template <int MODE>

@@ -349,11 +349,11 @@ hipError_t launch_vstrip(const VStripArgs &a, int nviews, Geom g, hipStream_t st
 #define VSTRIP_PD 4
 #endif
     constexpr int PD = VSTRIP_PD;  // rows of census / checkpoint loads in flight
-    if (g.D == 32) vstrip_kernel<1, false, 1, NV, 2, PD><<<grid, 64 * (1 + NV), 0, st>>>(a, g);
-    else if (g.D == 64) vstrip_kernel<1, true, 1, NV, 2, PD><<<grid, 64 * (1 + NV), 0, st>>>(a, g);
-    else if (g.D == 128) vstrip_kernel<2, true, 2, NV, 2, PD><<<grid, 64 * (2 + NV), 0, st>>>(a, g);
-    else if (g.D == 256) vstrip_kernel<4, true, 4, NV, 2, PD><<<grid, 64 * (4 + NV), 0, st>>>(a, g);
-    else return hipErrorInvalidValue;
+    if (g.D != 32 && g.D != 64 && g.D != 128 && g.D != 256) return hipErrorInvalidValue;
+    // NH = V horizontal waves beside the NV vertical ones
+    for_width(g.D, [&](auto V, auto FULL) {
+        vstrip_kernel<V, FULL, V, NV, 2, PD><<<grid, 64 * (V + NV), 0, st>>>(a, g);
+    });
     return hipGetLastError();
 }
 

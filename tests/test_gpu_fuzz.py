@@ -38,6 +38,11 @@ def _case(k: int):
 
 
 CASES = [_case(k) for k in range(N_CASES)]
+# No drawn case is a one-view frame at D = 32 (half a wave): the per-view
+# launches (stage A / B, the L8 sweep in both bodies, the final pass), the
+# one-view bands and the one-view slanted passes and strips at that width.
+CASES.append(dict(h=37, w=75, D=32, s=1, p1=10, p2=100, uniq=0.9, lr=1.0, kind="road", sky=False,
+                  blur=True, views=1, seed=N_CASES))
 
 
 @pytest.mark.parametrize("c", CASES, ids=[
