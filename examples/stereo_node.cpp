@@ -2,17 +2,22 @@
 // on libsgm_hip.so through the drop-in headers, without ROS or OpenCV:
 //
 //   images (8-bit PGM)            node.cpp:69-70   imread(..., IMREAD_GRAYSCALE)
+//   resize to img_w x img_h       node.cpp:75-78   cv::resize on the GPU (HipSolver::resize)
 //   sky masks, both views         node.cpp:80-87   SkyAreaDetector::detect
 //   SGM(h, w, s, d).process       node.cpp:49,93   (both views, LR check, post_filter)
 //   get_disp()                    node.cpp:104     -> OUT_disp.f32 (raw float32 rows)
 //   show_disp(debug_view)         node.cpp:107-110 -> OUT_debug.ppm (the node's imwrite)
 //   point cloud                   node.cpp:113-143 -> OUT_cloud.bin (N x 3 float64 + N u8)
 //
-// The node's resize to the configured size (node.cpp:75-76) is left out: the
-// configured size is the images' size.  The calibration (read_calib,
-// utils.cpp:59-89) comes from the command line.  Every stage runs on the GPU.
+// The configured size (node.cpp:19-20 g_img_w, g_img_h) is the images' size
+// unless img_w img_h are given: then the solver is built at that size and both
+// images are resized to it as node.cpp:75-76 does, on the GPU, before the sky
+// detector, the matcher and the point cloud see them.  The calibration
+// (read_calib, utils.cpp:59-89) comes from the command line.  Every stage runs
+// on the GPU.
 //
-// usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX [scale max_disp [fx fy cx cy [min_disp]]]
+// usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX
+//                    [scale max_disp [fx fy cx cy [min_disp [img_w img_h]]]]
 // min_disp (not in the node): search disparities [min_disp, min_disp + max_disp);
 // the map, the debug view and the cloud are then in true disparity.
 #include "sgm_amd/SGM.h"
@@ -58,9 +63,10 @@ static bool write_ppm(const std::string &path, const Mat &bgr) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 4 && argc != 6 && argc != 10 && argc != 11) {
+    if (argc != 4 && argc != 6 && argc != 10 && argc != 11 && argc != 13) {
         std::fprintf(stderr,
-                     "usage: %s LEFT.pgm RIGHT.pgm OUT_PREFIX [scale max_disp [fx fy cx cy [min_disp]]]\n",
+                     "usage: %s LEFT.pgm RIGHT.pgm OUT_PREFIX "
+                     "[scale max_disp [fx fy cx cy [min_disp [img_w img_h]]]]\n",
                      argv[0]);
         return 2;
     }
@@ -82,12 +88,23 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "cannot read two 8-bit PGM images of one size\n");
         return 2;
     }
-    const int h = img_l.rows, w = img_l.cols;
-    std::printf("left size: %d, %d\nright size: %d, %d\n", h, w, img_r.rows, img_r.cols);
+    // node.cpp:19-20 g_img_w, g_img_h (default: the images' size, nothing to resize)
+    const int w = argc > 12 ? std::atoi(argv[11]) : img_l.cols;
+    const int h = argc > 12 ? std::atoi(argv[12]) : img_l.rows;
+    std::printf("left size: %d, %d\nright size: %d, %d\n", img_l.rows, img_l.cols, img_r.rows,
+                img_r.cols);
 
     // node.cpp:49-51
     sgm_amd::SolverPtr sv = std::make_shared<sgm_amd::SGM>(h, w, scale, max_disp, 8, min_disp);
     SkyDetPtr sky_det = std::make_shared<sky_detector::SkyAreaDetector>();
+
+    if (argc > 12) {  // node.cpp:75-78, on the GPU
+        sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
+        sgm->resize(img_l, img_l);
+        sgm->resize(img_r, img_r);
+        std::printf("resized left size: %d, %d\n", img_l.rows, img_l.cols);
+        std::printf("resized right size: %d, %d\n", img_r.rows, img_r.cols);
+    }
 
     Mat sky_mask, sky_mask_beta;  // node.cpp:80-87 (no debug image is written)
     sky_det->detect(img_l, out + "_sky.png", sky_mask, scale);

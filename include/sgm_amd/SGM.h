@@ -19,6 +19,9 @@
  *   BM(h, w, s, d)               BM.cpp:4-97        (filtered-cost WTA, post-filtered)
  *   get_disp()                   Solver.h:36        (CV_32FC1, invalid = d+1)
  *   set_post_filter_launches(n)  (not in the reference) post_filter without host waits
+ *   resize(src, dst)             node.cpp:75-76     cv::resize(src, dst, Size(w, h)) on the GPU
+ *   set_input_size(rows, cols)   (not in the reference) process() takes rows x cols images
+ *                                and resizes them on the GPU first
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -235,6 +238,10 @@ public:
             fail("process", "inputs must be CV_8UC1 of the constructed size (SGM.cpp:34-38)");
         this->img_l = img_l;  // shallow, as SGM.cpp:59-60 (decimated on the device)
         this->img_r = img_r;
+        if (resizing_) {  // checked before any work: the resized images' host copies
+            resized_[0] = Mat(full_h_, full_w_, CV_8UC1);
+            resized_[1] = Mat(full_h_, full_w_, CV_8UC1);
+        }
         // Each mask applies on its own, as in the reference: sky_mask to the
         // left DSI (Solver.cpp:146-178), sky_mask_beta to the right one
         // (Solver.cpp:200-232); BM reads sky_mask only (BM.cpp:33-34).
@@ -258,8 +265,44 @@ public:
         if (confidence_on_ &&
             sgm_stage_confidence(handle_, SGM_VIEW_LEFT, confidence_.template ptr<float>(0)) != SGM_OK)
             fail("process", sgm_last_error(handle_));
+        if (resizing_) {
+            // what the frame matched: the node's resized img_l / img_r (node.cpp:75-76),
+            // for show_disp and the point cloud (node.cpp:107,138)
+            for (int v = 0; v < 2; ++v)
+                if (sgm_stage_resized(handle_, v, resized_[v].data) != SGM_OK)
+                    fail("process", sgm_last_error(handle_));
+            this->img_l = resized_[0];
+            this->img_r = resized_[1];
+        }
         if (scale > 1) decimate_left();
     }
+
+    // cv::resize(src, dst, Size(w, h)) (node.cpp:75-76: 8-bit, one channel,
+    // INTER_LINEAR in its pinned fixed-point form, sgm_stage_resize) on the
+    // GPU, to the constructed size; dst may be src, as in the node.
+    void resize(const Mat &src, Mat &dst) {
+        if (src.empty() || src.type() != CV_8UC1) fail("resize", "src must be a CV_8UC1 image");
+        Mat out(full_h_, full_w_, CV_8UC1);
+        if (sgm_stage_resize(handle_, src.data, src.rows, src.cols, (int)src.step, out.data) != SGM_OK)
+            fail("resize", sgm_last_error(handle_));
+        dst = out;
+    }
+
+    // The size of the images process() takes (sgm_set_input_size): every
+    // frame then starts by resizing both to the constructed size on the GPU,
+    // and images of any other size fail as a wrong-size image does.  (0, 0):
+    // off, the constructed size again.
+    void set_input_size(int rows, int cols) {
+        if (sgm_set_input_size(handle_, rows, cols) != SGM_OK)
+            fail("set_input_size", sgm_last_error(handle_));
+        resizing_ = rows != 0;
+        in_h_ = resizing_ ? rows : full_h_;
+        in_w_ = resizing_ ? cols : full_w_;
+        if (!resizing_) resized_[0] = resized_[1] = Mat();
+    }
+    // CV_8UC1 at the constructed size: the last process()'s resized image of
+    // `view` (0 left, 1 right); empty while no input size is set
+    const Mat &get_resized(int view) const { return resized_[view == 1 ? 1 : 0]; }
 
     sgm_handle *handle() const { return handle_; }
 
@@ -296,7 +339,7 @@ protected:
     // paths = 4: the reference built with USE_8_PATH = false (inc/SGM.h:7)
     // min_disp: the search range starts there (sgm_set_min_disp; BM: 0 only)
     HipSolver(int h, int w, int s, int d, int solver, int views = 2, int paths = 8, int min_disp = 0)
-        : Solver(h, w, s, d, min_disp), bm_(solver == SGM_SOLVER_BM) {
+        : Solver(h, w, s, d, min_disp), bm_(solver == SGM_SOLVER_BM), full_h_(h), full_w_(w) {
         if (paths != 4 && paths != 8) fail("Solver", "paths must be 4 or 8 (USE_8_PATH, inc/SGM.h:7)");
         if (bm_ && min_disp != 0) fail("Solver", "BM takes no min_disp");
         sgm_params p;
@@ -317,6 +360,9 @@ private:
     bool bm_;
     bool confidence_on_ = false;
     Mat confidence_;
+    int full_h_, full_w_;    // the constructed size (in_h_, in_w_: what process() takes)
+    bool resizing_ = false;  // set_input_size
+    Mat resized_[2];
 
     void check_mask(const Mat &m, const char *what) const {
         if (m.type() != CV_8UC1 || m.rows != img_h || m.cols != img_w)

@@ -184,6 +184,57 @@ int sgm_set_min_disp(sgm_handle *h, int m);
 /* The value that marks an invalid pixel in every float map of this handle:
  * max_disp + min_disp + 1 (D + 1 by default, Solver.cpp:21). */
 int sgm_get_invalid_disp(const sgm_handle *h, int *invalid);
+
+/* ---- input resize: the node's cv::resize(img, img, Size(w, h)) (node.cpp:75-76) ----
+ *
+ * cv::resize of an 8-bit one-channel image with the default INTER_LINEAR, in
+ * OpenCV's fixed-point form, pinned as DESIGN.md 5j states it (an exact half
+ * size is the 2x2 mean (a + b + c + d + 2) >> 2; otherwise 11-bit weights per
+ * axis from fx = (float)((dx + 0.5) * scale_x - 0.5), clamped at the borders)
+ * and bit-exact against tests/resize_recipe.py.  Parity with a particular
+ * OpenCV build is not pinned at this boundary, as for the pre-blur.
+ *
+ * sgm_resize_device: src (src_rows x src_cols u8, src_pitch bytes) -> dst at the
+ * handle's full size (height x width, dst_pitch bytes; padding untouched).  One
+ * launch on `stream` (NULL = the handle's stream), no host wait, no allocation:
+ * capturable into a HIP graph.  Any handle serves, aux_only included; the source
+ * may be any size from 1 x 1.  SGM_ERR_INVALID_ARG, with a message, for a NULL
+ * pointer, a size below 1, src_pitch < src_cols or dst_pitch < width. */
+int sgm_resize_device(sgm_handle *h, const uint8_t *d_src, int src_rows, int src_cols,
+                      int src_pitch, uint8_t *d_dst, int dst_pitch, void *stream);
+/* The same with HOST buffers (dst dense, height x width); synchronous. */
+int sgm_stage_resize(sgm_handle *h, const uint8_t *src, int src_rows, int src_cols,
+                     int src_pitch, uint8_t *dst);
+
+/* The size of the images a frame takes: a property of the handle, like
+ * sgm_set_min_disp (sgm_params and SGM_HIP_VERSION are unchanged).  (0, 0) = off
+ * (default): frames run exactly as before.  With a size set, sgm_process and
+ * sgm_process_device take src_rows x src_cols images (pitch >= src_cols); the
+ * frame's first launch resizes both into handle-owned height x width images
+ * (every frame handle's census reads both images, one-view and BM handles
+ * included), and everything inside the frame reads those: the census, the
+ * in-frame sky detector (params.sky_detect), the in-frame LKRefine, the BM
+ * solver.  Sky masks passed in stay on the working grid.  The stand-alone
+ * stage calls (sgm_lk_refine_device, sgm_sky_detect_device, sgm_stage_census,
+ * ...) keep taking full-size images.
+ * Allocates (or, at (0, 0), frees) the two resized images and the host API's
+ * staging of the raw ones, counted in sgm_device_bytes.  Synchronises the
+ * handle's last work first; call it outside stream capture, and re-capture
+ * graphs afterwards.  SGM_ERR_INVALID_ARG, with a message, for a negative size,
+ * exactly one of the two zero, and a non-zero size on an aux_only handle (it
+ * runs no frames). */
+int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols);
+int sgm_get_input_size(const sgm_handle *h, int *src_rows, int *src_cols);
+/* The last frame's resized image of `view` (SGM_VIEW_LEFT / SGM_VIEW_RIGHT):
+ * handle-owned DEVICE memory, height x width u8, *pitch bytes per row; valid
+ * until the next frame, sgm_set_input_size or sgm_destroy.  What the node hands
+ * to the point cloud (node.cpp:138 reads the resized img_l).  Reads of it are
+ * ordered after the frame on the frame's stream only.  SGM_ERR_INVALID_ARG with
+ * no input size set, before any frame, for any other view, or a NULL pointer. */
+int sgm_get_resized(sgm_handle *h, int view, const uint8_t **d_img, int *pitch);
+/* The same image copied to a HOST buffer (height x width, dense); synchronous. */
+int sgm_stage_resized(sgm_handle *h, int view, uint8_t *img);
+
 /* Bytes of device memory the handle holds. */
 size_t sgm_device_bytes(const sgm_handle *h);
 /* The handle's own stream (a hipStream_t; what a NULL stream argument

@@ -40,6 +40,8 @@ EXPORTS = (
     "sgm_set_confidence", "sgm_confidence_device", "sgm_stage_confidence",
     "sgm_confidence_filter_device", "sgm_stage_confidence_filter",
     "sgm_set_min_disp", "sgm_get_invalid_disp",
+    "sgm_resize_device", "sgm_stage_resize", "sgm_set_input_size", "sgm_get_input_size",
+    "sgm_get_resized", "sgm_stage_resized",
 )
 SGM_COMM_ID_BYTES = 128
 
@@ -153,6 +155,12 @@ def lib():
     L.sgm_get_size.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)]
     L.sgm_set_min_disp.argtypes = [P, I]
     L.sgm_get_invalid_disp.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_resize_device.argtypes = [P, P, I, I, I, P, I, P]
+    L.sgm_stage_resize.argtypes = [P, P, I, I, I, P]
+    L.sgm_set_input_size.argtypes = [P, I, I]
+    L.sgm_get_input_size.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
+    L.sgm_get_resized.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
+    L.sgm_stage_resized.argtypes = [P, I, P]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

@@ -110,8 +110,12 @@ void free_all(sgm_handle *h) {
 // memory on the CPU, so every host<->device transfer is one contiguous DMA
 // (pageable 2-D copies went through the runtime's staging path at a fraction
 // of PCIe bandwidth).  Layout: left | right | sky_l | sky_r | out f32 | raw u16.
+// rows x cols of the images a frame takes: the input size when one is set
+inline int frame_rows(const sgm_handle *h) { return h->in_rows ? h->in_rows : h->p.height; }
+inline int frame_cols(const sgm_handle *h) { return h->in_rows ? h->in_cols : h->p.width; }
+
 int ensure_pinned(sgm_handle *h) {
-    const size_t nin = (size_t)h->p.height * h->p.width, npx = (size_t)h->g.H * h->g.W;
+    const size_t nin = (size_t)frame_rows(h) * frame_cols(h), npx = (size_t)h->g.H * h->g.W;
     const size_t need = 2 * nin + 2 * npx + npx * sizeof(float) + npx * sizeof(uint16_t) + 64;
     if (h->h_pin && h->h_pin_bytes >= need) return SGM_OK;
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -498,6 +502,130 @@ int sgm_set_min_disp(sgm_handle *h, int m) {
     return SGM_OK;
 }
 
+// ---- input resize (node.cpp:75-76; sgm_resize.hip)
+
+int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!input_size_ok(src_rows, src_cols, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_size: %s", why);
+    if (h->p.aux_only && src_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_input_size: an aux_only handle runs no frames (sgm_resize_device "
+                       "takes its sizes per call)");
+    DeviceGuard guard(h->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_size: call it outside stream capture");
+    if (src_rows == h->in_rows && src_cols == h->in_cols) return SGM_OK;
+    // frames in flight still read the staged and the resized images
+    if (int rc = wait_last(h)) return rc;
+    const size_t nfull = (size_t)h->p.height * h->p.width;
+    const size_t nold = (size_t)h->in_rows * h->in_cols, nnew = (size_t)src_rows * src_cols;
+    for (int v = 0; v < 2; ++v) {
+        dfree(h, &h->d_raw[v], nold);
+        if (!src_rows) dfree(h, &h->d_rs[v], nfull);
+    }
+    h->in_rows = h->in_cols = 0;
+    h->rs_valid = false;
+    if (!src_rows) return SGM_OK;
+    int rc = SGM_OK;
+    for (int v = 0; v < 2 && !rc; ++v) {
+        if (!h->d_rs[v]) rc = dalloc(h, &h->d_rs[v], nfull);
+        if (!rc) rc = dalloc(h, &h->d_raw[v], nnew);
+    }
+    if (rc) {  // (off again: the handle runs as before)
+        for (int v = 0; v < 2; ++v) {
+            dfree(h, &h->d_raw[v], nnew);
+            dfree(h, &h->d_rs[v], nfull);
+        }
+        return rc;
+    }
+    h->in_rows = src_rows;
+    h->in_cols = src_cols;
+    return SGM_OK;
+}
+
+int sgm_get_input_size(const sgm_handle *h, int *src_rows, int *src_cols) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (src_rows) *src_rows = h->in_rows;
+    if (src_cols) *src_cols = h->in_cols;
+    return SGM_OK;
+}
+
+int sgm_get_resized(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!d_img || !pitch) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: NULL pointer");
+    if (!h->in_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: no input size is set (sgm_set_input_size)");
+    // (every frame handle's census reads both images, so both are resized)
+    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: the handle reads no image of view %d", view);
+    if (!h->rs_valid)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: no frame has run since the input size was set");
+    *d_img = h->d_rs[view];
+    *pitch = h->p.width;
+    return SGM_OK;
+}
+
+int sgm_stage_resized(sgm_handle *h, int view, uint8_t *img) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!img) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resized: NULL pointer");
+    const uint8_t *d_img = nullptr;
+    int pitch = 0;
+    if (int rc = sgm_get_resized(h, view, &d_img, &pitch)) return rc;
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return SGM_OK;
+}
+
+int sgm_resize_device(sgm_handle *h, const uint8_t *d_src, int src_rows, int src_cols, int src_pitch,
+                      uint8_t *d_dst, int dst_pitch, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!d_src || !d_dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_resize_device: NULL pointer");
+    if (!resize_src_ok(src_rows, src_cols, src_pitch, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_resize_device: %s", why);
+    if (dst_pitch < h->p.width)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_resize_device: dst_pitch %d below the width %d",
+                       dst_pitch, h->p.width);
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "resize", (double)h->p.height * h->p.width, st, [&] {
+               return sgm::launch_resize(&d_src, src_rows, src_cols, src_pitch, &d_dst, h->p.height,
+                                         h->p.width, dst_pitch, 1, st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_stage_resize(sgm_handle *h, const uint8_t *src, int src_rows, int src_cols, int src_pitch,
+                     uint8_t *dst) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resize: NULL pointer");
+    if (!resize_src_ok(src_rows, src_cols, src_pitch, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resize: %s", why);
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    const size_t nsrc = (size_t)src_rows * src_cols, nfull = (size_t)h->p.height * h->p.width;
+    int rc;
+    {
+        // staging: the source in a stream-ordered temporary, the result in d_in[0]
+        StreamTemp<uint8_t> d_src(h->st);
+        HIPCHK(h, hipMallocAsync((void **)&d_src.p, nsrc, h->st));
+        HIPCHK(h, hipMemcpy2DAsync(d_src.p, (size_t)src_cols, src, (size_t)src_pitch, (size_t)src_cols,
+                                   (size_t)src_rows, hipMemcpyHostToDevice, h->st));
+        rc = sgm_resize_device(h, d_src.p, src_rows, src_cols, src_cols, h->d_in[0], h->p.width, h->st);
+        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, h->d_in[0], nfull, hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return rc;
+}
+
 int sgm_set_confidence(sgm_handle *h, int enable) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
@@ -611,7 +739,7 @@ int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_ri
                        float *d_out, int out_pitch, uint16_t *d_raw_disp, void *stream) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (int rc = check_frame_err(h)) return rc;
-    if (!d_left || !d_right || !d_out || pitch < h->p.width || out_pitch < h->g.W ||
+    if (!d_left || !d_right || !d_out || pitch < frame_cols(h) || out_pitch < h->g.W ||
         ((d_sky_l || d_sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: bad pointer or pitch");
     if (h->p.aux_only)
@@ -626,7 +754,7 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
                 const uint8_t *sky_l, const uint8_t *sky_r, int sky_pitch, float *out,
                 int out_pitch, uint16_t *raw_disp) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (!left || !right || !out || pitch < h->p.width || out_pitch < h->g.W ||
+    if (!left || !right || !out || pitch < frame_cols(h) || out_pitch < h->g.W ||
         ((sky_l || sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: bad pointer or pitch");
     if (h->p.aux_only)
@@ -636,14 +764,17 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
     if ((rc = ensure_pinned(h))) return rc;
-    const size_t nin = (size_t)h->p.height * h->p.width, npx = (size_t)h->g.H * h->g.W;
+    // (with an input size set the raw images are staged and the frame resizes them)
+    const int in_h = frame_rows(h), in_w = frame_cols(h);
+    uint8_t *const *d_in = h->in_rows ? h->d_raw : h->d_in;
+    const size_t nin = (size_t)in_h * in_w, npx = (size_t)h->g.H * h->g.W;
     uint8_t *pl = h->h_pin, *pr = pl + nin, *psl = pr + nin, *psr = psl + npx;
     float *pout = reinterpret_cast<float *>(psr + npx + (16 - (size_t)(psr + npx) % 16) % 16);
     uint16_t *praw = reinterpret_cast<uint16_t *>(pout + npx);
-    pack_rows(pl, left, h->p.width, h->p.height, pitch);
-    pack_rows(pr, right, h->p.width, h->p.height, pitch);
-    HIPCHK(h, hipMemcpyAsync(h->d_in[0], pl, nin, hipMemcpyHostToDevice, h->st));
-    HIPCHK(h, hipMemcpyAsync(h->d_in[1], pr, nin, hipMemcpyHostToDevice, h->st));
+    pack_rows(pl, left, in_w, in_h, pitch);
+    pack_rows(pr, right, in_w, in_h, pitch);
+    HIPCHK(h, hipMemcpyAsync(d_in[0], pl, nin, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipMemcpyAsync(d_in[1], pr, nin, hipMemcpyHostToDevice, h->st));
     if (sky_l) {
         pack_rows(psl, sky_l, h->g.W, h->g.H, sky_pitch);
         HIPCHK(h, hipMemcpyAsync(h->d_sky[0], psl, npx, hipMemcpyHostToDevice, h->st));
@@ -652,7 +783,7 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
         pack_rows(psr, sky_r, h->g.W, h->g.H, sky_pitch);
         HIPCHK(h, hipMemcpyAsync(h->d_sky[1], psr, npx, hipMemcpyHostToDevice, h->st));
     }
-    const FrameIO f = {h->d_in[0], h->d_in[1], h->p.width, sky_l ? h->d_sky[0] : nullptr,
+    const FrameIO f = {d_in[0], d_in[1], in_w, sky_l ? h->d_sky[0] : nullptr,
                        sky_r ? h->d_sky[1] : nullptr, h->g.W, h->d_out, h->g.W,
                        raw_disp ? h->d_disp[0] : nullptr};
     if ((rc = run_frame(h, f, h->st))) return rc;

@@ -561,6 +561,20 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
     const int nv = h->nviews;
     const double elems = vol_elems(g);
     int rc;
+    // node.cpp:75-76: with an input size set the frame's first launch resizes
+    // both images to the full size (every handle's census reads both), and the
+    // sky detector, the census, LKRefine and BM read those
+    if (h->in_rows) {
+        const uint8_t *src[2] = {f.left, f.right};
+        HIPCHK(h, timed(h, "resize", 2.0 * h->p.height * h->p.width, st, [&] {
+                   return sgm::launch_resize(src, h->in_rows, h->in_cols, f.pitch, h->d_rs, h->p.height,
+                                             h->p.width, h->p.width, 2, st);
+               }));
+        f.left = h->d_rs[0];
+        f.right = h->d_rs[1];
+        f.pitch = h->p.width;
+        h->rs_valid = true;
+    }
     // Everything runs on one stream.  Two-view frames keep each view's cost
     // volume resident in the 256 MB Infinity Cache through its readers by
     // running the views' aggregation back to back (K128: 238.5 MB per view;

@@ -44,6 +44,10 @@ struct sgm_handle {
     hipStream_t last_st;  // the stream of the last entry point's work (null: none yet)
     bool last_recorded;   // ev_last was recorded at the end of that call (a caller's stream)
     uint8_t *d_in[2];     // full-size input staging (host API)
+    int in_rows, in_cols; // sgm_set_input_size: frames take in_rows x in_cols images (0, 0: off)
+    uint8_t *d_rs[2];     //   and resize them into these full-size images first (left, right)
+    uint8_t *d_raw[2];    //   staging of the raw images (host API)
+    bool rs_valid;        //   a frame has filled d_rs since the size was set (sgm_get_resized)
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
@@ -270,7 +274,7 @@ inline float *t_buf(sgm_handle *h, int v) { return h->d_ch[v]; }
 
 // One frame's device buffers, as sgm_process_device takes them.
 struct FrameIO {
-    const uint8_t *left, *right;  // full-size images
+    const uint8_t *left, *right;  // full-size images (input-size images with an input size set)
     int pitch;
     const uint8_t *sky_l, *sky_r;  // working-grid sky masks (null: none)
     int sky_pitch;

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sgm_resize_args.h"
+
 namespace sgm {
 
 // Floats of slack after the final cost volume: row-walking prefetch rings may
@@ -288,6 +290,12 @@ hipError_t launch_lk_refine(const uint8_t *left, const uint8_t *right, int pitch
 size_t sky_scratch_bytes(Geom g);
 hipError_t launch_sky_detect(const uint8_t *const *img, int pitch, uint8_t *const *mask,
                              int mask_pitch, void *scratch, int nviews, Geom g, hipStream_t st);
+// The node's cv::resize (node.cpp:75-76; sgm_resize.hip) of nviews
+// (1 or 2) u8 images of one size in one launch: src[v] src_rows x src_cols
+// (src_pitch bytes) -> dst[v] dst_rows x dst_cols (dst_pitch bytes, padding untouched).
+hipError_t launch_resize(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
+                         uint8_t *const *dst, int dst_rows, int dst_cols, int dst_pitch, int nviews,
+                         hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

@@ -54,7 +54,7 @@ class SGM:
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
-                 _solver: int = _capi.SGM_SOLVER_SGM):
+                 input_size=None, _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
         # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
@@ -110,11 +110,17 @@ class SGM:
         # (set_post_filter_launches); 0 = the adaptive, host-synchronised fill
         # confidence: every frame also keeps its per-pixel uniqueness ratio
         # (set_confidence / get_confidence)
+        # input_size = (h0, w0): process() takes h0 x w0 images and the frame
+        # resizes them to h x w first, as the node does (node.cpp:75-76;
+        # set_input_size)
+        self.in_h, self.in_w = h, w
         try:
             if post_filter_launches:
                 self.set_post_filter_launches(post_filter_launches)
             if confidence:
                 self.set_confidence(True)
+            if input_size is not None:
+                self.set_input_size(*input_size)
         except Exception:
             self.close()
             raise
@@ -151,8 +157,8 @@ class SGM:
     # ------------------------------------------------------------ process
     def process(self, img_l, img_r, sky_mask=None, sky_mask_beta=None) -> None:
         """SGM::process (src/SGM.cpp:32-826, sky overload :829-834)."""
-        l = _u8(img_l, (self.h, self.w), "img_l")
-        r = _u8(img_r, (self.h, self.w), "img_r")
+        l = _u8(img_l, (self.in_h, self.in_w), "img_l")
+        r = _u8(img_r, (self.in_h, self.in_w), "img_r")
         sl = None if sky_mask is None or np.size(sky_mask) == 0 else \
             _u8(sky_mask, (self.rows, self.cols), "sky_mask")
         sr = None if sky_mask_beta is None or np.size(sky_mask_beta) == 0 else \
@@ -164,7 +170,7 @@ class SGM:
         # would alias the previous frame's result).
         out = np.empty((self.rows, self.cols), np.float32)
         raw = np.empty((self.rows, self.cols), np.uint16)
-        check(self._lib.sgm_process(self._h, _ptr(l), _ptr(r), self.w, _ptr(sl), _ptr(sr),
+        check(self._lib.sgm_process(self._h, _ptr(l), _ptr(r), self.in_w, _ptr(sl), _ptr(sr),
                                     self.cols, _ptr(out), self.cols, _ptr(raw)),
               self._h)
         self._raw = raw
@@ -180,10 +186,55 @@ class SGM:
         (None: the handle's own stream; a torch stream's `cuda_stream`,
         including 0 for torch's default stream: that stream)."""
         check(self._lib.sgm_process_device(
-            self._h, ctypes.c_void_p(d_left), ctypes.c_void_p(d_right), pitch or self.w,
+            self._h, ctypes.c_void_p(d_left), ctypes.c_void_p(d_right), pitch or self.in_w,
             ctypes.c_void_p(d_sky_l or None), ctypes.c_void_p(d_sky_r or None),
             sky_pitch or self.cols, ctypes.c_void_p(d_out), out_pitch or self.cols,
             ctypes.c_void_p(d_raw or None), _stream(stream)), self._h)
+
+    # ------------------------------------------------------- input resize
+    def set_input_size(self, rows: int, cols: int) -> None:
+        """sgm_set_input_size: process() / process_device() take rows x cols
+        images, and the frame's first launch resizes them to h x w (the node's
+        cv::resize, node.cpp:75-76, in its pinned fixed-point form); (0, 0)
+        switches it off.  Not inside stream capture; re-capture graphs."""
+        check(self._lib.sgm_set_input_size(self._h, int(rows), int(cols)), self._h)
+        self.in_h, self.in_w = (int(rows), int(cols)) if rows else (self.h, self.w)
+
+    @property
+    def input_size(self):
+        """(rows, cols) of the images process() takes; (0, 0): the full size."""
+        r, c = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.sgm_get_input_size(self._h, ctypes.byref(r), ctypes.byref(c)), self._h)
+        return r.value, c.value
+
+    def resize(self, img, pitch: int | None = None) -> np.ndarray:
+        """cv::resize(img, Size(w, h)) of a 2-D u8 image of any size on the GPU
+        (sgm_stage_resize): h x w uint8.  pitch: bytes per row of `img` when it
+        is a padded buffer (its last axis is then the pitch)."""
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError(f"img: expected a 2-D image, got shape {a.shape}")
+        out = np.empty((self.h, self.w), np.uint8)
+        check(self._lib.sgm_stage_resize(self._h, _ptr(a), a.shape[0], a.shape[1],
+                                         pitch or a.shape[1], _ptr(out)), self._h)
+        return out
+
+    def resize_device(self, d_src: int, src_rows: int, src_cols: int, d_dst: int, *,
+                      src_pitch: int | None = None, dst_pitch: int | None = None,
+                      stream: int | None = None) -> None:
+        """The same on device buffers (sgm_resize_device: one launch, enqueue
+        only, capturable)."""
+        check(self._lib.sgm_resize_device(
+            self._h, ctypes.c_void_p(d_src or None), int(src_rows), int(src_cols),
+            src_cols if src_pitch is None else src_pitch, ctypes.c_void_p(d_dst or None),
+            self.w if dst_pitch is None else dst_pitch, _stream(stream)), self._h)
+
+    def get_resized(self, view: int = 0) -> np.ndarray:
+        """The last frame's resized image of `view` (0 = left, 1 = right):
+        h x w uint8, a host copy (sgm_stage_resized)."""
+        out = np.empty((self.h, self.w), np.uint8)
+        check(self._lib.sgm_stage_resized(self._h, int(view), _ptr(out)), self._h)
+        return out
 
     def check(self) -> None:
         """sgm_check: wait for the frames enqueued so far and raise SGMError
@@ -419,10 +470,11 @@ class BM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
-                 post_filter_launches: int = 0):
+                 post_filter_launches: int = 0, input_size=None):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
-                         post_filter_launches=post_filter_launches, _solver=_capi.SGM_SOLVER_BM)
+                         post_filter_launches=post_filter_launches, input_size=input_size,
+                         _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -435,6 +487,7 @@ class GPU_SGM(SGM):
     approximations."""
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
-                 post_filter_launches: int = 0, min_disp: int = 0):
+                 post_filter_launches: int = 0, min_disp: int = 0, input_size=None):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
-                         post_filter_launches=post_filter_launches, min_disp=min_disp)
+                         post_filter_launches=post_filter_launches, min_disp=min_disp,
+                         input_size=input_size)
