@@ -3,6 +3,7 @@
 //
 //   images (8-bit PGM)            node.cpp:69-70   imread(..., IMREAD_GRAYSCALE)
 //   resize to img_w x img_h       node.cpp:75-78   cv::resize on the GPU (HipSolver::resize)
+//   or rectify (MAPS.f32)         (not in the node) cv::remap on the GPU (HipSolver::set_rectify)
 //   sky masks, both views         node.cpp:80-87   SkyAreaDetector::detect
 //   SGM(h, w, s, d).process       node.cpp:49,93   (both views, LR check, post_filter)
 //   get_disp()                    node.cpp:104     -> OUT_disp.f32 (raw float32 rows)
@@ -15,9 +16,14 @@
 // detector, the matcher and the point cloud see them.  The calibration
 // (read_calib, utils.cpp:59-89) comes from the command line.  Every stage runs
 // on the GPU.
+// With MAPS.f32 -- four dense img_h x img_w float32 planes x_l, y_l, x_r, y_r,
+// cv::initUndistortRectifyMap's CV_32FC1 outputs for both views -- the images
+// are raw camera images and are rectified instead of resized: the sky detector
+// sees HipSolver::remap's images, process() takes the raw pair and every frame
+// begins with the remap, and the cloud reads the rectified left image.
 //
 // usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX
-//                    [scale max_disp [fx fy cx cy [min_disp [img_w img_h]]]]
+//                    [scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32]]]]]
 // min_disp (not in the node): search disparities [min_disp, min_disp + max_disp);
 // the map, the debug view and the cloud are then in true disparity.
 #include "sgm_amd/SGM.h"
@@ -63,10 +69,10 @@ static bool write_ppm(const std::string &path, const Mat &bgr) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 4 && argc != 6 && argc != 10 && argc != 11 && argc != 13) {
+    if (argc != 4 && argc != 6 && argc != 10 && argc != 11 && argc != 13 && argc != 14) {
         std::fprintf(stderr,
                      "usage: %s LEFT.pgm RIGHT.pgm OUT_PREFIX "
-                     "[scale max_disp [fx fy cx cy [min_disp [img_w img_h]]]]\n",
+                     "[scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32]]]]]\n",
                      argv[0]);
         return 2;
     }
@@ -98,12 +104,32 @@ int main(int argc, char **argv) {
     sgm_amd::SolverPtr sv = std::make_shared<sgm_amd::SGM>(h, w, scale, max_disp, 8, min_disp);
     SkyDetPtr sky_det = std::make_shared<sky_detector::SkyAreaDetector>();
 
-    if (argc > 12) {  // node.cpp:75-78, on the GPU
+    Mat raw_l = img_l, raw_r = img_r;  // what process() takes
+    if (argc > 13) {  // rectify instead: the maps are at the configured size
+        sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
+        Mat maps[4];
+        std::ifstream f(argv[13], std::ios::binary);
+        for (Mat &m : maps) {
+            m.create(h, w, CV_32FC1);
+            f.read(reinterpret_cast<char *>(m.data), (std::streamsize)h * w * 4);
+        }
+        if (!f || f.peek() != std::ifstream::traits_type::eof()) {
+            std::fprintf(stderr, "%s does not hold four %d x %d float32 planes\n", argv[13], h, w);
+            return 2;
+        }
+        sgm->set_rectify(img_l.rows, img_l.cols, maps[0], maps[1], maps[2], maps[3]);
+        sgm->remap(raw_l, img_l, 0);  // for the sky detector; the frame remaps the raw pair itself
+        sgm->remap(raw_r, img_r, 1);
+        std::printf("rectified left size: %d, %d\n", img_l.rows, img_l.cols);
+        std::printf("rectified right size: %d, %d\n", img_r.rows, img_r.cols);
+    } else if (argc > 12) {  // node.cpp:75-78, on the GPU
         sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
         sgm->resize(img_l, img_l);
         sgm->resize(img_r, img_r);
         std::printf("resized left size: %d, %d\n", img_l.rows, img_l.cols);
         std::printf("resized right size: %d, %d\n", img_r.rows, img_r.cols);
+        raw_l = img_l;
+        raw_r = img_r;
     }
 
     Mat sky_mask, sky_mask_beta;  // node.cpp:80-87 (no debug image is written)
@@ -111,7 +137,7 @@ int main(int argc, char **argv) {
     sky_det->detect(img_r, out + "_sky2.png", sky_mask_beta, scale);
 
     const auto be = std::chrono::steady_clock::now();
-    sv->process(img_l, img_r, sky_mask, sky_mask_beta);  // node.cpp:93
+    sv->process(raw_l, raw_r, sky_mask, sky_mask_beta);  // node.cpp:93
     const auto en = std::chrono::steady_clock::now();
     std::printf("stereo matching done\ntime cost: %lf ms\n",
                 std::chrono::duration<double, std::milli>(en - be).count());
@@ -133,6 +159,7 @@ int main(int argc, char **argv) {
     std::vector<unsigned char> pix(npx);
     int n = 0;
     Mat packed = disp.clone();
+    if (argc > 13) img_l = static_cast<sgm_amd::SGM *>(sv.get())->rectified(0);  // what the frame matched
     const int rc = sgm_stage_point_cloud(static_cast<sgm_amd::SGM *>(sv.get())->handle(),
                                          packed.ptr<float>(0), img_l.data, (int)img_l.step, &cam,
                                          xyz.data(), pix.data(), &n);

@@ -22,6 +22,10 @@
  *   resize(src, dst)             node.cpp:75-76     cv::resize(src, dst, Size(w, h)) on the GPU
  *   set_input_size(rows, cols)   (not in the reference) process() takes rows x cols images
  *                                and resizes them on the GPU first
+ *   set_rectify(rows, cols, xl, yl, xr, yr)  (not in the reference) process() takes raw
+ *                                rows x cols camera images and rectifies them on the GPU
+ *                                first: cv::remap through initUndistortRectifyMap's maps
+ *   remap(src, dst, view)        cv::remap(src, dst, map_x, map_y, INTER_LINEAR) on the GPU
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -238,7 +242,7 @@ public:
             fail("process", "inputs must be CV_8UC1 of the constructed size (SGM.cpp:34-38)");
         this->img_l = img_l;  // shallow, as SGM.cpp:59-60 (decimated on the device)
         this->img_r = img_r;
-        if (resizing_) {  // checked before any work: the resized images' host copies
+        if (resizing_ || rectifying_) {  // checked before any work: the resized images' host copies
             resized_[0] = Mat(full_h_, full_w_, CV_8UC1);
             resized_[1] = Mat(full_h_, full_w_, CV_8UC1);
         }
@@ -274,6 +278,13 @@ public:
             this->img_l = resized_[0];
             this->img_r = resized_[1];
         }
+        if (rectifying_) {  // likewise: the rectified pair the frame matched
+            for (int v = 0; v < 2; ++v)
+                if (sgm_stage_rectified(handle_, v, resized_[v].data) != SGM_OK)
+                    fail("process", sgm_last_error(handle_));
+            this->img_l = resized_[0];
+            this->img_r = resized_[1];
+        }
         if (scale > 1) decimate_left();
     }
 
@@ -293,16 +304,69 @@ public:
     // and images of any other size fail as a wrong-size image does.  (0, 0):
     // off, the constructed size again.
     void set_input_size(int rows, int cols) {
-        if (sgm_set_input_size(handle_, rows, cols) != SGM_OK)
-            fail("set_input_size", sgm_last_error(handle_));
-        resizing_ = rows != 0;
-        in_h_ = resizing_ ? rows : full_h_;
-        in_w_ = resizing_ ? cols : full_w_;
-        if (!resizing_) resized_[0] = resized_[1] = Mat();
+        const int rc = sgm_set_input_size(handle_, rows, cols);
+        sync_input_stage();  // (before failing: a failed allocation leaves the handle's stage off)
+        if (rc != SGM_OK) fail("set_input_size", sgm_last_error(handle_));
     }
     // CV_8UC1 at the constructed size: the last process()'s resized image of
     // `view` (0 left, 1 right); empty while no input size is set
-    const Mat &get_resized(int view) const { return resized_[view == 1 ? 1 : 0]; }
+    const Mat &get_resized(int view) const { return resizing_ ? resized_[view == 1 ? 1 : 0] : none_; }
+
+    // Rectification (sgm_set_rectify): process() then takes raw rows x cols
+    // camera images, and every frame starts by remapping both through these
+    // maps on the GPU -- cv::initUndistortRectifyMap(..., CV_32FC1, ...)'s
+    // outputs at the constructed size, one pair per view; cv::convertMaps +
+    // cv::remap INTER_LINEAR, BORDER_CONSTANT 0 in their pinned fixed-point
+    // form.  The maps may read a source of any size, so this also resizes: not
+    // together with set_input_size.  (0, 0) with four empty Mats: off.
+    void set_rectify(int rows, int cols, const Mat &map_x_l, const Mat &map_y_l, const Mat &map_x_r,
+                     const Mat &map_y_r) {
+        const Mat *in[4] = {&map_x_l, &map_y_l, &map_x_r, &map_y_r};
+        Mat m[4];
+        bool same_step = true;
+        for (int k = 0; k < 4; ++k) {
+            if (!in[k]->empty() &&
+                (in[k]->type() != CV_32FC1 || in[k]->rows != full_h_ || in[k]->cols != full_w_))
+                fail("set_rectify", "maps must be CV_32FC1 of the constructed size");
+            m[k] = *in[k];
+            same_step = same_step && (m[k].empty() || m[0].empty() || m[k].step == m[0].step);
+        }
+        // the C-ABI takes one pitch for the four maps: dense copies when their steps differ
+        for (int k = 0; k < 4 && !same_step; ++k)
+            if (!m[k].empty()) m[k] = m[k].clone();
+        int pitch = full_w_;
+        for (int k = 0; k < 4; ++k)
+            if (!m[k].empty()) pitch = (int)(m[k].step / sizeof(float));
+        const float *p[4];
+        for (int k = 0; k < 4; ++k) p[k] = m[k].empty() ? nullptr : m[k].template ptr<float>(0);
+        const int rc = sgm_set_rectify(handle_, rows, cols, p[0], p[1], p[2], p[3], pitch);
+        sync_input_stage();  // (before failing: a failed replacement of maps leaves them off)
+        if (rc != SGM_OK) fail("set_rectify", sgm_last_error(handle_));
+    }
+    // cv::remap(src, dst, map_x, map_y, INTER_LINEAR) of `view`'s (0 left, 1
+    // right) raw image through the maps set, on the GPU (sgm_stage_remap);
+    // dst may be src.
+    void remap(const Mat &src, Mat &dst, int view) {
+        int rows = 0, cols = 0;
+        sgm_get_rectify(handle_, &rows, &cols);
+        if (rows && (src.type() != CV_8UC1 || src.rows != rows || src.cols != cols))
+            fail("remap", "src must be a CV_8UC1 image of the size the maps were set for");
+        Mat out(full_h_, full_w_, CV_8UC1);
+        if (sgm_stage_remap(handle_, view, src.data, (int)src.step, out.data) != SGM_OK)
+            fail("remap", sgm_last_error(handle_));
+        dst = out;
+    }
+    // CV_8UC1 at the constructed size: the last process()'s rectified image of
+    // `view` (0 left, 1 right); empty while no maps are set
+    const Mat &rectified(int view) const { return rectifying_ ? resized_[view == 1 ? 1 : 0] : none_; }
+    // CV_8UC1 at the constructed size: 255 where all four taps of the pixel
+    // lie inside the raw image, else 0 (stereoRectify's validPixROI per pixel)
+    Mat rectify_valid(int view) {
+        Mat out(full_h_, full_w_, CV_8UC1);
+        if (sgm_stage_rectify_valid(handle_, view, out.data) != SGM_OK)
+            fail("rectify_valid", sgm_last_error(handle_));
+        return out;
+    }
 
     sgm_handle *handle() const { return handle_; }
 
@@ -362,7 +426,23 @@ private:
     Mat confidence_;
     int full_h_, full_w_;    // the constructed size (in_h_, in_w_: what process() takes)
     bool resizing_ = false;  // set_input_size
-    Mat resized_[2];
+    bool rectifying_ = false;  // set_rectify
+    Mat resized_[2];         // the resized or rectified pair of the last process()
+    Mat none_;
+
+    // resizing_, rectifying_ and the size process() takes, read back from the
+    // handle (sgm_last_error is untouched): at most one of the two stages is
+    // set, and switching the other off changes nothing
+    void sync_input_stage() {
+        int rs_rows = 0, rs_cols = 0, rc_rows = 0, rc_cols = 0;
+        sgm_get_input_size(handle_, &rs_rows, &rs_cols);
+        sgm_get_rectify(handle_, &rc_rows, &rc_cols);
+        resizing_ = rs_rows != 0;
+        rectifying_ = rc_rows != 0;
+        in_h_ = resizing_ ? rs_rows : rectifying_ ? rc_rows : full_h_;
+        in_w_ = resizing_ ? rs_cols : rectifying_ ? rc_cols : full_w_;
+        if (!resizing_ && !rectifying_) resized_[0] = resized_[1] = Mat();
+    }
 
     void check_mask(const Mat &m, const char *what) const {
         if (m.type() != CV_8UC1 || m.rows != img_h || m.cols != img_w)

@@ -235,6 +235,72 @@ int sgm_get_resized(sgm_handle *h, int view, const uint8_t **d_img, int *pitch);
 /* The same image copied to a HOST buffer (height x width, dense); synchronous. */
 int sgm_stage_resized(sgm_handle *h, int view, uint8_t *img);
 
+/* ---- rectification: cv::convertMaps + cv::remap of raw camera images ----
+ *
+ * cv::remap of an 8-bit one-channel image with INTER_LINEAR and BORDER_CONSTANT
+ * 0, over maps converted as cv::convertMaps does to OpenCV's fixed-point form
+ * (5 fraction bits), pinned as DESIGN.md 5k states it and bit-exact against
+ * tests/rectify_recipe.py: per coordinate q = rint(c * 32) clamped to
+ * [-32768 * 32, 32767 * 32] (NaN: the lower clamp), x0 = q >> 5, a = q & 31, and
+ *   dst = ((32-a)(32-b) S(y0,x0) + a(32-b) S(y0,x0+1) + (32-a)b S(y0+1,x0)
+ *          + ab S(y0+1,x0+1) + 512) >> 10,   S = 0 outside the source, per tap.
+ * Parity with a particular OpenCV build is not pinned at this boundary, as for
+ * the pre-blur and the resize.
+ *
+ * sgm_set_rectify: a property of the handle, like sgm_set_input_size
+ * (sgm_params and SGM_HIP_VERSION are unchanged).  Takes each view's HOST float
+ * maps as cv::initUndistortRectifyMap(..., CV_32FC1, ...) returns them, at the
+ * handle's full size (height x width, map_pitch floats per row): map_x[i, j],
+ * map_y[i, j] is the position in the src_rows x src_cols source that
+ * destination pixel (i, j) samples.  The source may be any size in [1, 32767]
+ * per axis, so the remap also does the resize; non-finite and huge coordinates
+ * give 0 pixels.  Converts the maps once on the host, uploads them packed (8
+ * bytes per pixel and view, counted in sgm_device_bytes) and keeps the valid
+ * masks.  (0, 0) with four NULL maps = off (default): everything is freed and
+ * frames run exactly as before.  Calling it again replaces the maps.
+ * With maps set, sgm_process and sgm_process_device take src_rows x src_cols
+ * images (pitch >= src_cols; a side-by-side frame splits by pitch: left = frame,
+ * right = frame + cols, pitch = 2 cols).  The frame's first launch remaps both
+ * into handle-owned height x width images (one-view and BM handles need both
+ * views' maps too: every frame handle's census reads both images), and
+ * everything inside the frame reads those: the census, the in-frame sky
+ * detector, the in-frame LKRefine, the BM solver.  Sky masks passed in stay on
+ * the working grid; the stand-alone stage calls keep taking full-size images.
+ * An aux_only handle may hold maps (for sgm_remap_device) but runs no frames.
+ * Synchronises the handle's last work first; call it outside stream capture,
+ * and re-capture graphs afterwards.  SGM_ERR_INVALID_ARG, with a message, for a
+ * size outside [1, 32767] (other than the all-off form), exactly one of the two
+ * zero, a NULL map with a non-zero size, map_pitch < width, and a non-zero size
+ * while an input size is set (sgm_set_input_size refuses a non-zero size while
+ * maps are set: one input stage at a time). */
+int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_x_l,
+                    const float *map_y_l, const float *map_x_r, const float *map_y_r,
+                    int map_pitch);
+int sgm_get_rectify(const sgm_handle *h, int *src_rows, int *src_cols);
+/* Remaps `view`'s (SGM_VIEW_LEFT / SGM_VIEW_RIGHT) source image (src_rows x
+ * src_cols u8 DEVICE memory, src_pitch bytes) into dst (height x width,
+ * dst_pitch bytes; padding untouched).  One launch on `stream` (NULL = the
+ * handle's stream), no host wait, no allocation: capturable into a HIP graph.
+ * Any handle with maps set serves, aux_only included.  SGM_ERR_INVALID_ARG,
+ * with a message, for a NULL pointer, no maps set, a view other than 0 or 1,
+ * src_pitch < src_cols or dst_pitch < width. */
+int sgm_remap_device(sgm_handle *h, int view, const uint8_t *d_src, int src_pitch,
+                     uint8_t *d_dst, int dst_pitch, void *stream);
+/* The same with HOST buffers (dst dense, height x width); synchronous. */
+int sgm_stage_remap(sgm_handle *h, int view, const uint8_t *src, int src_pitch, uint8_t *dst);
+/* The last frame's rectified image of `view`: handle-owned DEVICE memory,
+ * height x width u8, *pitch bytes per row; valid until the next frame,
+ * sgm_set_rectify or sgm_destroy.  What the point cloud reads.  Reads of it are
+ * ordered after the frame on the frame's stream only.  SGM_ERR_INVALID_ARG with
+ * no maps set, before any frame, for any other view, or a NULL pointer. */
+int sgm_get_rectified(sgm_handle *h, int view, const uint8_t **d_img, int *pitch);
+/* The same image copied to a HOST buffer (height x width, dense); synchronous. */
+int sgm_stage_rectified(sgm_handle *h, int view, uint8_t *img);
+/* `view`'s valid mask, to a HOST buffer (height x width, dense): 255 where all
+ * four taps of the pixel lie inside the source, else 0 -- the per-pixel form of
+ * stereoRectify's validPixROI.  Built on the host when the maps are set. */
+int sgm_stage_rectify_valid(sgm_handle *h, int view, uint8_t *mask);
+
 /* Bytes of device memory the handle holds. */
 size_t sgm_device_bytes(const sgm_handle *h);
 /* The handle's own stream (a hipStream_t; what a NULL stream argument

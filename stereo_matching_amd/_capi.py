@@ -42,6 +42,8 @@ EXPORTS = (
     "sgm_set_min_disp", "sgm_get_invalid_disp",
     "sgm_resize_device", "sgm_stage_resize", "sgm_set_input_size", "sgm_get_input_size",
     "sgm_get_resized", "sgm_stage_resized",
+    "sgm_set_rectify", "sgm_get_rectify", "sgm_remap_device", "sgm_stage_remap",
+    "sgm_get_rectified", "sgm_stage_rectified", "sgm_stage_rectify_valid",
 )
 SGM_COMM_ID_BYTES = 128
 
@@ -161,6 +163,13 @@ def lib():
     L.sgm_get_input_size.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
     L.sgm_get_resized.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
     L.sgm_stage_resized.argtypes = [P, I, P]
+    L.sgm_set_rectify.argtypes = [P, I, I, P, P, P, P, I]
+    L.sgm_get_rectify.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
+    L.sgm_remap_device.argtypes = [P, I, P, I, P, I, P]
+    L.sgm_stage_remap.argtypes = [P, I, P, I, P]
+    L.sgm_get_rectified.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
+    L.sgm_stage_rectified.argtypes = [P, I, P]
+    L.sgm_stage_rectify_valid.argtypes = [P, I, P]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

@@ -110,9 +110,10 @@ void free_all(sgm_handle *h) {
 // memory on the CPU, so every host<->device transfer is one contiguous DMA
 // (pageable 2-D copies went through the runtime's staging path at a fraction
 // of PCIe bandwidth).  Layout: left | right | sky_l | sky_r | out f32 | raw u16.
-// rows x cols of the images a frame takes: the input size when one is set
-inline int frame_rows(const sgm_handle *h) { return h->in_rows ? h->in_rows : h->p.height; }
-inline int frame_cols(const sgm_handle *h) { return h->in_rows ? h->in_cols : h->p.width; }
+// rows x cols of the images a frame takes: the input size or the rectification
+// maps' source size when one is set (never both)
+inline int frame_rows(const sgm_handle *h) { return h->in_rows ? h->in_rows : h->rc_rows ? h->rc_rows : h->p.height; }
+inline int frame_cols(const sgm_handle *h) { return h->in_rows ? h->in_cols : h->rc_rows ? h->rc_cols : h->p.width; }
 
 int ensure_pinned(sgm_handle *h) {
     const size_t nin = (size_t)frame_rows(h) * frame_cols(h), npx = (size_t)h->g.H * h->g.W;
@@ -513,6 +514,10 @@ int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols) {
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_set_input_size: an aux_only handle runs no frames (sgm_resize_device "
                        "takes its sizes per call)");
+    if (h->rc_rows && src_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_input_size: rectification maps are set (sgm_set_rectify): one input "
+                       "stage at a time, and the remap resizes too");
     DeviceGuard guard(h->device);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
@@ -624,6 +629,163 @@ int sgm_stage_resize(sgm_handle *h, const uint8_t *src, int src_rows, int src_co
     }
     HIPCHK(h, hipStreamSynchronize(h->st));
     return rc;
+}
+
+// ---- rectification (sgm_rectify.hip, sgm_rectify_maps.h)
+
+// Frees what sgm_set_rectify allocated and switches it off.
+static void rectify_off(sgm_handle *h) {
+    const size_t nfull = (size_t)h->p.height * h->p.width, nsrc = (size_t)h->rc_rows * h->rc_cols;
+    for (int v = 0; v < 2; ++v) {
+        dfree(h, &h->d_map[v], 2 * nfull);
+        if (!h->p.aux_only) {
+            dfree(h, &h->d_raw[v], nsrc);
+            dfree(h, &h->d_rs[v], nfull);
+        }
+        std::vector<uint8_t>().swap(h->valid[v]);
+    }
+    h->rc_rows = h->rc_cols = 0;
+    h->rs_valid = false;
+}
+
+int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_x_l, const float *map_y_l,
+                    const float *map_x_r, const float *map_y_r, int map_pitch) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    const float *const maps[4] = {map_x_l, map_y_l, map_x_r, map_y_r};
+    if (!rectify_args_ok(src_rows, src_cols, maps, map_pitch, h->p.width, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_rectify: %s", why);
+    if (h->in_rows && src_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_rectify: an input size is set (sgm_set_input_size): one input stage at "
+                       "a time, and the remap resizes too");
+    DeviceGuard guard(h->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_rectify: call it outside stream capture");
+    if (!src_rows && !h->rc_rows) return SGM_OK;
+    // frames in flight still read the maps, the staged and the rectified images
+    if (int rc = wait_last(h)) return rc;
+    rectify_off(h);
+    if (!src_rows) return SGM_OK;
+    const size_t nfull = (size_t)h->p.height * h->p.width, nsrc = (size_t)src_rows * src_cols;
+    h->rc_rows = src_rows;  // (rectify_off frees by these sizes on a failure below)
+    h->rc_cols = src_cols;
+    std::vector<uint32_t> packed;
+    int rc = SGM_OK;
+    try {
+        packed.resize(2 * nfull);
+        for (int v = 0; v < 2; ++v) h->valid[v].resize(nfull);
+    } catch (const std::bad_alloc &) {
+        rc = set_err(h, SGM_ERR_OUT_OF_MEMORY, "sgm_set_rectify: out of host memory");
+    }
+    for (int v = 0; v < 2 && !rc; ++v) {
+        rectify_convert(maps[2 * v], maps[2 * v + 1], map_pitch, h->p.height, h->p.width, src_rows, src_cols,
+                        packed.data(), h->valid[v].data());
+        if ((rc = dalloc(h, &h->d_map[v], 2 * nfull))) break;
+        if (hipMemcpy(h->d_map[v], packed.data(), 2 * nfull * sizeof(uint32_t), hipMemcpyHostToDevice) !=
+            hipSuccess)
+            rc = set_err(h, SGM_ERR_HIP, "sgm_set_rectify: the upload of the packed map failed");
+        // (an aux_only handle runs no frames: it keeps the maps for sgm_remap_device alone)
+        if (!rc && !h->p.aux_only) {
+            if ((rc = dalloc(h, &h->d_rs[v], nfull))) break;
+            rc = dalloc(h, &h->d_raw[v], nsrc);
+        }
+    }
+    if (rc) rectify_off(h);  // (off again: the handle runs as before)
+    return rc;
+}
+
+int sgm_get_rectify(const sgm_handle *h, int *src_rows, int *src_cols) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (src_rows) *src_rows = h->rc_rows;
+    if (src_cols) *src_cols = h->rc_cols;
+    return SGM_OK;
+}
+
+int sgm_remap_device(sgm_handle *h, int view, const uint8_t *d_src, int src_pitch, uint8_t *d_dst,
+                     int dst_pitch, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!d_src || !d_dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_remap_device: NULL pointer");
+    if (!h->rc_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_remap_device: no maps are set (sgm_set_rectify)");
+    if (!rectify_call_ok(view, src_pitch, h->rc_cols, dst_pitch, h->p.width, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_remap_device: %s", why);
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "rectify", (double)h->p.height * h->p.width, st, [&] {
+               return sgm::launch_rectify(&d_src, h->rc_rows, h->rc_cols, src_pitch, &h->d_map[view], &d_dst,
+                                          h->p.height, h->p.width, dst_pitch, 1, st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_stage_remap(sgm_handle *h, int view, const uint8_t *src, int src_pitch, uint8_t *dst) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: NULL pointer");
+    if (!h->rc_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: no maps are set (sgm_set_rectify)");
+    if (!rectify_call_ok(view, src_pitch, h->rc_cols, h->p.width, h->p.width, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: %s", why);
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    const size_t nsrc = (size_t)h->rc_rows * h->rc_cols, nfull = (size_t)h->p.height * h->p.width;
+    int rc;
+    {
+        // staging: the source in a stream-ordered temporary, the result in d_in[0]
+        StreamTemp<uint8_t> d_src(h->st);
+        HIPCHK(h, hipMallocAsync((void **)&d_src.p, nsrc, h->st));
+        HIPCHK(h, hipMemcpy2DAsync(d_src.p, (size_t)h->rc_cols, src, (size_t)src_pitch, (size_t)h->rc_cols,
+                                   (size_t)h->rc_rows, hipMemcpyHostToDevice, h->st));
+        rc = sgm_remap_device(h, view, d_src.p, h->rc_cols, h->d_in[0], h->p.width, h->st);
+        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, h->d_in[0], nfull, hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return rc;
+}
+
+int sgm_get_rectified(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!d_img || !pitch) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: NULL pointer");
+    if (!h->rc_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: no maps are set (sgm_set_rectify)");
+    // (every frame handle's census reads both images, so both are rectified)
+    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: the handle reads no image of view %d", view);
+    if (!h->rs_valid)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: no frame has run since the maps were set");
+    *d_img = h->d_rs[view];
+    *pitch = h->p.width;
+    return SGM_OK;
+}
+
+int sgm_stage_rectified(sgm_handle *h, int view, uint8_t *img) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!img) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectified: NULL pointer");
+    const uint8_t *d_img = nullptr;
+    int pitch = 0;
+    if (int rc = sgm_get_rectified(h, view, &d_img, &pitch)) return rc;
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return SGM_OK;
+}
+
+int sgm_stage_rectify_valid(sgm_handle *h, int view, uint8_t *mask) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!mask) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: NULL pointer");
+    if (!h->rc_rows)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: no maps are set (sgm_set_rectify)");
+    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: view must be 0 (left) or 1 (right), got %d",
+                       view);
+    memcpy(mask, h->valid[view].data(), h->valid[view].size());
+    return SGM_OK;
 }
 
 int sgm_set_confidence(sgm_handle *h, int enable) {
@@ -764,9 +926,9 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
     if ((rc = ensure_pinned(h))) return rc;
-    // (with an input size set the raw images are staged and the frame resizes them)
+    // (with an input size or maps set the raw images are staged and the frame resizes or remaps them)
     const int in_h = frame_rows(h), in_w = frame_cols(h);
-    uint8_t *const *d_in = h->in_rows ? h->d_raw : h->d_in;
+    uint8_t *const *d_in = h->in_rows || h->rc_rows ? h->d_raw : h->d_in;
     const size_t nin = (size_t)in_h * in_w, npx = (size_t)h->g.H * h->g.W;
     uint8_t *pl = h->h_pin, *pr = pl + nin, *psl = pr + nin, *psr = psl + npx;
     float *pout = reinterpret_cast<float *>(psr + npx + (16 - (size_t)(psr + npx) % 16) % 16);

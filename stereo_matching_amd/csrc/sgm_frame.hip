@@ -574,6 +574,18 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
         f.right = h->d_rs[1];
         f.pitch = h->p.width;
         h->rs_valid = true;
+    } else if (h->rc_rows) {
+        // with rectification maps set the same slot remaps both images instead
+        // (the maps are built at the full size, so the remap resizes too)
+        const uint8_t *src[2] = {f.left, f.right};
+        HIPCHK(h, timed(h, "rectify", 2.0 * h->p.height * h->p.width, st, [&] {
+                   return sgm::launch_rectify(src, h->rc_rows, h->rc_cols, f.pitch, h->d_map, h->d_rs,
+                                              h->p.height, h->p.width, h->p.width, 2, st);
+               }));
+        f.left = h->d_rs[0];
+        f.right = h->d_rs[1];
+        f.pitch = h->p.width;
+        h->rs_valid = true;
     }
     // Everything runs on one stream.  Two-view frames keep each view's cost
     // volume resident in the 256 MB Infinity Cache through its readers by

@@ -48,6 +48,11 @@ struct sgm_handle {
     uint8_t *d_rs[2];     //   and resize them into these full-size images first (left, right)
     uint8_t *d_raw[2];    //   staging of the raw images (host API)
     bool rs_valid;        //   a frame has filled d_rs since the size was set (sgm_get_resized)
+    int rc_rows, rc_cols; // sgm_set_rectify: frames take rc_rows x rc_cols images (0, 0: off; never
+                          //   together with an input size) and remap them into d_rs first, staged
+                          //   in d_raw like the resize's (aux_only handles: the maps alone)
+    uint32_t *d_map[2];   //   each view's packed map, two words per full-size pixel (sgm_rectify_maps.h)
+    std::vector<uint8_t> valid[2];  //   each view's valid mask (host, full size, dense)
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
@@ -274,7 +279,7 @@ inline float *t_buf(sgm_handle *h, int v) { return h->d_ch[v]; }
 
 // One frame's device buffers, as sgm_process_device takes them.
 struct FrameIO {
-    const uint8_t *left, *right;  // full-size images (input-size images with an input size set)
+    const uint8_t *left, *right;  // full-size images (camera-size images with an input size or maps set)
     int pitch;
     const uint8_t *sky_l, *sky_r;  // working-grid sky masks (null: none)
     int sky_pitch;

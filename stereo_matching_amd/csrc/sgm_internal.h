@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sgm_rectify_maps.h"
 #include "sgm_resize_args.h"
 
 namespace sgm {
@@ -296,6 +297,13 @@ hipError_t launch_sky_detect(const uint8_t *const *img, int pitch, uint8_t *cons
 hipError_t launch_resize(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
                          uint8_t *const *dst, int dst_rows, int dst_cols, int dst_pitch, int nviews,
                          hipStream_t st);
+// The rectification remap (sgm_rectify.hip) of nviews (1 or 2) u8
+// images of one size in one launch: src[v] src_rows x src_cols (src_pitch
+// bytes) sampled through map[v] (dst_rows x dst_cols packed entries of two
+// words, sgm_rectify_maps.h) -> dst[v] (dst_pitch bytes, padding untouched).
+hipError_t launch_rectify(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
+                          const uint32_t *const *map, uint8_t *const *dst, int dst_rows, int dst_cols,
+                          int dst_pitch, int nviews, hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

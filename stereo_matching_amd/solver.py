@@ -54,7 +54,7 @@ class SGM:
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
-                 input_size=None, _solver: int = _capi.SGM_SOLVER_SGM):
+                 input_size=None, rectify=None, _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
         # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
@@ -113,6 +113,9 @@ class SGM:
         # input_size = (h0, w0): process() takes h0 x w0 images and the frame
         # resizes them to h x w first, as the node does (node.cpp:75-76;
         # set_input_size)
+        # rectify = (src_h, src_w, mapx_l, mapy_l, mapx_r, mapy_r): process()
+        # takes raw src_h x src_w camera images and the frame remaps them
+        # through the h x w float maps first (set_rectify); not with input_size
         self.in_h, self.in_w = h, w
         try:
             if post_filter_launches:
@@ -121,6 +124,8 @@ class SGM:
                 self.set_confidence(True)
             if input_size is not None:
                 self.set_input_size(*input_size)
+            if rectify is not None:
+                self.set_rectify(*rectify)
         except Exception:
             self.close()
             raise
@@ -197,8 +202,21 @@ class SGM:
         images, and the frame's first launch resizes them to h x w (the node's
         cv::resize, node.cpp:75-76, in its pinned fixed-point form); (0, 0)
         switches it off.  Not inside stream capture; re-capture graphs."""
-        check(self._lib.sgm_set_input_size(self._h, int(rows), int(cols)), self._h)
-        self.in_h, self.in_w = (int(rows), int(cols)) if rows else (self.h, self.w)
+        try:
+            check(self._lib.sgm_set_input_size(self._h, int(rows), int(cols)), self._h)
+        finally:
+            self._sync_input_shape()
+
+    def _sync_input_shape(self) -> None:
+        """in_h, in_w: the shape of the images process() takes, read back from
+        the handle -- the input size or the rectification maps' source size,
+        whichever is set (never both), else h x w.  After every setter call,
+        a failed one included: switching the inactive stage off changes
+        nothing, and a failed replacement of maps leaves them off."""
+        rows, cols = self.input_size
+        if not rows:
+            rows, cols = self.rectify_size
+        self.in_h, self.in_w = (rows, cols) if rows else (self.h, self.w)
 
     @property
     def input_size(self):
@@ -234,6 +252,70 @@ class SGM:
         h x w uint8, a host copy (sgm_stage_resized)."""
         out = np.empty((self.h, self.w), np.uint8)
         check(self._lib.sgm_stage_resized(self._h, int(view), _ptr(out)), self._h)
+        return out
+
+    # ------------------------------------------------------ rectification
+    def set_rectify(self, src_rows: int, src_cols: int, mapx_l=None, mapy_l=None,
+                    mapx_r=None, mapy_r=None) -> None:
+        """sgm_set_rectify: process() / process_device() take raw src_rows x
+        src_cols camera images, and the frame's first launch remaps both
+        through the h x w float32 maps (cv::initUndistortRectifyMap's CV_32FC1
+        outputs; cv::convertMaps + cv::remap INTER_LINEAR, BORDER_CONSTANT 0 in
+        their pinned fixed-point form).  (0, 0) with no maps
+        switches it off.  Not inside stream capture; re-capture graphs."""
+        maps = []
+        for name, m in (("mapx_l", mapx_l), ("mapy_l", mapy_l), ("mapx_r", mapx_r), ("mapy_r", mapy_r)):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.float32)
+                if m.shape != (self.h, self.w):
+                    raise ValueError(f"{name}: expected shape {(self.h, self.w)}, got {m.shape}")
+            maps.append(m)
+        try:
+            check(self._lib.sgm_set_rectify(self._h, int(src_rows), int(src_cols), *(_ptr(m) for m in maps),
+                                            self.w), self._h)
+        finally:
+            self._sync_input_shape()
+
+    @property
+    def rectify_size(self):
+        """(rows, cols) of the raw images the maps read; (0, 0): no maps set."""
+        r, c = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.sgm_get_rectify(self._h, ctypes.byref(r), ctypes.byref(c)), self._h)
+        return r.value, c.value
+
+    def remap(self, img, view: int = 0, pitch: int | None = None) -> np.ndarray:
+        """`view`'s (0 = left, 1 = right) raw image rectified on the GPU
+        (sgm_stage_remap): h x w uint8.  pitch: bytes per row of `img` when it
+        is a padded buffer (its last axis is then the pitch)."""
+        rows, cols = self.rectify_size
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        if rows and (a.ndim != 2 or a.shape[0] != rows or a.shape[1] != (pitch or cols)):
+            raise ValueError(f"img: expected shape {(rows, pitch or cols)}, got {a.shape}")
+        out = np.empty((self.h, self.w), np.uint8)
+        check(self._lib.sgm_stage_remap(self._h, int(view), _ptr(a), pitch or cols, _ptr(out)), self._h)
+        return out
+
+    def remap_device(self, d_src: int, d_dst: int, view: int = 0, *, src_pitch: int | None = None,
+                     dst_pitch: int | None = None, stream: int | None = None) -> None:
+        """The same on device buffers (sgm_remap_device: one launch, enqueue
+        only, capturable)."""
+        check(self._lib.sgm_remap_device(
+            self._h, int(view), ctypes.c_void_p(d_src or None),
+            self.rectify_size[1] if src_pitch is None else src_pitch, ctypes.c_void_p(d_dst or None),
+            self.w if dst_pitch is None else dst_pitch, _stream(stream)), self._h)
+
+    def rectified(self, view: int = 0) -> np.ndarray:
+        """The last frame's rectified image of `view` (0 = left, 1 = right):
+        h x w uint8, a host copy (sgm_stage_rectified)."""
+        out = np.empty((self.h, self.w), np.uint8)
+        check(self._lib.sgm_stage_rectified(self._h, int(view), _ptr(out)), self._h)
+        return out
+
+    def rectify_valid(self, view: int = 0) -> np.ndarray:
+        """`view`'s valid mask (sgm_stage_rectify_valid): h x w uint8, 255
+        where all four taps of the pixel lie inside the raw image, else 0."""
+        out = np.empty((self.h, self.w), np.uint8)
+        check(self._lib.sgm_stage_rectify_valid(self._h, int(view), _ptr(out)), self._h)
         return out
 
     def check(self) -> None:
@@ -470,11 +552,11 @@ class BM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
-                 post_filter_launches: int = 0, input_size=None):
+                 post_filter_launches: int = 0, input_size=None, rectify=None):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
                          post_filter_launches=post_filter_launches, input_size=input_size,
-                         _solver=_capi.SGM_SOLVER_BM)
+                         rectify=rectify, _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -487,7 +569,7 @@ class GPU_SGM(SGM):
     approximations."""
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
-                 post_filter_launches: int = 0, min_disp: int = 0, input_size=None):
+                 post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
                          post_filter_launches=post_filter_launches, min_disp=min_disp,
-                         input_size=input_size)
+                         input_size=input_size, rectify=rectify)

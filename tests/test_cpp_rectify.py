@@ -1,0 +1,140 @@
+"""The rectification remap's C++ side.  The host conversion
+(stereo_matching_amd/csrc/sgm_rectify_maps.h) runs as a stand-alone program
+(tests/cpp/rectify_maps_main.cpp), built once plainly and once under ASan and
+UBSan: the packed maps and valid masks it prints equal the recipe's
+(tests/rectify_recipe.py), and every argument error is refused.  The class
+surface (include/sgm_amd/SGM.h: set_rectify, process() on raw Mats, remap(),
+rectified(), rectify_valid()) compiles with g++ against the C-ABI library and
+-- on the GPU -- gives the map the Python pipeline computes on recipe(raw)."""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import rectify_recipe as rc
+from stereo_matching_amd import SGM, _capi, synthetic
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAPS_SRC = os.path.join(ROOT, "tests", "cpp", "rectify_maps_main.cpp")
+SURFACE_SRC = os.path.join(ROOT, "tests", "cpp", "sgm_rectify_surface.cpp")
+BUILDS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
+
+
+@pytest.fixture(scope="module", params=list(BUILDS))
+def maps_exe(request, tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("maps") / f"rectify_maps_{request.param}")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + BUILDS[request.param] + [MAPS_SRC, "-o", out],
+                   check=True, capture_output=True, text=True)
+    return out
+
+
+def run(exe, *args):
+    return subprocess.run([exe, *args], capture_output=True, text=True, timeout=60)     # directly: no preload
+
+
+def small_maps():
+    """6 x 9 maps onto a 5 x 7 source that hold every case of the CPU tests:
+    the identity, an integer shift, a = b = 31, each border straddled, the
+    ties with k even and odd, NaN, +-inf and +-1e30."""
+    mx, my = rc.identity_maps(6, 9)
+    mx[1] += 2                                        # an integer shift (its end leaves the source)
+    my[1] -= 1
+    mx[2, :4] = [31 / 32, 1 + 31 / 32, -0.5, 6.5]     # a = 31; left and right borders straddled
+    my[2, :4] = [31 / 32, 2, 1, 1]
+    mx[3, :4] = [2, 2, -0.5, 6.5]                     # top, bottom, two corners
+    my[3, :4] = [-0.75, 4.75, -0.5, 4.5]
+    ks = [0, 1, 2, 3, 30, 31, 32, 33, 95]
+    mx[4] = [(k + 0.5) / 32 for k in ks]              # the ties, k even and odd
+    my[4] = [-(k + 0.5) / 32 for k in ks]
+    mx[5, :5] = rc.SPECIALS
+    my[5, 4:9] = rc.SPECIALS
+    return mx.astype(np.float32), my.astype(np.float32)
+
+
+@pytest.mark.parametrize("pitch", [9, 13])
+def test_conversion_matches_the_recipe(maps_exe, tmp_path, pitch):
+    mx, my = small_maps()
+    h, w = mx.shape
+    path = str(tmp_path / "maps.f32")
+    with open(path, "wb") as f:
+        for m in (mx, my):
+            buf = np.full((h, pitch), np.nan, np.float32)     # (padding the conversion must not read as map)
+            buf[:, :w] = m
+            f.write(buf.tobytes())
+    r = run(maps_exe, "convert", path, str(h), str(w), str(pitch), "5", "7")
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = np.array([[int(a, 16), int(b, 16), int(v)] for a, b, v in (ln.split() for ln in r.stdout.splitlines())],
+                   np.int64).reshape(h, w, 3)
+    assert np.array_equal(got[..., :2], rc.packed(mx, my, 5, 7))
+    assert np.array_equal(got[..., 2], rc.convert(mx, my, 5, 7)[4])
+    x0, y0, a, b, valid = rc.convert(mx, my, 5, 7)
+    # the cases are really there
+    assert (a[2, 0], b[2, 0]) == (31, 31) and x0[2, 2] == -1 and x0[2, 3] == 6 and y0[3, 0] == -1 and y0[3, 1] == 4
+    assert (a[4] % 2 == 0).all() and (x0[5, :5] == [-32768, 32767, -32768, 32767, -32768]).all()
+    assert valid[0, 0] == 255 and valid[0, 6] == 0 and (valid[5] == 0).all() and 0 < (valid == 255).sum() < h * w
+
+
+def test_argument_checks(maps_exe):
+    r = run(maps_exe, "args")
+    assert r.returncode == 0 and "rectify args ok" in r.stdout, r.stdout + r.stderr
+    lines = dict(ln.split(": ", 1) for ln in r.stdout.splitlines() if ": " in ln)
+    for ok in ("off", "smallest", "largest", "left dense", "right padded"):
+        assert lines[ok] == "accepted", ok
+    for bad in ("rows 0", "cols 0", "rows negative", "cols negative", "rows 32768", "cols 32768", "rows INT_MIN",
+                "off with a map", "sizes without maps", "map 0 NULL", "map 1 NULL", "map 2 NULL", "map 3 NULL",
+                "map_pitch below width", "map_pitch negative", "view 2", "view -1", "src_pitch below src_cols",
+                "dst_pitch below width"):
+        assert lines[bad].startswith("refused: ") and len(lines[bad]) > len("refused: "), bad
+    r = run(maps_exe)
+    assert r.returncode == 64 and "usage" in r.stderr
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    if not os.path.exists(_capi.LIB_PATH):
+        _capi.build()
+    out = str(tmp_path_factory.mktemp("cpp") / "sgm_rectify_surface")
+    libdir = os.path.dirname(_capi.LIB_PATH)
+    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    SURFACE_SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
+                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", out],
+                   check=True, capture_output=True, text=True)
+    return out
+
+
+def test_surface_compiles_and_checks_its_arguments(exe):
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 64 and "usage" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bad_arguments_and_wrong_size_images_are_refused(exe):
+    r = subprocess.run([exe, "bad"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.count("threw as expected") == 8, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_rectify_class_matches_the_python_pipeline(exe, tmp_path):
+    (sh, sw), (h, w, D) = (37, 53), (24, 80, 32)
+    left, right = synthetic.stereo_pair(sh, sw, D, pair_index=5, kind="road")
+    ml, mr = rc.maps(h, w, sh, sw, 0), rc.maps(h, w, sh, sw, 1)
+    rl, rright = rc.remap(left, *ml), rc.remap(right, *mr)
+    with SGM(h, w, 1, D, post_filter=True) as sgm:
+        sgm.process(rl, rright)
+        want = sgm.get_disp()
+    fl, fr, fm, fo = (str(tmp_path / n) for n in ("l.raw", "r.raw", "maps.f32", "out"))
+    left.tofile(fl)
+    right.tofile(fr)
+    np.stack([*ml, *mr]).astype(np.float32).tofile(fm)
+    r = subprocess.run([exe, "run", fl, fr, fm, str(sh), str(sw), str(h), str(w), str(D), fo],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert f"rectified {h} {w} and {h} {w}" in r.stdout, r.stdout
+    got = np.fromfile(fo + ".disp", dtype=np.float32).reshape(h, w)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(np.fromfile(fo + ".left", np.uint8).reshape(h, w), rl)
+    assert np.array_equal(np.fromfile(fo + ".right", np.uint8).reshape(h, w), rright)
+    assert np.array_equal(np.fromfile(fo + ".valid", np.uint8).reshape(h, w), rc.convert(*mr, sh, sw)[4])
