@@ -1,7 +1,8 @@
 // stereo_node.cpp -- the reference ROS node's per-frame flow (node.cpp:25-151)
 // on libsgm_hip.so through the drop-in headers, without ROS or OpenCV:
 //
-//   images (8-bit PGM)            node.cpp:69-70   imread(..., IMREAD_GRAYSCALE)
+//   images (8-bit PGM, or PPM)    node.cpp:69-70   imread(..., IMREAD_GRAYSCALE); a colour pair's
+//                                                  conversion runs on the GPU (set_input_format)
 //   resize to img_w x img_h       node.cpp:75-78   cv::resize on the GPU (HipSolver::resize)
 //   or rectify (MAPS.f32)         (not in the node) cv::remap on the GPU (HipSolver::set_rectify)
 //   sky masks, both views         node.cpp:80-87   SkyAreaDetector::detect
@@ -22,6 +23,12 @@
 // sees HipSolver::remap's images, process() takes the raw pair and every frame
 // begins with the remap, and the cloud reads the rectified left image.
 //
+// LEFT and RIGHT may be binary PPM files (P6, maxval 255) instead: they are read
+// as RGB8, the solver's input format is set to SGM_PIX_RGB8 and process() takes
+// the colour pair -- every frame converts it on the GPU, inside the resize or
+// the remap when one is on.  The sky detector sees HipSolver::gray's images, the
+// debug view and the cloud read the grey image the frame matched.
+//
 // usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX
 //                    [scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32]]]]]
 // min_disp (not in the node): search disparities [min_disp, min_disp + max_disp);
@@ -39,16 +46,18 @@
 using sgm_amd::Mat;
 typedef std::shared_ptr<sky_detector::SkyAreaDetector> SkyDetPtr;  // node.cpp:8
 
-// binary PGM (P5, maxval 255) -> CV_8UC1
+// binary PGM (P5, maxval 255) -> CV_8UC1; binary PPM (P6, maxval 255) -> CV_8UC3 in RGB order
 static bool read_pgm(const std::string &path, Mat &img) {
     std::ifstream f(path, std::ios::binary);
     std::string magic;
     int w = 0, h = 0, maxval = 0;
-    if (!(f >> magic >> w >> h >> maxval) || magic != "P5" || maxval != 255 || w <= 0 || h <= 0)
+    if (!(f >> magic >> w >> h >> maxval) || (magic != "P5" && magic != "P6") || maxval != 255 || w <= 0 ||
+        h <= 0)
         return false;
     f.get();  // the single whitespace after maxval
-    img.create(h, w, CV_8UC1);
-    for (int i = 0; i < h; ++i) f.read(reinterpret_cast<char *>(img.ptr<unsigned char>(i)), w);
+    const int ch = magic == "P6" ? 3 : 1;
+    img.create(h, w, ch == 3 ? CV_8UC3 : CV_8UC1);
+    for (int i = 0; i < h; ++i) f.read(reinterpret_cast<char *>(img.ptr<unsigned char>(i)), (std::streamsize)w * ch);
     return (bool)f;
 }
 
@@ -90,7 +99,7 @@ int main(int argc, char **argv) {
 
     Mat img_l, img_r;
     if (!read_pgm(argv[1], img_l) || !read_pgm(argv[2], img_r) || img_l.rows != img_r.rows ||
-        img_l.cols != img_r.cols) {
+        img_l.cols != img_r.cols || img_l.type() != img_r.type()) {
         std::fprintf(stderr, "cannot read two 8-bit PGM images of one size\n");
         return 2;
     }
@@ -105,6 +114,13 @@ int main(int argc, char **argv) {
     SkyDetPtr sky_det = std::make_shared<sky_detector::SkyAreaDetector>();
 
     Mat raw_l = img_l, raw_r = img_r;  // what process() takes
+    const bool colour = img_l.type() == CV_8UC3;
+    if (colour) {  // a P6 pair: the frame converts it; img_l, img_r (grey) are for the sky detector
+        sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
+        sgm->set_input_format(SGM_PIX_RGB8);
+        sgm->gray(raw_l, img_l, SGM_PIX_RGB8);
+        sgm->gray(raw_r, img_r, SGM_PIX_RGB8);
+    }
     if (argc > 13) {  // rectify instead: the maps are at the configured size
         sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
         Mat maps[4];
@@ -118,18 +134,21 @@ int main(int argc, char **argv) {
             return 2;
         }
         sgm->set_rectify(img_l.rows, img_l.cols, maps[0], maps[1], maps[2], maps[3]);
-        sgm->remap(raw_l, img_l, 0);  // for the sky detector; the frame remaps the raw pair itself
-        sgm->remap(raw_r, img_r, 1);
+        sgm->remap(img_l, img_l, 0);  // for the sky detector; the frame remaps the raw pair itself
+        sgm->remap(img_r, img_r, 1);
         std::printf("rectified left size: %d, %d\n", img_l.rows, img_l.cols);
         std::printf("rectified right size: %d, %d\n", img_r.rows, img_r.cols);
     } else if (argc > 12) {  // node.cpp:75-78, on the GPU
         sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
+        if (colour) sgm->set_input_size(img_l.rows, img_l.cols);  // (the frame resizes the colour pair itself)
         sgm->resize(img_l, img_l);
         sgm->resize(img_r, img_r);
         std::printf("resized left size: %d, %d\n", img_l.rows, img_l.cols);
         std::printf("resized right size: %d, %d\n", img_r.rows, img_r.cols);
-        raw_l = img_l;
-        raw_r = img_r;
+        if (!colour) {
+            raw_l = img_l;
+            raw_r = img_r;
+        }
     }
 
     Mat sky_mask, sky_mask_beta;  // node.cpp:80-87 (no debug image is written)
@@ -160,6 +179,7 @@ int main(int argc, char **argv) {
     int n = 0;
     Mat packed = disp.clone();
     if (argc > 13) img_l = static_cast<sgm_amd::SGM *>(sv.get())->rectified(0);  // what the frame matched
+    else if (colour) img_l = static_cast<sgm_amd::SGM *>(sv.get())->input_gray(0);
     const int rc = sgm_stage_point_cloud(static_cast<sgm_amd::SGM *>(sv.get())->handle(),
                                          packed.ptr<float>(0), img_l.data, (int)img_l.step, &cam,
                                          xyz.data(), pix.data(), &n);

@@ -26,6 +26,11 @@
  *                                rows x cols camera images and rectifies them on the GPU
  *                                first: cv::remap through initUndistortRectifyMap's maps
  *   remap(src, dst, view)        cv::remap(src, dst, map_x, map_y, INTER_LINEAR) on the GPU
+ *   set_input_format(fmt)        (not in the reference) process() takes CV_8UC3 / CV_8UC4 colour
+ *                                images (SGM_PIX_BGR8, ...) and converts them on the GPU first
+ *   gray(src, dst, fmt)          node.cpp:69-70     the decoder's / cvtColor's grey conversion
+ *                                on the GPU, Y = (4899 R + 9617 G + 1868 B + 8192) >> 14
+ *   input_gray(view)             the grey image the last process() matched
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -62,6 +67,9 @@ typedef cv::Vec3b Vec3b;
 #ifndef CV_8UC3
 #define CV_8UC3 16
 #endif
+#ifndef CV_8UC4
+#define CV_8UC4 24
+#endif
 namespace sgm_amd {
 struct Vec3b {
     unsigned char v[3];
@@ -94,7 +102,7 @@ public:
     }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     int type() const { return type_; }
-    int channels() const { return type_ == CV_8UC3 ? 3 : 1; }
+    int channels() const { return type_ == CV_8UC3 ? 3 : (type_ == CV_8UC4 ? 4 : 1); }
     Mat clone() const {  // packed copy (step = cols * elem), row by row as cv::Mat::clone
         Mat m(rows, cols, type_);
         for (int i = 0; i < rows && !empty(); ++i)
@@ -109,7 +117,7 @@ public:
     template <typename T> const T &at(int i, int j) const { return ptr<T>(i)[j]; }
 
 private:
-    static size_t elem_size(int t) { return t == CV_32FC1 ? 4 : (t == CV_8UC3 ? 3 : 1); }
+    static size_t elem_size(int t) { return t == CV_32FC1 || t == CV_8UC4 ? 4 : (t == CV_8UC3 ? 3 : 1); }
     int type_ = -1;
     std::shared_ptr<unsigned char> buf_;
 };
@@ -238,11 +246,14 @@ public:
     }
     virtual void process(Mat &img_l, Mat &img_r) {
         if (img_l.rows != img_r.rows || img_l.cols != img_r.cols || img_l.type() != img_r.type() ||
-            img_l.type() != CV_8UC1 || img_l.rows != in_h_ || img_l.cols != in_w_)
-            fail("process", "inputs must be CV_8UC1 of the constructed size (SGM.cpp:34-38)");
+            img_l.type() != pix_type(format_) || img_l.rows != in_h_ || img_l.cols != in_w_)
+            fail("process", format_ == SGM_PIX_GRAY8
+                                ? "inputs must be CV_8UC1 of the constructed size (SGM.cpp:34-38)"
+                                : "inputs must be CV_8UC3 / CV_8UC4, as the input format says, of the "
+                                  "constructed size");
         this->img_l = img_l;  // shallow, as SGM.cpp:59-60 (decimated on the device)
         this->img_r = img_r;
-        if (resizing_ || rectifying_) {  // checked before any work: the resized images' host copies
+        if (resizing_ || rectifying_ || format_ != SGM_PIX_GRAY8) {  // checked before any work: the grey images' host copies
             resized_[0] = Mat(full_h_, full_w_, CV_8UC1);
             resized_[1] = Mat(full_h_, full_w_, CV_8UC1);
         }
@@ -285,7 +296,41 @@ public:
             this->img_l = resized_[0];
             this->img_r = resized_[1];
         }
+        if (format_ != SGM_PIX_GRAY8 && !resizing_ && !rectifying_) {  // likewise: the converted pair
+            for (int v = 0; v < 2; ++v)
+                if (sgm_stage_input_gray(handle_, v, resized_[v].data) != SGM_OK)
+                    fail("process", sgm_last_error(handle_));
+            this->img_l = resized_[0];
+            this->img_r = resized_[1];
+        }
         if (scale > 1) decimate_left();
+    }
+
+    // The pixel format of the images process() takes (sgm_set_input_format):
+    // SGM_PIX_BGR8 / SGM_PIX_RGB8 take CV_8UC3 Mats, SGM_PIX_BGRA8 /
+    // SGM_PIX_RGBA8 CV_8UC4 ones, and every frame converts them to grey on the
+    // GPU first -- inside the resize or the remap when one is set.
+    // SGM_PIX_GRAY8: off, CV_8UC1 again.
+    void set_input_format(int fmt) {
+        const int rc = sgm_set_input_format(handle_, fmt);
+        sync_input_stage();  // (before failing: a failed allocation leaves the handle's stages off)
+        if (rc != SGM_OK) fail("set_input_format", sgm_last_error(handle_));
+    }
+    // The decoder's grey conversion (node.cpp:69-70 IMREAD_GRAYSCALE; cvtColor)
+    // of a colour image of any size on the GPU (sgm_stage_gray); dst may be src.
+    void gray(const Mat &src, Mat &dst, int fmt) {
+        if (src.empty() || fmt == SGM_PIX_GRAY8 || src.type() != pix_type(fmt))
+            fail("gray", "src must be a CV_8UC3 / CV_8UC4 image, as the colour format says");
+        Mat out(src.rows, src.cols, CV_8UC1);
+        if (sgm_stage_gray(handle_, fmt, src.data, src.rows, src.cols, (int)src.step, out.data) != SGM_OK)
+            fail("gray", sgm_last_error(handle_));
+        dst = out;
+    }
+    // CV_8UC1 at the constructed size: the grey image of `view` (0 left, 1
+    // right) the last process() matched -- converted, and resized or rectified
+    // when those stages are set; empty while the input format is grey
+    const Mat &input_gray(int view) const {
+        return format_ != SGM_PIX_GRAY8 ? resized_[view == 1 ? 1 : 0] : none_;
     }
 
     // cv::resize(src, dst, Size(w, h)) (node.cpp:75-76: 8-bit, one channel,
@@ -427,7 +472,8 @@ private:
     int full_h_, full_w_;    // the constructed size (in_h_, in_w_: what process() takes)
     bool resizing_ = false;  // set_input_size
     bool rectifying_ = false;  // set_rectify
-    Mat resized_[2];         // the resized or rectified pair of the last process()
+    int format_ = SGM_PIX_GRAY8;  // set_input_format
+    Mat resized_[2];         // the resized, rectified or converted pair of the last process()
     Mat none_;
 
     // resizing_, rectifying_ and the size process() takes, read back from the
@@ -441,7 +487,13 @@ private:
         rectifying_ = rc_rows != 0;
         in_h_ = resizing_ ? rs_rows : rectifying_ ? rc_rows : full_h_;
         in_w_ = resizing_ ? rs_cols : rectifying_ ? rc_cols : full_w_;
-        if (!resizing_ && !rectifying_) resized_[0] = resized_[1] = Mat();
+        sgm_get_input_format(handle_, &format_);
+        if (!resizing_ && !rectifying_ && format_ == SGM_PIX_GRAY8) resized_[0] = resized_[1] = Mat();
+    }
+
+    // the Mat type of a pixel format's images
+    static int pix_type(int fmt) {
+        return fmt == SGM_PIX_GRAY8 ? CV_8UC1 : (fmt == SGM_PIX_BGR8 || fmt == SGM_PIX_RGB8 ? CV_8UC3 : CV_8UC4);
     }
 
     void check_mask(const Mat &m, const char *what) const {

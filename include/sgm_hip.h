@@ -301,6 +301,77 @@ int sgm_stage_rectified(sgm_handle *h, int view, uint8_t *img);
  * stereoRectify's validPixROI.  Built on the host when the maps are set. */
 int sgm_stage_rectify_valid(sgm_handle *h, int view, uint8_t *mask);
 
+/* ---- colour input: the decoder's / cvtColor's grey conversion on the GPU ----
+ *
+ * The reference reads its images with imread(..., IMREAD_GRAYSCALE)
+ * (node.cpp:69-70); a colour camera delivers bgr8, rgb8, bgra8 or rgba8.  For
+ * 8-bit pixels, pinned as DESIGN.md 5l states it and bit-exact against
+ * tests/gray_recipe.py:
+ *   Y = (4899 R + 9617 G + 1868 B + 8192) >> 14
+ * the fixed-point form of OpenCV 2.4.13's cvtColor(BGR2GRAY) and of its
+ * decoder's grey conversion (0.299, 0.587, 0.114 at 14 bits, summing to 16384:
+ * R = G = B = v gives v; pure red 76, green 150, blue 29; always in [0, 255]).
+ * The alpha byte of a 4-channel format is ignored.  Later OpenCV releases use
+ * 15-bit coefficients: parity with a particular OpenCV build is not pinned at
+ * this boundary, as for the pre-blur, the resize and the remap.
+ * Channels are interleaved, 1, 3 or 4 bytes per pixel; pitches stay in bytes. */
+enum {
+    SGM_PIX_GRAY8 = 0,
+    SGM_PIX_BGR8 = 1,
+    SGM_PIX_RGB8 = 2,
+    SGM_PIX_BGRA8 = 3,
+    SGM_PIX_RGBA8 = 4
+};
+
+/* The pixel format of the images a frame takes: a property of the handle, like
+ * sgm_set_input_size and sgm_set_rectify (sgm_params and SGM_HIP_VERSION are
+ * unchanged).  SGM_PIX_GRAY8 = off (default): frames run exactly as before.
+ * With a colour format set, sgm_process and sgm_process_device take colour
+ * images of the size the handle's frames take (the full size, the input size or
+ * the maps' source size), pitch >= cols x bytes per pixel; a side-by-side frame
+ * still splits by pitch (right = left + cols x bytes per pixel).  The format may
+ * be set before or after sgm_set_input_size / sgm_set_rectify.  The frame's
+ * first launch then writes handle-owned height x width grey images: with an
+ * input size or maps set it is the same one resize or remap launch, which
+ * converts each tap as it reads it (bit-equal to converting first); with
+ * neither it is one conversion launch more.  Everything inside the frame reads
+ * those images: the census, the in-frame sky detector, the in-frame LKRefine,
+ * the BM solver.  Sky masks and the stand-alone stage calls (sgm_resize_device,
+ * sgm_remap_device, sgm_stage_*, ...) stay one-channel.
+ * Allocates and frees what the format needs -- the two grey images when no
+ * input stage holds them already, the host API's staging of the raw images at
+ * cols x bytes per pixel -- counted in sgm_device_bytes.  Synchronises the
+ * handle's last work first; call it outside stream capture, and re-capture
+ * graphs afterwards.  SGM_ERR_INVALID_ARG, with a message, for an unknown
+ * format and for a colour format on an aux_only handle (it runs no frames); a
+ * refused call changes nothing. */
+int sgm_set_input_format(sgm_handle *h, int fmt);
+int sgm_get_input_format(const sgm_handle *h, int *fmt);
+/* Converts src (rows x cols pixels of the colour format fmt, DEVICE memory,
+ * src_pitch bytes) into dst (rows x cols u8, dst_pitch bytes; padding
+ * untouched).  Pointers and pitches may have any alignment.  One launch on
+ * `stream` (NULL = the handle's stream), no host wait, no allocation:
+ * capturable into a HIP graph.  Any handle serves, aux_only included; the size
+ * is the call's own, from 1 x 1.  SGM_ERR_INVALID_ARG, with a message, for a
+ * NULL pointer, a size below 1, SGM_PIX_GRAY8 or an unknown format, src_pitch <
+ * cols x bytes per pixel or dst_pitch < cols. */
+int sgm_gray_device(sgm_handle *h, int fmt, const uint8_t *d_src, int rows, int cols,
+                    int src_pitch, uint8_t *d_dst, int dst_pitch, void *stream);
+/* The same with HOST buffers (dst dense, rows x cols); synchronous. */
+int sgm_stage_gray(sgm_handle *h, int fmt, const uint8_t *src, int rows, int cols, int src_pitch,
+                   uint8_t *dst);
+/* The last frame's grey image of `view` (SGM_VIEW_LEFT / SGM_VIEW_RIGHT) on a
+ * handle with a colour format: handle-owned DEVICE memory, height x width u8,
+ * *pitch bytes per row; valid until the next frame, a change of the format or
+ * of an input stage, or sgm_destroy.  What the node hands to the point cloud
+ * and to show_disp.  With an input stage set it is the buffer sgm_get_resized /
+ * sgm_get_rectified return (they keep working).  Reads of it are ordered after
+ * the frame on the frame's stream only.  SGM_ERR_INVALID_ARG for a grey handle,
+ * before any frame, for any other view, or a NULL pointer. */
+int sgm_get_input_gray(sgm_handle *h, int view, const uint8_t **d_img, int *pitch);
+/* The same image copied to a HOST buffer (height x width, dense); synchronous. */
+int sgm_stage_input_gray(sgm_handle *h, int view, uint8_t *img);
+
 /* Bytes of device memory the handle holds. */
 size_t sgm_device_bytes(const sgm_handle *h);
 /* The handle's own stream (a hipStream_t; what a NULL stream argument

@@ -44,7 +44,12 @@ EXPORTS = (
     "sgm_get_resized", "sgm_stage_resized",
     "sgm_set_rectify", "sgm_get_rectify", "sgm_remap_device", "sgm_stage_remap",
     "sgm_get_rectified", "sgm_stage_rectified", "sgm_stage_rectify_valid",
+    "sgm_set_input_format", "sgm_get_input_format", "sgm_gray_device", "sgm_stage_gray",
+    "sgm_get_input_gray", "sgm_stage_input_gray",
 )
+# sgm_set_input_format's pixel formats (SGM_PIX_*), by their ROS encoding names
+PIX_FORMATS = {"gray8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4}
+PIX_BYTES = {0: 1, 1: 3, 2: 3, 3: 4, 4: 4}
 SGM_COMM_ID_BYTES = 128
 
 
@@ -170,6 +175,12 @@ def lib():
     L.sgm_get_rectified.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
     L.sgm_stage_rectified.argtypes = [P, I, P]
     L.sgm_stage_rectify_valid.argtypes = [P, I, P]
+    L.sgm_set_input_format.argtypes = [P, I]
+    L.sgm_get_input_format.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_gray_device.argtypes = [P, I, P, I, I, I, P, I, P]
+    L.sgm_stage_gray.argtypes = [P, I, P, I, I, I, P]
+    L.sgm_get_input_gray.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
+    L.sgm_stage_input_gray.argtypes = [P, I, P]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

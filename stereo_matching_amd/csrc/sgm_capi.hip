@@ -115,8 +115,12 @@ void free_all(sgm_handle *h) {
 inline int frame_rows(const sgm_handle *h) { return h->in_rows ? h->in_rows : h->rc_rows ? h->rc_rows : h->p.height; }
 inline int frame_cols(const sgm_handle *h) { return h->in_rows ? h->in_cols : h->rc_rows ? h->rc_cols : h->p.width; }
 
+// bytes per pixel, and per row, of those images (sgm_set_input_format)
+inline int frame_bpp(const sgm_handle *h) { return sgm::pix_bpp(h->fmt); }
+inline int frame_row_bytes(const sgm_handle *h) { return frame_cols(h) * frame_bpp(h); }
+
 int ensure_pinned(sgm_handle *h) {
-    const size_t nin = (size_t)frame_rows(h) * frame_cols(h), npx = (size_t)h->g.H * h->g.W;
+    const size_t nin = (size_t)frame_rows(h) * frame_row_bytes(h), npx = (size_t)h->g.H * h->g.W;
     const size_t need = 2 * nin + 2 * npx + npx * sizeof(float) + npx * sizeof(uint16_t) + 64;
     if (h->h_pin && h->h_pin_bytes >= need) return SGM_OK;
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -503,6 +507,51 @@ int sgm_set_min_disp(sgm_handle *h, int m) {
     return SGM_OK;
 }
 
+// ---- the buffers of the input stages (resize, rectification, colour format)
+
+// Makes d_rs and d_raw fit the handle's input stages as they stand: with an
+// input size, maps (on a handle that runs frames) or a colour format set, the
+// two full-size grey images the frame's first launch writes and the host API's
+// staging of the two raw images at their size and format; with none, neither.
+// Buffers that fit already are kept.  On a failed allocation every input stage
+// is switched off and the handle runs as it did at sgm_create.
+static void rectify_free_maps(sgm_handle *h);
+static int fit_input_buffers(sgm_handle *h) {
+    const bool staged = h->in_rows || (h->rc_rows && !h->p.aux_only) || h->fmt;
+    const size_t nfull = (size_t)h->p.height * h->p.width;
+    const size_t nraw = staged ? (size_t)frame_rows(h) * frame_row_bytes(h) : 0;
+    int rc = SGM_OK;
+    h->rs_valid = false;
+    for (int v = 0; v < 2 && !rc; ++v) {
+        if (!staged) dfree(h, &h->d_rs[v], nfull);
+        else if (!h->d_rs[v]) rc = dalloc(h, &h->d_rs[v], nfull);
+    }
+    if (!rc && nraw != h->raw_bytes) {
+        for (int v = 0; v < 2; ++v) dfree(h, &h->d_raw[v], h->raw_bytes);
+        h->raw_bytes = 0;
+        for (int v = 0; v < 2 && !rc; ++v) rc = dalloc(h, &h->d_raw[v], nraw);
+        if (!rc) h->raw_bytes = nraw;
+    }
+    if (rc) {
+        // (dalloc nulls the pointer it failed on; raw_bytes is still the freed size's 0 or the old one)
+        for (int v = 0; v < 2; ++v) {
+            dfree(h, &h->d_raw[v], h->raw_bytes ? h->raw_bytes : nraw);
+            dfree(h, &h->d_rs[v], nfull);
+        }
+        h->raw_bytes = 0;
+        h->in_rows = h->in_cols = 0;
+        h->fmt = SGM_PIX_GRAY8;
+        rectify_free_maps(h);
+    }
+    return rc;
+}
+
+// The frames' images at format fmt must stay addressable with an int.
+static bool frame_bytes_ok(const sgm_handle *h, int fmt, int rows, int cols) {
+    size_t bytes;
+    return sgm::pix_image_bytes(fmt, rows ? rows : h->p.height, rows ? cols : h->p.width, &bytes);
+}
+
 // ---- input resize (node.cpp:75-76; sgm_resize.hip)
 
 int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols) {
@@ -518,6 +567,9 @@ int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols) {
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_set_input_size: rectification maps are set (sgm_set_rectify): one input "
                        "stage at a time, and the remap resizes too");
+    if (!frame_bytes_ok(h, h->fmt, src_rows, src_cols))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_size: image too large: %d x %d at %d bytes per pixel",
+                       src_rows, src_cols, frame_bpp(h));
     DeviceGuard guard(h->device);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
@@ -526,30 +578,9 @@ int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols) {
     if (src_rows == h->in_rows && src_cols == h->in_cols) return SGM_OK;
     // frames in flight still read the staged and the resized images
     if (int rc = wait_last(h)) return rc;
-    const size_t nfull = (size_t)h->p.height * h->p.width;
-    const size_t nold = (size_t)h->in_rows * h->in_cols, nnew = (size_t)src_rows * src_cols;
-    for (int v = 0; v < 2; ++v) {
-        dfree(h, &h->d_raw[v], nold);
-        if (!src_rows) dfree(h, &h->d_rs[v], nfull);
-    }
-    h->in_rows = h->in_cols = 0;
-    h->rs_valid = false;
-    if (!src_rows) return SGM_OK;
-    int rc = SGM_OK;
-    for (int v = 0; v < 2 && !rc; ++v) {
-        if (!h->d_rs[v]) rc = dalloc(h, &h->d_rs[v], nfull);
-        if (!rc) rc = dalloc(h, &h->d_raw[v], nnew);
-    }
-    if (rc) {  // (off again: the handle runs as before)
-        for (int v = 0; v < 2; ++v) {
-            dfree(h, &h->d_raw[v], nnew);
-            dfree(h, &h->d_rs[v], nfull);
-        }
-        return rc;
-    }
     h->in_rows = src_rows;
     h->in_cols = src_cols;
-    return SGM_OK;
+    return fit_input_buffers(h);
 }
 
 int sgm_get_input_size(const sgm_handle *h, int *src_rows, int *src_cols) {
@@ -633,19 +664,21 @@ int sgm_stage_resize(sgm_handle *h, const uint8_t *src, int src_rows, int src_co
 
 // ---- rectification (sgm_rectify.hip, sgm_rectify_maps.h)
 
-// Frees what sgm_set_rectify allocated and switches it off.
-static void rectify_off(sgm_handle *h) {
-    const size_t nfull = (size_t)h->p.height * h->p.width, nsrc = (size_t)h->rc_rows * h->rc_cols;
+// Frees the maps and the masks and switches the remap off (the images follow
+// in fit_input_buffers).
+static void rectify_free_maps(sgm_handle *h) {
+    const size_t nfull = (size_t)h->p.height * h->p.width;
     for (int v = 0; v < 2; ++v) {
         dfree(h, &h->d_map[v], 2 * nfull);
-        if (!h->p.aux_only) {
-            dfree(h, &h->d_raw[v], nsrc);
-            dfree(h, &h->d_rs[v], nfull);
-        }
         std::vector<uint8_t>().swap(h->valid[v]);
     }
     h->rc_rows = h->rc_cols = 0;
-    h->rs_valid = false;
+}
+
+// Frees what sgm_set_rectify allocated and switches it off.
+static int rectify_off(sgm_handle *h) {
+    rectify_free_maps(h);
+    return fit_input_buffers(h);
 }
 
 int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_x_l, const float *map_y_l,
@@ -659,6 +692,9 @@ int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_set_rectify: an input size is set (sgm_set_input_size): one input stage at "
                        "a time, and the remap resizes too");
+    if (!frame_bytes_ok(h, h->fmt, src_rows, src_cols))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_rectify: image too large: %d x %d at %d bytes per pixel",
+                       src_rows, src_cols, frame_bpp(h));
     DeviceGuard guard(h->device);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
@@ -667,13 +703,10 @@ int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_
     if (!src_rows && !h->rc_rows) return SGM_OK;
     // frames in flight still read the maps, the staged and the rectified images
     if (int rc = wait_last(h)) return rc;
-    rectify_off(h);
-    if (!src_rows) return SGM_OK;
-    const size_t nfull = (size_t)h->p.height * h->p.width, nsrc = (size_t)src_rows * src_cols;
-    h->rc_rows = src_rows;  // (rectify_off frees by these sizes on a failure below)
-    h->rc_cols = src_cols;
+    int rc = rectify_off(h);
+    if (rc || !src_rows) return rc;
+    const size_t nfull = (size_t)h->p.height * h->p.width;
     std::vector<uint32_t> packed;
-    int rc = SGM_OK;
     try {
         packed.resize(2 * nfull);
         for (int v = 0; v < 2; ++v) h->valid[v].resize(nfull);
@@ -687,14 +720,15 @@ int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_
         if (hipMemcpy(h->d_map[v], packed.data(), 2 * nfull * sizeof(uint32_t), hipMemcpyHostToDevice) !=
             hipSuccess)
             rc = set_err(h, SGM_ERR_HIP, "sgm_set_rectify: the upload of the packed map failed");
-        // (an aux_only handle runs no frames: it keeps the maps for sgm_remap_device alone)
-        if (!rc && !h->p.aux_only) {
-            if ((rc = dalloc(h, &h->d_rs[v], nfull))) break;
-            rc = dalloc(h, &h->d_raw[v], nsrc);
-        }
     }
-    if (rc) rectify_off(h);  // (off again: the handle runs as before)
-    return rc;
+    if (rc) {  // (off again: the handle runs as before)
+        (void)rectify_off(h);
+        return rc;
+    }
+    // (an aux_only handle runs no frames: it keeps the maps for sgm_remap_device alone)
+    h->rc_rows = src_rows;
+    h->rc_cols = src_cols;
+    return fit_input_buffers(h);
 }
 
 int sgm_get_rectify(const sgm_handle *h, int *src_rows, int *src_cols) {
@@ -785,6 +819,109 @@ int sgm_stage_rectify_valid(sgm_handle *h, int view, uint8_t *mask) {
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: view must be 0 (left) or 1 (right), got %d",
                        view);
     memcpy(mask, h->valid[view].data(), h->valid[view].size());
+    return SGM_OK;
+}
+
+// ---- colour input (sgm_gray.hip, sgm_pix.h, sgm_gray_args.h)
+
+int sgm_set_input_format(sgm_handle *h, int fmt) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!input_format_ok(fmt, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_format: %s", why);
+    if (h->p.aux_only && fmt != SGM_PIX_GRAY8)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_input_format: an aux_only handle runs no frames (sgm_gray_device takes "
+                       "its format per call)");
+    if (!frame_bytes_ok(h, fmt, frame_rows(h), frame_cols(h)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_format: image too large: %d x %d at %d bytes per pixel",
+                       frame_rows(h), frame_cols(h), sgm::pix_bpp(fmt));
+    DeviceGuard guard(h->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_format: call it outside stream capture");
+    if (fmt == h->fmt) return SGM_OK;
+    // frames in flight still read the staged and the grey images
+    if (int rc = wait_last(h)) return rc;
+    h->fmt = fmt;
+    return fit_input_buffers(h);
+}
+
+int sgm_get_input_format(const sgm_handle *h, int *fmt) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (fmt) *fmt = h->fmt;
+    return SGM_OK;
+}
+
+int sgm_gray_device(sgm_handle *h, int fmt, const uint8_t *d_src, int rows, int cols, int src_pitch,
+                    uint8_t *d_dst, int dst_pitch, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!d_src || !d_dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_gray_device: NULL pointer");
+    if (!gray_call_ok(fmt, rows, cols, src_pitch, dst_pitch, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_gray_device: %s", why);
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "gray", (double)rows * cols, st, [&] {
+               return sgm::launch_gray(fmt, &d_src, rows, cols, src_pitch, &d_dst, dst_pitch, 1, st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_stage_gray(sgm_handle *h, int fmt, const uint8_t *src, int rows, int cols, int src_pitch,
+                   uint8_t *dst) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    char why[160];
+    if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_gray: NULL pointer");
+    if (!gray_call_ok(fmt, rows, cols, src_pitch, cols, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_gray: %s", why);
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    const size_t row = (size_t)cols * sgm::pix_bpp(fmt), npx = (size_t)rows * cols;
+    int rc;
+    {
+        // staging: the source and the result in stream-ordered temporaries (any size serves)
+        StreamTemp<uint8_t> d_src(h->st), d_dst(h->st);
+        HIPCHK(h, hipMallocAsync((void **)&d_src.p, row * rows, h->st));
+        HIPCHK(h, hipMallocAsync((void **)&d_dst.p, npx, h->st));
+        HIPCHK(h, hipMemcpy2DAsync(d_src.p, row, src, (size_t)src_pitch, row, (size_t)rows,
+                                   hipMemcpyHostToDevice, h->st));
+        rc = sgm_gray_device(h, fmt, d_src.p, rows, cols, (int)row, d_dst.p, cols, h->st);
+        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, d_dst.p, npx, hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return rc;
+}
+
+int sgm_get_input_gray(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!d_img || !pitch) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_input_gray: NULL pointer");
+    if (!h->fmt)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_get_input_gray: the input format is grey (sgm_set_input_format): the frame reads "
+                       "the caller's images");
+    // (every frame handle's census reads both images, so both are converted)
+    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_input_gray: the handle reads no image of view %d", view);
+    if (!h->rs_valid)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_input_gray: no frame has run since the format was set");
+    *d_img = h->d_rs[view];
+    *pitch = h->p.width;
+    return SGM_OK;
+}
+
+int sgm_stage_input_gray(sgm_handle *h, int view, uint8_t *img) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!img) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_input_gray: NULL pointer");
+    const uint8_t *d_img = nullptr;
+    int pitch = 0;
+    if (int rc = sgm_get_input_gray(h, view, &d_img, &pitch)) return rc;
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, nullptr);
+    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     return SGM_OK;
 }
 
@@ -901,7 +1038,7 @@ int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_ri
                        float *d_out, int out_pitch, uint16_t *d_raw_disp, void *stream) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (int rc = check_frame_err(h)) return rc;
-    if (!d_left || !d_right || !d_out || pitch < frame_cols(h) || out_pitch < h->g.W ||
+    if (!d_left || !d_right || !d_out || pitch < frame_row_bytes(h) || out_pitch < h->g.W ||
         ((d_sky_l || d_sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: bad pointer or pitch");
     if (h->p.aux_only)
@@ -916,7 +1053,7 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
                 const uint8_t *sky_l, const uint8_t *sky_r, int sky_pitch, float *out,
                 int out_pitch, uint16_t *raw_disp) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (!left || !right || !out || pitch < frame_cols(h) || out_pitch < h->g.W ||
+    if (!left || !right || !out || pitch < frame_row_bytes(h) || out_pitch < h->g.W ||
         ((sky_l || sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: bad pointer or pitch");
     if (h->p.aux_only)
@@ -926,9 +1063,10 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
     if ((rc = ensure_pinned(h))) return rc;
-    // (with an input size or maps set the raw images are staged and the frame resizes or remaps them)
-    const int in_h = frame_rows(h), in_w = frame_cols(h);
-    uint8_t *const *d_in = h->in_rows || h->rc_rows ? h->d_raw : h->d_in;
+    // (with an input size, maps or a colour format set the raw images are staged and the frame
+    // resizes, remaps or converts them; in_w: their bytes per row)
+    const int in_h = frame_rows(h), in_w = frame_row_bytes(h);
+    uint8_t *const *d_in = h->in_rows || h->rc_rows || h->fmt ? h->d_raw : h->d_in;
     const size_t nin = (size_t)in_h * in_w, npx = (size_t)h->g.H * h->g.W;
     uint8_t *pl = h->h_pin, *pr = pl + nin, *psl = pr + nin, *psr = psl + npx;
     float *pout = reinterpret_cast<float *>(psr + npx + (16 - (size_t)(psr + npx) % 16) % 16);

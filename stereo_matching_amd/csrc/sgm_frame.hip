@@ -568,7 +568,7 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
         const uint8_t *src[2] = {f.left, f.right};
         HIPCHK(h, timed(h, "resize", 2.0 * h->p.height * h->p.width, st, [&] {
                    return sgm::launch_resize(src, h->in_rows, h->in_cols, f.pitch, h->d_rs, h->p.height,
-                                             h->p.width, h->p.width, 2, st);
+                                             h->p.width, h->p.width, 2, st, h->fmt);
                }));
         f.left = h->d_rs[0];
         f.right = h->d_rs[1];
@@ -580,7 +580,19 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
         const uint8_t *src[2] = {f.left, f.right};
         HIPCHK(h, timed(h, "rectify", 2.0 * h->p.height * h->p.width, st, [&] {
                    return sgm::launch_rectify(src, h->rc_rows, h->rc_cols, f.pitch, h->d_map, h->d_rs,
-                                              h->p.height, h->p.width, h->p.width, 2, st);
+                                              h->p.height, h->p.width, h->p.width, 2, st, h->fmt);
+               }));
+        f.left = h->d_rs[0];
+        f.right = h->d_rs[1];
+        f.pitch = h->p.width;
+        h->rs_valid = true;
+    } else if (h->fmt) {
+        // a colour format with neither: one launch converts both images (with a
+        // resize or a remap set that launch converts its taps itself)
+        const uint8_t *src[2] = {f.left, f.right};
+        HIPCHK(h, timed(h, "gray", 2.0 * h->p.height * h->p.width, st, [&] {
+                   return sgm::launch_gray(h->fmt, src, h->p.height, h->p.width, f.pitch, h->d_rs,
+                                           h->p.width, 2, st);
                }));
         f.left = h->d_rs[0];
         f.right = h->d_rs[1];

@@ -53,6 +53,11 @@ struct sgm_handle {
                           //   in d_raw like the resize's (aux_only handles: the maps alone)
     uint32_t *d_map[2];   //   each view's packed map, two words per full-size pixel (sgm_rectify_maps.h)
     std::vector<uint8_t> valid[2];  //   each view's valid mask (host, full size, dense)
+    int fmt;              // sgm_set_input_format: the pixel format of the images frames take
+                          //   (SGM_PIX_GRAY8 = 0: off).  A colour format makes the resize or the remap
+                          //   convert its taps, or with neither set a launch of its own convert the
+                          //   images, into d_rs; d_raw then stages cols x bytes per pixel per row
+    size_t raw_bytes;     // bytes of each d_raw (0: none): fit_input_buffers, sgm_capi.hip
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sgm_gray_args.h"
 #include "sgm_rectify_maps.h"
 #include "sgm_resize_args.h"
 
@@ -294,16 +295,24 @@ hipError_t launch_sky_detect(const uint8_t *const *img, int pitch, uint8_t *cons
 // The node's cv::resize (node.cpp:75-76; sgm_resize.hip) of nviews
 // (1 or 2) u8 images of one size in one launch: src[v] src_rows x src_cols
 // (src_pitch bytes) -> dst[v] dst_rows x dst_cols (dst_pitch bytes, padding untouched).
+// fmt: the source's pixel format (SGM_PIX_*; a colour source is converted to
+// grey tap by tap), dst is always one channel.
 hipError_t launch_resize(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
                          uint8_t *const *dst, int dst_rows, int dst_cols, int dst_pitch, int nviews,
-                         hipStream_t st);
+                         hipStream_t st, int fmt = 0);
 // The rectification remap (sgm_rectify.hip) of nviews (1 or 2) u8
 // images of one size in one launch: src[v] src_rows x src_cols (src_pitch
 // bytes) sampled through map[v] (dst_rows x dst_cols packed entries of two
 // words, sgm_rectify_maps.h) -> dst[v] (dst_pitch bytes, padding untouched).
+// fmt: the source's pixel format, as launch_resize's.
 hipError_t launch_rectify(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
                           const uint32_t *const *map, uint8_t *const *dst, int dst_rows, int dst_cols,
-                          int dst_pitch, int nviews, hipStream_t st);
+                          int dst_pitch, int nviews, hipStream_t st, int fmt = 0);
+// Colour to grey (sgm_gray.hip) of nviews (1 or 2) images of one
+// size in one launch: src[v] rows x cols pixels of a colour format fmt
+// (src_pitch bytes) -> dst[v] rows x cols u8 (dst_pitch bytes, padding untouched).
+hipError_t launch_gray(int fmt, const uint8_t *const *src, int rows, int cols, int src_pitch,
+                       uint8_t *const *dst, int dst_pitch, int nviews, hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

@@ -16,7 +16,13 @@
 // contiguous bytes; a rectification map is smooth, so a wave's four byte
 // gathers fall in a few cache lines of two source rows.  A tap outside the
 // source issues no load.  Nothing is read back, allocated or copied per call.
+//
+// The kernel is a template over the source's pixel format (sgm_pix.h, DESIGN.md
+// 5l): a colour source's taps are converted to grey as they are read, which is
+// bit-equal to remapping the converted image (a tap outside is still 0 and
+// still issues no load); format 0 (grey) is the plain byte load.
 #include "sgm_device.h"
+#include "sgm_pix.h"
 
 namespace sgm {
 namespace {
@@ -30,8 +36,10 @@ struct RectifyViews {
     uint8_t *dst[2];
 };
 
+template <int F>
 __global__ __launch_bounds__(256) void rectify_kernel(RectifyViews rv, int sh, int sw, int sp, int dh,
                                                       int dw, int dp) {
+    constexpr int bpp = Pix<F>::bpp;
     const int z = (int)__builtin_amdgcn_workgroup_id_z();
     const uint8_t *__restrict__ src = rv.src[z];
     const uint2 *__restrict__ map = rv.map[z];
@@ -58,12 +66,12 @@ __global__ __launch_bounds__(256) void rectify_kernel(RectifyViews rv, int sh, i
         const bool in_x0 = (unsigned)x0 < (unsigned)sw, in_x1 = (unsigned)(x0 + 1) < (unsigned)sw;
         const bool in_y0 = (unsigned)y0 < (unsigned)sh, in_y1 = (unsigned)(y0 + 1) < (unsigned)sh;
         // the tap's offset as an integer: the source is indexed under the tap's own test only
-        const long long o = (long long)y0 * sp + x0;
+        const long long o = (long long)y0 * sp + x0 * bpp;
         int s00 = 0, s01 = 0, s10 = 0, s11 = 0;
-        if (in_y0 && in_x0) s00 = src[o];
-        if (in_y0 && in_x1) s01 = src[o + 1];
-        if (in_y1 && in_x0) s10 = src[o + sp];
-        if (in_y1 && in_x1) s11 = src[o + sp + 1];
+        if (in_y0 && in_x0) s00 = gray_px<F>(src + o);
+        if (in_y0 && in_x1) s01 = gray_px<F>(src + o + bpp);
+        if (in_y1 && in_x0) s10 = gray_px<F>(src + o + sp);
+        if (in_y1 && in_x1) s11 = gray_px<F>(src + o + sp + bpp);
         const int v = ((32 - a) * (32 - b) * s00 + a * (32 - b) * s01 + (32 - a) * b * s10 + a * b * s11 + 512) >> 10;
         dst[(size_t)dy * dp + dx] = (uint8_t)v;
     }
@@ -73,7 +81,7 @@ __global__ __launch_bounds__(256) void rectify_kernel(RectifyViews rv, int sh, i
 
 hipError_t launch_rectify(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
                           const uint32_t *const *map, uint8_t *const *dst, int dst_rows, int dst_cols,
-                          int dst_pitch, int nviews, hipStream_t st) {
+                          int dst_pitch, int nviews, hipStream_t st, int fmt) {
     RectifyViews rv{};
     for (int v = 0; v < nviews; ++v) {
         rv.src[v] = src[v];
@@ -82,8 +90,11 @@ hipError_t launch_rectify(const uint8_t *const *src, int src_rows, int src_cols,
     }
     const dim3 grid((unsigned)((dst_cols + kRectifyCols - 1) / kRectifyCols),
                     (unsigned)((dst_rows + kRectifyRows - 1) / kRectifyRows), (unsigned)nviews);
-    hipLaunchKernelGGL(rectify_kernel, grid, dim3(256), 0, st, rv, src_rows, src_cols, src_pitch,
-                       dst_rows, dst_cols, dst_pitch);
+#define SGM_RECTIFY_LAUNCH(F)                                                                        \
+    hipLaunchKernelGGL(rectify_kernel<F>, grid, dim3(256), 0, st, rv, src_rows, src_cols, src_pitch, \
+                       dst_rows, dst_cols, dst_pitch)
+    SGM_PIX_DISPATCH(fmt, SGM_RECTIFY_LAUNCH);
+#undef SGM_RECTIFY_LAUNCH
     return hipGetLastError();
 }
 

@@ -16,7 +16,13 @@
 // coefficients once (gfx950 runs fp64 at the fp32 rate; -ffp-contract=off
 // keeps the expression unfused), each wave walks 4 rows whose coefficients are
 // wave-uniform.  Nothing is read back, allocated or copied per call.
+//
+// The kernel is a template over the source's pixel format (sgm_pix.h, DESIGN.md
+// 5l): a colour source's taps are converted to grey as they are read, which is
+// bit-equal to resizing the converted image; format 0 (grey) is the plain byte
+// load.
 #include "sgm_device.h"
+#include "sgm_pix.h"
 
 namespace sgm {
 namespace {
@@ -43,9 +49,11 @@ __device__ __forceinline__ void resize_coef(int d, double scale, int n, int &s, 
     c1 = sat_s16((int)rintf(f * 2048.f));
 }
 
+template <int F>
 __global__ __launch_bounds__(256) void resize_kernel(ResizeViews rv, int sh, int sw, int sp, int dh,
                                                      int dw, int dp, double scale_x, double scale_y,
                                                      int half) {
+    constexpr int bpp = Pix<F>::bpp;
     const int z = (int)__builtin_amdgcn_workgroup_id_z();
     const uint8_t *__restrict__ src = rv.src[z];
     uint8_t *__restrict__ dst = rv.dst[z];
@@ -58,8 +66,9 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeViews rv, int sh, int
         for (int r = 0; r < 4; ++r) {
             const int dy = y0 + r;
             if (dy >= dh) break;
-            const uint8_t *a = src + (size_t)(2 * dy) * sp + 2 * dx, *b = a + sp;
-            dst[(size_t)dy * dp + dx] = (uint8_t)(((int)a[0] + a[1] + b[0] + b[1] + 2) >> 2);
+            const uint8_t *a = src + (size_t)(2 * dy) * sp + 2 * dx * bpp, *b = a + sp;
+            dst[(size_t)dy * dp + dx] =
+                (uint8_t)((gray_px<F>(a) + gray_px<F>(a + bpp) + gray_px<F>(b) + gray_px<F>(b + bpp) + 2) >> 2);
         }
         return;
     }
@@ -75,11 +84,11 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeViews rv, int sh, int
         b0 = uniform(b0);
         b1 = uniform(b1);
         const int sy1 = sy + 1 < sh ? sy + 1 : sh - 1;
-        const uint8_t *p0 = src + (size_t)sy * sp + sx, *p1 = src + (size_t)sy1 * sp + sx;
-        int h0 = (int)p0[0] * a0, h1 = (int)p1[0] * a0;
+        const uint8_t *p0 = src + (size_t)sy * sp + sx * bpp, *p1 = src + (size_t)sy1 * sp + sx * bpp;
+        int h0 = gray_px<F>(p0) * a0, h1 = gray_px<F>(p1) * a0;
         if (a1 != 0) {  // (the clamped right edge reads no pixel past the row)
-            h0 += (int)p0[1] * a1;
-            h1 += (int)p1[1] * a1;
+            h0 += gray_px<F>(p0 + bpp) * a1;
+            h1 += gray_px<F>(p1 + bpp) * a1;
         }
         const int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
         dst[(size_t)dy * dp + dx] = (uint8_t)v;
@@ -90,7 +99,7 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeViews rv, int sh, int
 
 hipError_t launch_resize(const uint8_t *const *src, int src_rows, int src_cols, int src_pitch,
                          uint8_t *const *dst, int dst_rows, int dst_cols, int dst_pitch, int nviews,
-                         hipStream_t st) {
+                         hipStream_t st, int fmt) {
     ResizeViews rv{};
     for (int v = 0; v < nviews; ++v) {
         rv.src[v] = src[v];
@@ -99,8 +108,11 @@ hipError_t launch_resize(const uint8_t *const *src, int src_rows, int src_cols, 
     const ResizeScale sc = resize_scale(src_rows, src_cols, dst_rows, dst_cols);
     const dim3 grid((unsigned)((dst_cols + kResizeCols - 1) / kResizeCols),
                     (unsigned)((dst_rows + kResizeRows - 1) / kResizeRows), (unsigned)nviews);
-    hipLaunchKernelGGL(resize_kernel, grid, dim3(256), 0, st, rv, src_rows, src_cols, src_pitch,
-                       dst_rows, dst_cols, dst_pitch, sc.x, sc.y, sc.half);
+#define SGM_RESIZE_LAUNCH(F)                                                                        \
+    hipLaunchKernelGGL(resize_kernel<F>, grid, dim3(256), 0, st, rv, src_rows, src_cols, src_pitch, \
+                       dst_rows, dst_cols, dst_pitch, sc.x, sc.y, sc.half)
+    SGM_PIX_DISPATCH(fmt, SGM_RESIZE_LAUNCH);
+#undef SGM_RESIZE_LAUNCH
     return hipGetLastError();
 }
 

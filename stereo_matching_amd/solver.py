@@ -40,6 +40,21 @@ def _u8(a, shape, what):
     return a
 
 
+_FMT_NAMES = {v: k for k, v in _capi.PIX_FORMATS.items()}
+
+
+def _fmt_code(fmt) -> int:
+    """SGM_PIX_* of a format name; an integer passes through (the library
+    refuses one it does not know)."""
+    if isinstance(fmt, str):
+        if fmt not in _capi.PIX_FORMATS:
+            raise ValueError(f"input format must be one of {sorted(_capi.PIX_FORMATS)}, got {fmt!r}")
+        return _capi.PIX_FORMATS[fmt]
+    if fmt is None:
+        return 0
+    return int(fmt)
+
+
 class SGM:
     """Semi-global matcher on one MI355X (HIP device `device`).
 
@@ -54,7 +69,8 @@ class SGM:
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
-                 input_size=None, rectify=None, _solver: int = _capi.SGM_SOLVER_SGM):
+                 input_size=None, rectify=None, input_format: str = "gray8",
+                 _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
         # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
@@ -116,8 +132,14 @@ class SGM:
         # rectify = (src_h, src_w, mapx_l, mapy_l, mapx_r, mapy_r): process()
         # takes raw src_h x src_w camera images and the frame remaps them
         # through the h x w float maps first (set_rectify); not with input_size
-        self.in_h, self.in_w = h, w
+        # input_format ("gray8" | "bgr8" | "rgb8" | "bgra8" | "rgba8"): process()
+        # takes (in_h, in_w, channels) colour images and the frame converts
+        # them to grey on the GPU first, inside the resize or the remap when one
+        # is set (set_input_format)
+        self.in_h, self.in_w, self.in_ch = h, w, 1
         try:
+            if _fmt_code(input_format):
+                self.set_input_format(input_format)
             if post_filter_launches:
                 self.set_post_filter_launches(post_filter_launches)
             if confidence:
@@ -162,8 +184,9 @@ class SGM:
     # ------------------------------------------------------------ process
     def process(self, img_l, img_r, sky_mask=None, sky_mask_beta=None) -> None:
         """SGM::process (src/SGM.cpp:32-826, sky overload :829-834)."""
-        l = _u8(img_l, (self.in_h, self.in_w), "img_l")
-        r = _u8(img_r, (self.in_h, self.in_w), "img_r")
+        shape = (self.in_h, self.in_w) if self.in_ch == 1 else (self.in_h, self.in_w, self.in_ch)
+        l = _u8(img_l, shape, "img_l")
+        r = _u8(img_r, shape, "img_r")
         sl = None if sky_mask is None or np.size(sky_mask) == 0 else \
             _u8(sky_mask, (self.rows, self.cols), "sky_mask")
         sr = None if sky_mask_beta is None or np.size(sky_mask_beta) == 0 else \
@@ -175,7 +198,7 @@ class SGM:
         # would alias the previous frame's result).
         out = np.empty((self.rows, self.cols), np.float32)
         raw = np.empty((self.rows, self.cols), np.uint16)
-        check(self._lib.sgm_process(self._h, _ptr(l), _ptr(r), self.in_w, _ptr(sl), _ptr(sr),
+        check(self._lib.sgm_process(self._h, _ptr(l), _ptr(r), self.in_w * self.in_ch, _ptr(sl), _ptr(sr),
                                     self.cols, _ptr(out), self.cols, _ptr(raw)),
               self._h)
         self._raw = raw
@@ -189,9 +212,10 @@ class SGM:
                        out_pitch: int | None = None, d_raw: int = 0, stream: int | None = None) -> None:
         """Device-pointer variant (sgm_process_device): enqueue on `stream`
         (None: the handle's own stream; a torch stream's `cuda_stream`,
-        including 0 for torch's default stream: that stream)."""
+        including 0 for torch's default stream: that stream).  pitch: bytes per
+        image row, by default in_w x the input format's bytes per pixel."""
         check(self._lib.sgm_process_device(
-            self._h, ctypes.c_void_p(d_left), ctypes.c_void_p(d_right), pitch or self.in_w,
+            self._h, ctypes.c_void_p(d_left), ctypes.c_void_p(d_right), pitch or self.in_w * self.in_ch,
             ctypes.c_void_p(d_sky_l or None), ctypes.c_void_p(d_sky_r or None),
             sky_pitch or self.cols, ctypes.c_void_p(d_out), out_pitch or self.cols,
             ctypes.c_void_p(d_raw or None), _stream(stream)), self._h)
@@ -217,6 +241,7 @@ class SGM:
         if not rows:
             rows, cols = self.rectify_size
         self.in_h, self.in_w = (rows, cols) if rows else (self.h, self.w)
+        self.in_ch = _capi.PIX_BYTES[_fmt_code(self.input_format)]
 
     @property
     def input_size(self):
@@ -316,6 +341,60 @@ class SGM:
         where all four taps of the pixel lie inside the raw image, else 0."""
         out = np.empty((self.h, self.w), np.uint8)
         check(self._lib.sgm_stage_rectify_valid(self._h, int(view), _ptr(out)), self._h)
+        return out
+
+    # ------------------------------------------------------- colour input
+    def set_input_format(self, fmt: str) -> None:
+        """sgm_set_input_format: process() / process_device() take images of
+        the pixel format `fmt` ("bgr8", "rgb8", "bgra8", "rgba8": interleaved,
+        (in_h, in_w, 3 or 4) arrays; "gray8": off, one channel again).  The
+        frame's first launch converts them, Y = (4899 R + 9617 G + 1868 B +
+        8192) >> 14: inside the resize or the remap when one is
+        set, else as one launch of its own.  Not inside stream capture;
+        re-capture graphs."""
+        try:
+            check(self._lib.sgm_set_input_format(self._h, _fmt_code(fmt)), self._h)
+        finally:
+            self._sync_input_shape()
+
+    @property
+    def input_format(self) -> str:
+        """The pixel format of the images process() takes ("gray8": one channel)."""
+        f = ctypes.c_int()
+        check(self._lib.sgm_get_input_format(self._h, ctypes.byref(f)), self._h)
+        return _FMT_NAMES[f.value]
+
+    def gray(self, img, fmt: str) -> np.ndarray:
+        """A colour image of any size as grey on the GPU (sgm_stage_gray):
+        (rows, cols, 3 or 4) uint8 -> rows x cols uint8."""
+        code = _fmt_code(fmt)
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        bpp = _capi.PIX_BYTES[code]
+        if a.ndim != 3 or a.shape[2] != bpp:
+            raise ValueError(f"img: expected a (rows, cols, {bpp}) image for {fmt!r}, got shape {a.shape}")
+        out = np.empty(a.shape[:2], np.uint8)
+        check(self._lib.sgm_stage_gray(self._h, code, _ptr(a), a.shape[0], a.shape[1],
+                                       a.shape[1] * bpp, _ptr(out)), self._h)
+        return out
+
+    def gray_device(self, fmt: str, d_src: int, rows: int, cols: int, d_dst: int, *,
+                    src_pitch: int | None = None, dst_pitch: int | None = None,
+                    stream: int | None = None) -> None:
+        """The same on device buffers (sgm_gray_device: one launch, enqueue
+        only, capturable)."""
+        code = _fmt_code(fmt)
+        check(self._lib.sgm_gray_device(
+            self._h, code, ctypes.c_void_p(d_src or None), int(rows), int(cols),
+            cols * _capi.PIX_BYTES.get(code, 1) if src_pitch is None else src_pitch,
+            ctypes.c_void_p(d_dst or None), cols if dst_pitch is None else dst_pitch,
+            _stream(stream)), self._h)
+
+    def input_gray(self, view: int = 0) -> np.ndarray:
+        """The last frame's grey image of `view` (0 = left, 1 = right) on a
+        handle with a colour format: h x w uint8, a host copy
+        (sgm_stage_input_gray).  What the point cloud and show_disp read."""
+        out = np.empty((self.h, self.w), np.uint8)
+        check(self._lib.sgm_stage_input_gray(self._h, int(view), _ptr(out)), self._h)
         return out
 
     def check(self) -> None:
@@ -552,11 +631,12 @@ class BM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
-                 post_filter_launches: int = 0, input_size=None, rectify=None):
+                 post_filter_launches: int = 0, input_size=None, rectify=None,
+                 input_format: str = "gray8"):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
                          post_filter_launches=post_filter_launches, input_size=input_size,
-                         rectify=rectify, _solver=_capi.SGM_SOLVER_BM)
+                         rectify=rectify, input_format=input_format, _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -569,7 +649,8 @@ class GPU_SGM(SGM):
     approximations."""
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
-                 post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None):
+                 post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None,
+                 input_format: str = "gray8"):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
                          post_filter_launches=post_filter_launches, min_disp=min_disp,
-                         input_size=input_size, rectify=rectify)
+                         input_size=input_size, rectify=rectify, input_format=input_format)
