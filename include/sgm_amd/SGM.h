@@ -253,7 +253,7 @@ public:
                                   "constructed size");
         this->img_l = img_l;  // shallow, as SGM.cpp:59-60 (decimated on the device)
         this->img_r = img_r;
-        if (resizing_ || rectifying_ || format_ != SGM_PIX_GRAY8) {  // checked before any work: the grey images' host copies
+        if (staging()) {  // checked before any work: the grey images' host copies
             resized_[0] = Mat(full_h_, full_w_, CV_8UC1);
             resized_[1] = Mat(full_h_, full_w_, CV_8UC1);
         }
@@ -280,26 +280,14 @@ public:
         if (confidence_on_ &&
             sgm_stage_confidence(handle_, SGM_VIEW_LEFT, confidence_.template ptr<float>(0)) != SGM_OK)
             fail("process", sgm_last_error(handle_));
-        if (resizing_) {
-            // what the frame matched: the node's resized img_l / img_r (node.cpp:75-76),
-            // for show_disp and the point cloud (node.cpp:107,138)
+        if (staging()) {
+            // what the frame matched: the node's resized img_l / img_r (node.cpp:75-76), the
+            // rectified or the converted pair, for show_disp and the point cloud (node.cpp:107,138)
+            const auto stage = resizing_     ? sgm_stage_resized
+                               : rectifying_ ? sgm_stage_rectified
+                                             : sgm_stage_input_gray;
             for (int v = 0; v < 2; ++v)
-                if (sgm_stage_resized(handle_, v, resized_[v].data) != SGM_OK)
-                    fail("process", sgm_last_error(handle_));
-            this->img_l = resized_[0];
-            this->img_r = resized_[1];
-        }
-        if (rectifying_) {  // likewise: the rectified pair the frame matched
-            for (int v = 0; v < 2; ++v)
-                if (sgm_stage_rectified(handle_, v, resized_[v].data) != SGM_OK)
-                    fail("process", sgm_last_error(handle_));
-            this->img_l = resized_[0];
-            this->img_r = resized_[1];
-        }
-        if (format_ != SGM_PIX_GRAY8 && !resizing_ && !rectifying_) {  // likewise: the converted pair
-            for (int v = 0; v < 2; ++v)
-                if (sgm_stage_input_gray(handle_, v, resized_[v].data) != SGM_OK)
-                    fail("process", sgm_last_error(handle_));
+                if (stage(handle_, v, resized_[v].data) != SGM_OK) fail("process", sgm_last_error(handle_));
             this->img_l = resized_[0];
             this->img_r = resized_[1];
         }
@@ -488,8 +476,11 @@ private:
         in_h_ = resizing_ ? rs_rows : rectifying_ ? rc_rows : full_h_;
         in_w_ = resizing_ ? rs_cols : rectifying_ ? rc_cols : full_w_;
         sgm_get_input_format(handle_, &format_);
-        if (!resizing_ && !rectifying_ && format_ == SGM_PIX_GRAY8) resized_[0] = resized_[1] = Mat();
+        if (!staging()) resized_[0] = resized_[1] = Mat();
     }
+
+    // an input stage is set: process() keeps host copies of the grey pair the frame matched
+    bool staging() const { return resizing_ || rectifying_ || format_ != SGM_PIX_GRAY8; }
 
     // the Mat type of a pixel format's images
     static int pix_type(int fmt) {

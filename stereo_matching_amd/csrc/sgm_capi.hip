@@ -1,9 +1,10 @@
 // sgm_capi.hip -- the C-ABI of libsgm_hip.so (include/sgm_hip.h).
 //
 // Parameter checks, sgm_create / sgm_destroy and the setters, the extern "C"
-// entry points and the sgm_stage_* functions of the parity tests.  What a
-// frame enqueues is in sgm_frame.hip; sgm_create picks its schedule (enum
-// Schedule, sgm_handle.h) once.
+// entry points and the sgm_stage_* functions of the parity tests.  The input
+// stage's part of the C-ABI is in sgm_input.hip; what a frame enqueues is in
+// sgm_frame.hip; sgm_create picks its schedule (enum Schedule, sgm_handle.h)
+// once.
 // All device memory is allocated at sgm_create (the reference allocates its
 // scratch in the constructors, Solver.cpp:18-27 and SGM.cpp:7-24), apart from
 // the maps the setters switch on and off.
@@ -110,17 +111,10 @@ void free_all(sgm_handle *h) {
 // memory on the CPU, so every host<->device transfer is one contiguous DMA
 // (pageable 2-D copies went through the runtime's staging path at a fraction
 // of PCIe bandwidth).  Layout: left | right | sky_l | sky_r | out f32 | raw u16.
-// rows x cols of the images a frame takes: the input size or the rectification
-// maps' source size when one is set (never both)
-inline int frame_rows(const sgm_handle *h) { return h->in_rows ? h->in_rows : h->rc_rows ? h->rc_rows : h->p.height; }
-inline int frame_cols(const sgm_handle *h) { return h->in_rows ? h->in_cols : h->rc_rows ? h->rc_cols : h->p.width; }
-
-// bytes per pixel, and per row, of those images (sgm_set_input_format)
-inline int frame_bpp(const sgm_handle *h) { return sgm::pix_bpp(h->fmt); }
-inline int frame_row_bytes(const sgm_handle *h) { return frame_cols(h) * frame_bpp(h); }
-
+// (left, right: the images a frame takes, at the input stage's size and format)
 int ensure_pinned(sgm_handle *h) {
-    const size_t nin = (size_t)frame_rows(h) * frame_row_bytes(h), npx = (size_t)h->g.H * h->g.W;
+    const size_t nin = (size_t)h->in.rows(h->p.height) * h->in.row_bytes(h->p.width);
+    const size_t npx = (size_t)h->g.H * h->g.W;
     const size_t need = 2 * nin + 2 * npx + npx * sizeof(float) + npx * sizeof(uint16_t) + 64;
     if (h->h_pin && h->h_pin_bytes >= need) return SGM_OK;
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -136,18 +130,6 @@ int copy_in_image(sgm_handle *h, uint8_t *dst, const uint8_t *src, int pitch) {
     return SGM_OK;
 }
 
-// A hipMallocAsync temporary of the stages: freed on its stream when the
-// scope ends, on every return path.
-template <typename T>
-struct StreamTemp {
-    T *p = nullptr;
-    hipStream_t st;
-    explicit StreamTemp(hipStream_t stream) : st(stream) {}
-    ~StreamTemp() {
-        if (p) (void)hipFreeAsync(p, st);
-    }
-};
-
 void pack_rows(uint8_t *dst, const uint8_t *src, size_t row_bytes, int rows, size_t pitch) {
     if (pitch == row_bytes) {
         memcpy(dst, src, row_bytes * rows);
@@ -156,7 +138,39 @@ void pack_rows(uint8_t *dst, const uint8_t *src, size_t row_bytes, int rows, siz
     for (int i = 0; i < rows; ++i) memcpy(dst + i * row_bytes, src + i * pitch, row_bytes);
 }
 
+// The slanted passes' hang guard (sgm_slant.hip): a receiver that polls a
+// neighbouring tile's hand-off for seconds gives up, and that frame's maps
+// are wrong.  It sets a host-mapped word; the next call on the handle (or
+// sgm_process, after its own frame) reports it and clears it.
+// The fixed-budget post filter (sgm_set_post_filter_launches) reports the
+// same way through a word of its own (every handle has one): its verdict
+// kernel sets it when the budget's last fill launch still changed a tile.
+int check_frame_err(sgm_handle *h) {
+    // read and clear in one step: a give-up stored by a frame still running
+    // between a plain read and a plain clear would be lost
+    const bool slant = h->h_slant_err && __atomic_exchange_n(h->h_slant_err, 0u, __ATOMIC_ACQ_REL);
+    // (the verdict kernel stores the budget that was not enough: 1..4096)
+    const unsigned fill = h->h_pf_err ? __atomic_exchange_n(h->h_pf_err, 0u, __ATOMIC_ACQ_REL) : 0u;
+    if (!slant && !fill) return SGM_OK;
+    if (!fill)
+        return set_err(h, SGM_ERR_HIP, "slanted aggregation: a tile hand-off timed out; that frame's maps are invalid");
+    return set_err(h, SGM_ERR_HIP,
+                   "post_filter: median fill not proven in %u launches "
+                   "(sgm_set_post_filter_launches); that frame's map is invalid%s",
+                   fill, slant ? "; slanted aggregation: a tile hand-off timed out too" : "");
+}
+
 }  // namespace
+
+// Waits for the last call's work: on a caller's stream its end was recorded
+// in ev_last; on the handle's own stream, that stream (the H pair's stream
+// is joined into the frame's stream before the bottom-up pass).
+int wait_last(sgm_handle *h) {
+    if (h->last_st && h->last_recorded) HIPCHK(h, hipEventSynchronize(h->ev_last));
+    else if (!h->last_st || h->last_st == h->st) HIPCHK(h, hipStreamSynchronize(h->st));
+    else HIPCHK(h, hipDeviceSynchronize());  // a caller's stream whose end could not be recorded
+    return SGM_OK;
+}
 
 extern "C" {
 
@@ -400,38 +414,6 @@ size_t sgm_device_bytes(const sgm_handle *h) { return h ? h->bytes : 0; }
 
 void *sgm_get_stream(const sgm_handle *h) { return h ? (void *)h->st : nullptr; }
 
-// The slanted passes' hang guard (sgm_slant.hip): a receiver that polls a
-// neighbouring tile's hand-off for seconds gives up, and that frame's maps
-// are wrong.  It sets a host-mapped word; the next call on the handle (or
-// sgm_process, after its own frame) reports it and clears it.
-// The fixed-budget post filter (sgm_set_post_filter_launches) reports the
-// same way through a word of its own (every handle has one): its verdict
-// kernel sets it when the budget's last fill launch still changed a tile.
-int check_frame_err(sgm_handle *h) {
-    // read and clear in one step: a give-up stored by a frame still running
-    // between a plain read and a plain clear would be lost
-    const bool slant = h->h_slant_err && __atomic_exchange_n(h->h_slant_err, 0u, __ATOMIC_ACQ_REL);
-    // (the verdict kernel stores the budget that was not enough: 1..4096)
-    const unsigned fill = h->h_pf_err ? __atomic_exchange_n(h->h_pf_err, 0u, __ATOMIC_ACQ_REL) : 0u;
-    if (!slant && !fill) return SGM_OK;
-    if (!fill)
-        return set_err(h, SGM_ERR_HIP, "slanted aggregation: a tile hand-off timed out; that frame's maps are invalid");
-    return set_err(h, SGM_ERR_HIP,
-                   "post_filter: median fill not proven in %u launches "
-                   "(sgm_set_post_filter_launches); that frame's map is invalid%s",
-                   fill, slant ? "; slanted aggregation: a tile hand-off timed out too" : "");
-}
-
-// Waits for the last call's work: on a caller's stream its end was recorded
-// in ev_last; on the handle's own stream, that stream (the H pair's stream
-// is joined into the frame's stream before the bottom-up pass).
-static int wait_last(sgm_handle *h) {
-    if (h->last_st && h->last_recorded) HIPCHK(h, hipEventSynchronize(h->ev_last));
-    else if (!h->last_st || h->last_st == h->st) HIPCHK(h, hipStreamSynchronize(h->st));
-    else HIPCHK(h, hipDeviceSynchronize());  // a caller's stream whose end could not be recorded
-    return SGM_OK;
-}
-
 int sgm_check(sgm_handle *h) {
     if (!h) return SGM_ERR_INVALID_ARG;
     DeviceGuard guard(h->device);
@@ -473,456 +455,33 @@ int sgm_set_min_disp(sgm_handle *h, int m) {
                        "sgm_set_min_disp: max_disp + min_disp + 1 must fit the raw u16 map (<= 65535)");
     if (h->p.solver == SGM_SOLVER_BM && m != 0)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_min_disp: not supported by the BM solver");
-    DeviceGuard guard(h->device);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_min_disp: call it outside stream capture");
-    if (m == h->min_disp) return SGM_OK;
-    // frames in flight still read the tables and the handle's geometry
-    if (int rc = wait_last(h)) return rc;
-    const size_t npx = (size_t)h->g.H * h->g.W;
-    // each image's shifted table (16 B per pixel for both; frames write the
-    // ones their views read, sgm_stage_cost its view's); at 0 the tables
-    // themselves, nothing allocated.  (aux_only handles compute no cost.)
-    const bool want = m != 0 && !h->p.aux_only, have = h->d_cts[0] != h->d_ct[0];
-    if (want && !have) {
-        uint64_t *t[2] = {nullptr, nullptr};
-        int rc = dalloc(h, &t[0], npx);
-        if (!rc) rc = dalloc(h, &t[1], npx);
-        if (rc) {
-            for (auto &q : t) dfree(h, &q, npx);
-            return rc;
+    // (frames in flight still read the tables and the handle's geometry)
+    return change_setting(h, "sgm_set_min_disp", m == h->min_disp, [&]() -> int {
+        const size_t npx = (size_t)h->g.H * h->g.W;
+        // each image's shifted table (16 B per pixel for both; frames write the
+        // ones their views read, sgm_stage_cost its view's); at 0 the tables
+        // themselves, nothing allocated.  (aux_only handles compute no cost.)
+        const bool want = m != 0 && !h->p.aux_only, have = h->d_cts[0] != h->d_ct[0];
+        if (want && !have) {
+            uint64_t *t[2] = {nullptr, nullptr};
+            int rc = dalloc(h, &t[0], npx);
+            if (!rc) rc = dalloc(h, &t[1], npx);
+            if (rc) {
+                for (auto &q : t) dfree(h, &q, npx);
+                return rc;
+            }
+            h->d_cts[0] = t[0];
+            h->d_cts[1] = t[1];
+        } else if (!want && have) {
+            for (int v = 0; v < 2; ++v) {
+                dfree(h, &h->d_cts[v], npx);
+                h->d_cts[v] = h->d_ct[v];
+            }
         }
-        h->d_cts[0] = t[0];
-        h->d_cts[1] = t[1];
-    } else if (!want && have) {
-        for (int v = 0; v < 2; ++v) {
-            dfree(h, &h->d_cts[v], npx);
-            h->d_cts[v] = h->d_ct[v];
-        }
-    }
-    h->min_disp = m;
-    h->gt.D = h->g.D + m;
-    return SGM_OK;
-}
-
-// ---- the buffers of the input stages (resize, rectification, colour format)
-
-// Makes d_rs and d_raw fit the handle's input stages as they stand: with an
-// input size, maps (on a handle that runs frames) or a colour format set, the
-// two full-size grey images the frame's first launch writes and the host API's
-// staging of the two raw images at their size and format; with none, neither.
-// Buffers that fit already are kept.  On a failed allocation every input stage
-// is switched off and the handle runs as it did at sgm_create.
-static void rectify_free_maps(sgm_handle *h);
-static int fit_input_buffers(sgm_handle *h) {
-    const bool staged = h->in_rows || (h->rc_rows && !h->p.aux_only) || h->fmt;
-    const size_t nfull = (size_t)h->p.height * h->p.width;
-    const size_t nraw = staged ? (size_t)frame_rows(h) * frame_row_bytes(h) : 0;
-    int rc = SGM_OK;
-    h->rs_valid = false;
-    for (int v = 0; v < 2 && !rc; ++v) {
-        if (!staged) dfree(h, &h->d_rs[v], nfull);
-        else if (!h->d_rs[v]) rc = dalloc(h, &h->d_rs[v], nfull);
-    }
-    if (!rc && nraw != h->raw_bytes) {
-        for (int v = 0; v < 2; ++v) dfree(h, &h->d_raw[v], h->raw_bytes);
-        h->raw_bytes = 0;
-        for (int v = 0; v < 2 && !rc; ++v) rc = dalloc(h, &h->d_raw[v], nraw);
-        if (!rc) h->raw_bytes = nraw;
-    }
-    if (rc) {
-        // (dalloc nulls the pointer it failed on; raw_bytes is still the freed size's 0 or the old one)
-        for (int v = 0; v < 2; ++v) {
-            dfree(h, &h->d_raw[v], h->raw_bytes ? h->raw_bytes : nraw);
-            dfree(h, &h->d_rs[v], nfull);
-        }
-        h->raw_bytes = 0;
-        h->in_rows = h->in_cols = 0;
-        h->fmt = SGM_PIX_GRAY8;
-        rectify_free_maps(h);
-    }
-    return rc;
-}
-
-// The frames' images at format fmt must stay addressable with an int.
-static bool frame_bytes_ok(const sgm_handle *h, int fmt, int rows, int cols) {
-    size_t bytes;
-    return sgm::pix_image_bytes(fmt, rows ? rows : h->p.height, rows ? cols : h->p.width, &bytes);
-}
-
-// ---- input resize (node.cpp:75-76; sgm_resize.hip)
-
-int sgm_set_input_size(sgm_handle *h, int src_rows, int src_cols) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!input_size_ok(src_rows, src_cols, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_size: %s", why);
-    if (h->p.aux_only && src_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_set_input_size: an aux_only handle runs no frames (sgm_resize_device "
-                       "takes its sizes per call)");
-    if (h->rc_rows && src_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_set_input_size: rectification maps are set (sgm_set_rectify): one input "
-                       "stage at a time, and the remap resizes too");
-    if (!frame_bytes_ok(h, h->fmt, src_rows, src_cols))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_size: image too large: %d x %d at %d bytes per pixel",
-                       src_rows, src_cols, frame_bpp(h));
-    DeviceGuard guard(h->device);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_size: call it outside stream capture");
-    if (src_rows == h->in_rows && src_cols == h->in_cols) return SGM_OK;
-    // frames in flight still read the staged and the resized images
-    if (int rc = wait_last(h)) return rc;
-    h->in_rows = src_rows;
-    h->in_cols = src_cols;
-    return fit_input_buffers(h);
-}
-
-int sgm_get_input_size(const sgm_handle *h, int *src_rows, int *src_cols) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (src_rows) *src_rows = h->in_rows;
-    if (src_cols) *src_cols = h->in_cols;
-    return SGM_OK;
-}
-
-int sgm_get_resized(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!d_img || !pitch) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: NULL pointer");
-    if (!h->in_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: no input size is set (sgm_set_input_size)");
-    // (every frame handle's census reads both images, so both are resized)
-    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: the handle reads no image of view %d", view);
-    if (!h->rs_valid)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_resized: no frame has run since the input size was set");
-    *d_img = h->d_rs[view];
-    *pitch = h->p.width;
-    return SGM_OK;
-}
-
-int sgm_stage_resized(sgm_handle *h, int view, uint8_t *img) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!img) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resized: NULL pointer");
-    const uint8_t *d_img = nullptr;
-    int pitch = 0;
-    if (int rc = sgm_get_resized(h, view, &d_img, &pitch)) return rc;
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
-}
-
-int sgm_resize_device(sgm_handle *h, const uint8_t *d_src, int src_rows, int src_cols, int src_pitch,
-                      uint8_t *d_dst, int dst_pitch, void *stream) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!d_src || !d_dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_resize_device: NULL pointer");
-    if (!resize_src_ok(src_rows, src_cols, src_pitch, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_resize_device: %s", why);
-    if (dst_pitch < h->p.width)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_resize_device: dst_pitch %d below the width %d",
-                       dst_pitch, h->p.width);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, stream);
-    hipStream_t st = scope.st;
-    HIPCHK(h, timed(h, "resize", (double)h->p.height * h->p.width, st, [&] {
-               return sgm::launch_resize(&d_src, src_rows, src_cols, src_pitch, &d_dst, h->p.height,
-                                         h->p.width, dst_pitch, 1, st);
-           }));
-    return SGM_OK;
-}
-
-int sgm_stage_resize(sgm_handle *h, const uint8_t *src, int src_rows, int src_cols, int src_pitch,
-                     uint8_t *dst) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resize: NULL pointer");
-    if (!resize_src_ok(src_rows, src_cols, src_pitch, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resize: %s", why);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    const size_t nsrc = (size_t)src_rows * src_cols, nfull = (size_t)h->p.height * h->p.width;
-    int rc;
-    {
-        // staging: the source in a stream-ordered temporary, the result in d_in[0]
-        StreamTemp<uint8_t> d_src(h->st);
-        HIPCHK(h, hipMallocAsync((void **)&d_src.p, nsrc, h->st));
-        HIPCHK(h, hipMemcpy2DAsync(d_src.p, (size_t)src_cols, src, (size_t)src_pitch, (size_t)src_cols,
-                                   (size_t)src_rows, hipMemcpyHostToDevice, h->st));
-        rc = sgm_resize_device(h, d_src.p, src_rows, src_cols, src_cols, h->d_in[0], h->p.width, h->st);
-        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, h->d_in[0], nfull, hipMemcpyDeviceToHost, h->st));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return rc;
-}
-
-// ---- rectification (sgm_rectify.hip, sgm_rectify_maps.h)
-
-// Frees the maps and the masks and switches the remap off (the images follow
-// in fit_input_buffers).
-static void rectify_free_maps(sgm_handle *h) {
-    const size_t nfull = (size_t)h->p.height * h->p.width;
-    for (int v = 0; v < 2; ++v) {
-        dfree(h, &h->d_map[v], 2 * nfull);
-        std::vector<uint8_t>().swap(h->valid[v]);
-    }
-    h->rc_rows = h->rc_cols = 0;
-}
-
-// Frees what sgm_set_rectify allocated and switches it off.
-static int rectify_off(sgm_handle *h) {
-    rectify_free_maps(h);
-    return fit_input_buffers(h);
-}
-
-int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_x_l, const float *map_y_l,
-                    const float *map_x_r, const float *map_y_r, int map_pitch) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    const float *const maps[4] = {map_x_l, map_y_l, map_x_r, map_y_r};
-    if (!rectify_args_ok(src_rows, src_cols, maps, map_pitch, h->p.width, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_rectify: %s", why);
-    if (h->in_rows && src_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_set_rectify: an input size is set (sgm_set_input_size): one input stage at "
-                       "a time, and the remap resizes too");
-    if (!frame_bytes_ok(h, h->fmt, src_rows, src_cols))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_rectify: image too large: %d x %d at %d bytes per pixel",
-                       src_rows, src_cols, frame_bpp(h));
-    DeviceGuard guard(h->device);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_rectify: call it outside stream capture");
-    if (!src_rows && !h->rc_rows) return SGM_OK;
-    // frames in flight still read the maps, the staged and the rectified images
-    if (int rc = wait_last(h)) return rc;
-    int rc = rectify_off(h);
-    if (rc || !src_rows) return rc;
-    const size_t nfull = (size_t)h->p.height * h->p.width;
-    std::vector<uint32_t> packed;
-    try {
-        packed.resize(2 * nfull);
-        for (int v = 0; v < 2; ++v) h->valid[v].resize(nfull);
-    } catch (const std::bad_alloc &) {
-        rc = set_err(h, SGM_ERR_OUT_OF_MEMORY, "sgm_set_rectify: out of host memory");
-    }
-    for (int v = 0; v < 2 && !rc; ++v) {
-        rectify_convert(maps[2 * v], maps[2 * v + 1], map_pitch, h->p.height, h->p.width, src_rows, src_cols,
-                        packed.data(), h->valid[v].data());
-        if ((rc = dalloc(h, &h->d_map[v], 2 * nfull))) break;
-        if (hipMemcpy(h->d_map[v], packed.data(), 2 * nfull * sizeof(uint32_t), hipMemcpyHostToDevice) !=
-            hipSuccess)
-            rc = set_err(h, SGM_ERR_HIP, "sgm_set_rectify: the upload of the packed map failed");
-    }
-    if (rc) {  // (off again: the handle runs as before)
-        (void)rectify_off(h);
-        return rc;
-    }
-    // (an aux_only handle runs no frames: it keeps the maps for sgm_remap_device alone)
-    h->rc_rows = src_rows;
-    h->rc_cols = src_cols;
-    return fit_input_buffers(h);
-}
-
-int sgm_get_rectify(const sgm_handle *h, int *src_rows, int *src_cols) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (src_rows) *src_rows = h->rc_rows;
-    if (src_cols) *src_cols = h->rc_cols;
-    return SGM_OK;
-}
-
-int sgm_remap_device(sgm_handle *h, int view, const uint8_t *d_src, int src_pitch, uint8_t *d_dst,
-                     int dst_pitch, void *stream) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!d_src || !d_dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_remap_device: NULL pointer");
-    if (!h->rc_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_remap_device: no maps are set (sgm_set_rectify)");
-    if (!rectify_call_ok(view, src_pitch, h->rc_cols, dst_pitch, h->p.width, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_remap_device: %s", why);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, stream);
-    hipStream_t st = scope.st;
-    HIPCHK(h, timed(h, "rectify", (double)h->p.height * h->p.width, st, [&] {
-               return sgm::launch_rectify(&d_src, h->rc_rows, h->rc_cols, src_pitch, &h->d_map[view], &d_dst,
-                                          h->p.height, h->p.width, dst_pitch, 1, st);
-           }));
-    return SGM_OK;
-}
-
-int sgm_stage_remap(sgm_handle *h, int view, const uint8_t *src, int src_pitch, uint8_t *dst) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: NULL pointer");
-    if (!h->rc_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: no maps are set (sgm_set_rectify)");
-    if (!rectify_call_ok(view, src_pitch, h->rc_cols, h->p.width, h->p.width, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: %s", why);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    const size_t nsrc = (size_t)h->rc_rows * h->rc_cols, nfull = (size_t)h->p.height * h->p.width;
-    int rc;
-    {
-        // staging: the source in a stream-ordered temporary, the result in d_in[0]
-        StreamTemp<uint8_t> d_src(h->st);
-        HIPCHK(h, hipMallocAsync((void **)&d_src.p, nsrc, h->st));
-        HIPCHK(h, hipMemcpy2DAsync(d_src.p, (size_t)h->rc_cols, src, (size_t)src_pitch, (size_t)h->rc_cols,
-                                   (size_t)h->rc_rows, hipMemcpyHostToDevice, h->st));
-        rc = sgm_remap_device(h, view, d_src.p, h->rc_cols, h->d_in[0], h->p.width, h->st);
-        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, h->d_in[0], nfull, hipMemcpyDeviceToHost, h->st));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return rc;
-}
-
-int sgm_get_rectified(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!d_img || !pitch) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: NULL pointer");
-    if (!h->rc_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: no maps are set (sgm_set_rectify)");
-    // (every frame handle's census reads both images, so both are rectified)
-    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: the handle reads no image of view %d", view);
-    if (!h->rs_valid)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_rectified: no frame has run since the maps were set");
-    *d_img = h->d_rs[view];
-    *pitch = h->p.width;
-    return SGM_OK;
-}
-
-int sgm_stage_rectified(sgm_handle *h, int view, uint8_t *img) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!img) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectified: NULL pointer");
-    const uint8_t *d_img = nullptr;
-    int pitch = 0;
-    if (int rc = sgm_get_rectified(h, view, &d_img, &pitch)) return rc;
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
-}
-
-int sgm_stage_rectify_valid(sgm_handle *h, int view, uint8_t *mask) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!mask) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: NULL pointer");
-    if (!h->rc_rows)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: no maps are set (sgm_set_rectify)");
-    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_rectify_valid: view must be 0 (left) or 1 (right), got %d",
-                       view);
-    memcpy(mask, h->valid[view].data(), h->valid[view].size());
-    return SGM_OK;
-}
-
-// ---- colour input (sgm_gray.hip, sgm_pix.h, sgm_gray_args.h)
-
-int sgm_set_input_format(sgm_handle *h, int fmt) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!input_format_ok(fmt, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_format: %s", why);
-    if (h->p.aux_only && fmt != SGM_PIX_GRAY8)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_set_input_format: an aux_only handle runs no frames (sgm_gray_device takes "
-                       "its format per call)");
-    if (!frame_bytes_ok(h, fmt, frame_rows(h), frame_cols(h)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_format: image too large: %d x %d at %d bytes per pixel",
-                       frame_rows(h), frame_cols(h), sgm::pix_bpp(fmt));
-    DeviceGuard guard(h->device);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_input_format: call it outside stream capture");
-    if (fmt == h->fmt) return SGM_OK;
-    // frames in flight still read the staged and the grey images
-    if (int rc = wait_last(h)) return rc;
-    h->fmt = fmt;
-    return fit_input_buffers(h);
-}
-
-int sgm_get_input_format(const sgm_handle *h, int *fmt) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (fmt) *fmt = h->fmt;
-    return SGM_OK;
-}
-
-int sgm_gray_device(sgm_handle *h, int fmt, const uint8_t *d_src, int rows, int cols, int src_pitch,
-                    uint8_t *d_dst, int dst_pitch, void *stream) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!d_src || !d_dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_gray_device: NULL pointer");
-    if (!gray_call_ok(fmt, rows, cols, src_pitch, dst_pitch, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_gray_device: %s", why);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, stream);
-    hipStream_t st = scope.st;
-    HIPCHK(h, timed(h, "gray", (double)rows * cols, st, [&] {
-               return sgm::launch_gray(fmt, &d_src, rows, cols, src_pitch, &d_dst, dst_pitch, 1, st);
-           }));
-    return SGM_OK;
-}
-
-int sgm_stage_gray(sgm_handle *h, int fmt, const uint8_t *src, int rows, int cols, int src_pitch,
-                   uint8_t *dst) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    char why[160];
-    if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_gray: NULL pointer");
-    if (!gray_call_ok(fmt, rows, cols, src_pitch, cols, why, sizeof(why)))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_gray: %s", why);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    const size_t row = (size_t)cols * sgm::pix_bpp(fmt), npx = (size_t)rows * cols;
-    int rc;
-    {
-        // staging: the source and the result in stream-ordered temporaries (any size serves)
-        StreamTemp<uint8_t> d_src(h->st), d_dst(h->st);
-        HIPCHK(h, hipMallocAsync((void **)&d_src.p, row * rows, h->st));
-        HIPCHK(h, hipMallocAsync((void **)&d_dst.p, npx, h->st));
-        HIPCHK(h, hipMemcpy2DAsync(d_src.p, row, src, (size_t)src_pitch, row, (size_t)rows,
-                                   hipMemcpyHostToDevice, h->st));
-        rc = sgm_gray_device(h, fmt, d_src.p, rows, cols, (int)row, d_dst.p, cols, h->st);
-        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, d_dst.p, npx, hipMemcpyDeviceToHost, h->st));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return rc;
-}
-
-int sgm_get_input_gray(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!d_img || !pitch) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_input_gray: NULL pointer");
-    if (!h->fmt)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_get_input_gray: the input format is grey (sgm_set_input_format): the frame reads "
-                       "the caller's images");
-    // (every frame handle's census reads both images, so both are converted)
-    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_input_gray: the handle reads no image of view %d", view);
-    if (!h->rs_valid)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_input_gray: no frame has run since the format was set");
-    *d_img = h->d_rs[view];
-    *pitch = h->p.width;
-    return SGM_OK;
-}
-
-int sgm_stage_input_gray(sgm_handle *h, int view, uint8_t *img) {
-    if (!h) return SGM_ERR_INVALID_ARG;
-    if (!img) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_input_gray: NULL pointer");
-    const uint8_t *d_img = nullptr;
-    int pitch = 0;
-    if (int rc = sgm_get_input_gray(h, view, &d_img, &pitch)) return rc;
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
+        h->min_disp = m;
+        h->gt.D = h->g.D + m;
+        return SGM_OK;
+    });
 }
 
 int sgm_set_confidence(sgm_handle *h, int enable) {
@@ -930,31 +489,27 @@ int sgm_set_confidence(sgm_handle *h, int enable) {
     if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_set_confidence: BM and aux_only handles run no aggregated WTA");
-    DeviceGuard guard(h->device);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_confidence: call it outside stream capture");
-    if ((enable != 0) == (h->d_ratio[0] != nullptr)) return SGM_OK;
-    // frames in flight still store through (or read) the maps
-    if (int rc = wait_last(h)) return rc;
-    const size_t npx = (size_t)h->g.H * h->g.W;
-    if (!enable) {
-        for (int v = 0; v < 2; ++v) dfree(h, &h->d_ratio[v], npx);
-        return SGM_OK;
-    }
-    for (int v = 0; v < h->nviews; ++v) {
-        int rc = dalloc(h, &h->d_ratio[v], npx);
-        // (a map no frame has written yet reads as zeros)
-        if (!rc && hipMemset(h->d_ratio[v], 0, npx * sizeof(float)) != hipSuccess)
-            rc = set_err(h, SGM_ERR_HIP, "hipMemset of the confidence map failed");
-        if (rc) {
-            for (int w = 0; w < 2; ++w) dfree(h, &h->d_ratio[w], npx);
-            return rc;
+    // (frames in flight still store through, or read, the maps)
+    const bool unchanged = (enable != 0) == (h->d_ratio[0] != nullptr);
+    return change_setting(h, "sgm_set_confidence", unchanged, [&]() -> int {
+        const size_t npx = (size_t)h->g.H * h->g.W;
+        if (!enable) {
+            for (int v = 0; v < 2; ++v) dfree(h, &h->d_ratio[v], npx);
+            return SGM_OK;
         }
-        h->ratio_cm[v] = false;
-    }
-    return SGM_OK;
+        for (int v = 0; v < h->nviews; ++v) {
+            int rc = dalloc(h, &h->d_ratio[v], npx);
+            // (a map no frame has written yet reads as zeros)
+            if (!rc && hipMemset(h->d_ratio[v], 0, npx * sizeof(float)) != hipSuccess)
+                rc = set_err(h, SGM_ERR_HIP, "hipMemset of the confidence map failed");
+            if (rc) {
+                for (int w = 0; w < 2; ++w) dfree(h, &h->d_ratio[w], npx);
+                return rc;
+            }
+            h->ratio_cm[v] = false;
+        }
+        return SGM_OK;
+    });
 }
 
 int sgm_confidence_device(sgm_handle *h, int view, float *d_ratio, int pitch, void *stream) {
@@ -1038,7 +593,7 @@ int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_ri
                        float *d_out, int out_pitch, uint16_t *d_raw_disp, void *stream) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (int rc = check_frame_err(h)) return rc;
-    if (!d_left || !d_right || !d_out || pitch < frame_row_bytes(h) || out_pitch < h->g.W ||
+    if (!d_left || !d_right || !d_out || pitch < h->in.row_bytes(h->p.width) || out_pitch < h->g.W ||
         ((d_sky_l || d_sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: bad pointer or pitch");
     if (h->p.aux_only)
@@ -1053,7 +608,7 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
                 const uint8_t *sky_l, const uint8_t *sky_r, int sky_pitch, float *out,
                 int out_pitch, uint16_t *raw_disp) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (!left || !right || !out || pitch < frame_row_bytes(h) || out_pitch < h->g.W ||
+    if (!left || !right || !out || pitch < h->in.row_bytes(h->p.width) || out_pitch < h->g.W ||
         ((sky_l || sky_r) && sky_pitch < h->g.W))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: bad pointer or pitch");
     if (h->p.aux_only)
@@ -1063,10 +618,10 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
     if ((rc = ensure_pinned(h))) return rc;
-    // (with an input size, maps or a colour format set the raw images are staged and the frame
-    // resizes, remaps or converts them; in_w: their bytes per row)
-    const int in_h = frame_rows(h), in_w = frame_row_bytes(h);
-    uint8_t *const *d_in = h->in_rows || h->rc_rows || h->fmt ? h->d_raw : h->d_in;
+    // (a handle that stages, sgm_input_stage.h, takes the raw images in its staging buffers and
+    // the frame resizes, remaps or converts them; in_w: their bytes per row)
+    const int in_h = h->in.rows(h->p.height), in_w = h->in.row_bytes(h->p.width);
+    uint8_t *const *d_in = h->in.stages(h->p.aux_only) ? h->d_raw : h->d_in;
     const size_t nin = (size_t)in_h * in_w, npx = (size_t)h->g.H * h->g.W;
     uint8_t *pl = h->h_pin, *pr = pl + nin, *psl = pr + nin, *psr = psl + npx;
     float *pout = reinterpret_cast<float *>(psr + npx + (16 - (size_t)(psr + npx) % 16) % 16);

@@ -546,6 +546,38 @@ int finish_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     return SGM_OK;
 }
 
+// The frame's input slot (DESIGN.md "The input slot"): at most one launch, by
+// the handle's input stage (sgm_input_stage.h), writes both full-size grey
+// images into d_rs (every handle's census reads both), and the sky detector,
+// the census, LKRefine and BM read those instead of the caller's images.  An
+// input size: node.cpp:75-76's resize (5j); maps: the remap, which resizes too
+// (5k); a colour format converts inside either, or with neither as a launch of
+// its own (5l).
+int input_slot(sgm_handle *h, FrameIO *f, hipStream_t st) {
+    const sgm::InputStage &in = h->in;
+    const sgm::InputKind kind = in.kind();
+    if (kind == sgm::INPUT_NONE) return SGM_OK;
+    static const char *const names[] = {nullptr, "resize", "rectify", "gray"};
+    const uint8_t *src[2] = {f->left, f->right};
+    const int H = h->p.height, W = h->p.width, pitch = f->pitch;
+    HIPCHK(h, timed(h, names[kind], 2.0 * H * W, st, [&] {
+               switch (kind) {
+               case sgm::INPUT_RESIZE:
+                   return sgm::launch_resize(src, in.in_rows, in.in_cols, pitch, h->d_rs, H, W, W, 2, st, in.fmt);
+               case sgm::INPUT_RECTIFY:
+                   return sgm::launch_rectify(src, in.rc_rows, in.rc_cols, pitch, h->d_map, h->d_rs, H, W, W, 2,
+                                              st, in.fmt);
+               default:
+                   return sgm::launch_gray(in.fmt, src, H, W, pitch, h->d_rs, W, 2, st);
+               }
+           }));
+    f->left = h->d_rs[0];
+    f->right = h->d_rs[1];
+    f->pitch = W;
+    h->rs_valid = true;
+    return SGM_OK;
+}
+
 }  // namespace
 
 int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
@@ -561,44 +593,7 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
     const int nv = h->nviews;
     const double elems = vol_elems(g);
     int rc;
-    // node.cpp:75-76: with an input size set the frame's first launch resizes
-    // both images to the full size (every handle's census reads both), and the
-    // sky detector, the census, LKRefine and BM read those
-    if (h->in_rows) {
-        const uint8_t *src[2] = {f.left, f.right};
-        HIPCHK(h, timed(h, "resize", 2.0 * h->p.height * h->p.width, st, [&] {
-                   return sgm::launch_resize(src, h->in_rows, h->in_cols, f.pitch, h->d_rs, h->p.height,
-                                             h->p.width, h->p.width, 2, st, h->fmt);
-               }));
-        f.left = h->d_rs[0];
-        f.right = h->d_rs[1];
-        f.pitch = h->p.width;
-        h->rs_valid = true;
-    } else if (h->rc_rows) {
-        // with rectification maps set the same slot remaps both images instead
-        // (the maps are built at the full size, so the remap resizes too)
-        const uint8_t *src[2] = {f.left, f.right};
-        HIPCHK(h, timed(h, "rectify", 2.0 * h->p.height * h->p.width, st, [&] {
-                   return sgm::launch_rectify(src, h->rc_rows, h->rc_cols, f.pitch, h->d_map, h->d_rs,
-                                              h->p.height, h->p.width, h->p.width, 2, st, h->fmt);
-               }));
-        f.left = h->d_rs[0];
-        f.right = h->d_rs[1];
-        f.pitch = h->p.width;
-        h->rs_valid = true;
-    } else if (h->fmt) {
-        // a colour format with neither: one launch converts both images (with a
-        // resize or a remap set that launch converts its taps itself)
-        const uint8_t *src[2] = {f.left, f.right};
-        HIPCHK(h, timed(h, "gray", 2.0 * h->p.height * h->p.width, st, [&] {
-                   return sgm::launch_gray(h->fmt, src, h->p.height, h->p.width, f.pitch, h->d_rs,
-                                           h->p.width, 2, st);
-               }));
-        f.left = h->d_rs[0];
-        f.right = h->d_rs[1];
-        f.pitch = h->p.width;
-        h->rs_valid = true;
-    }
+    if ((rc = input_slot(h, &f, st)) != SGM_OK) return rc;
     // Everything runs on one stream.  Two-view frames keep each view's cost
     // volume resident in the 256 MB Infinity Cache through its readers by
     // running the views' aggregation back to back (K128: 238.5 MB per view;

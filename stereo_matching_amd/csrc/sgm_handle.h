@@ -1,10 +1,11 @@
 // sgm_handle.h -- the handle behind include/sgm_hip.h and the host helpers
-// every function that works on it uses: shared by the C-ABI (sgm_capi.hip) and
-// the frame schedules (sgm_frame.hip).  Host-only; not part of the public
-// interface.
+// every function that works on it uses: shared by the C-ABI (sgm_capi.hip, and
+// sgm_input.hip for the input stage) and the frame schedules (sgm_frame.hip).
+// Host-only; not part of the public interface.
 #pragma once
 
 #include "../../include/sgm_hip.h"
+#include "sgm_input_stage.h"
 #include "sgm_internal.h"
 
 #include <algorithm>
@@ -44,20 +45,15 @@ struct sgm_handle {
     hipStream_t last_st;  // the stream of the last entry point's work (null: none yet)
     bool last_recorded;   // ev_last was recorded at the end of that call (a caller's stream)
     uint8_t *d_in[2];     // full-size input staging (host API)
-    int in_rows, in_cols; // sgm_set_input_size: frames take in_rows x in_cols images (0, 0: off)
-    uint8_t *d_rs[2];     //   and resize them into these full-size images first (left, right)
-    uint8_t *d_raw[2];    //   staging of the raw images (host API)
-    bool rs_valid;        //   a frame has filled d_rs since the size was set (sgm_get_resized)
-    int rc_rows, rc_cols; // sgm_set_rectify: frames take rc_rows x rc_cols images (0, 0: off; never
-                          //   together with an input size) and remap them into d_rs first, staged
-                          //   in d_raw like the resize's (aux_only handles: the maps alone)
-    uint32_t *d_map[2];   //   each view's packed map, two words per full-size pixel (sgm_rectify_maps.h)
+    sgm::InputStage in;   // the input size, the maps' source size and the pixel format frames take
+                          //   (sgm_input_stage.h; all off: frames read the caller's images)
+    uint8_t *d_rs[2];     //   the full-size grey images the frame's first launch writes (left, right)
+    uint8_t *d_raw[2];    //   staging of the raw images (host API): cols x bytes per pixel per row
+    bool rs_valid;        //   a frame has filled d_rs since a setter last changed the stage
+    uint32_t *d_map[2];   //   each view's packed map, two words per full-size pixel (sgm_rectify_maps.h;
+                          //   aux_only handles: the maps alone, for sgm_remap_device)
     std::vector<uint8_t> valid[2];  //   each view's valid mask (host, full size, dense)
-    int fmt;              // sgm_set_input_format: the pixel format of the images frames take
-                          //   (SGM_PIX_GRAY8 = 0: off).  A colour format makes the resize or the remap
-                          //   convert its taps, or with neither set a launch of its own convert the
-                          //   images, into d_rs; d_raw then stages cols x bytes per pixel per row
-    size_t raw_bytes;     // bytes of each d_raw (0: none): fit_input_buffers, sgm_capi.hip
+    size_t raw_bytes;     // bytes of each d_raw (0: none): fit_input_buffers, sgm_input.hip
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
@@ -183,6 +179,38 @@ inline int set_err(sgm_handle *h, int code, const char *fmt, ...) {
                            "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__,   \
                            __LINE__);                                                        \
     } while (0)
+
+// Waits for the last call's work (sgm_capi.hip; kept out of the library's
+// exported symbols).
+__attribute__((visibility("hidden"))) int wait_last(sgm_handle *h);
+
+// What every setter that reallocates buffers does after its argument checks:
+// refuse inside a stream capture (`fn`: the setter's name, for the message),
+// return at once when nothing changes, else wait for the frames in flight
+// (they still read what `apply` frees or replaces) and apply.
+template <typename F>
+int change_setting(sgm_handle *h, const char *fn, bool unchanged, F &&apply) {
+    DeviceGuard guard(h->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(h, hipStreamIsCapturing(h->st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(h, SGM_ERR_INVALID_ARG, "%s: call it outside stream capture", fn);
+    if (unchanged) return SGM_OK;
+    if (int rc = wait_last(h)) return rc;
+    return apply();
+}
+
+// A hipMallocAsync temporary of the stages: freed on its stream when the
+// scope ends, on every return path.
+template <typename T>
+struct StreamTemp {
+    T *p = nullptr;
+    hipStream_t st;
+    explicit StreamTemp(hipStream_t stream) : st(stream) {}
+    ~StreamTemp() {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+};
 
 template <typename T>
 int dalloc(sgm_handle *h, T **p, size_t count) {

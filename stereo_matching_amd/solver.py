@@ -226,10 +226,23 @@ class SGM:
         images, and the frame's first launch resizes them to h x w (the node's
         cv::resize, node.cpp:75-76, in its pinned fixed-point form); (0, 0)
         switches it off.  Not inside stream capture; re-capture graphs."""
+        self._set_input(self._lib.sgm_set_input_size, int(rows), int(cols))
+
+    def _set_input(self, setter, *args) -> None:
+        """One call of an input stage's setter, then _sync_input_shape(),
+        whether or not the call raised."""
         try:
-            check(self._lib.sgm_set_input_size(self._h, int(rows), int(cols)), self._h)
+            check(setter(self._h, *args), self._h)
         finally:
             self._sync_input_shape()
+
+    def _input_image(self, stage, view: int) -> np.ndarray:
+        """The last frame's full-size grey image of `view` as `stage`
+        (sgm_stage_resized, sgm_stage_rectified or sgm_stage_input_gray)
+        downloads it: h x w uint8."""
+        out = np.empty((self.h, self.w), np.uint8)
+        check(stage(self._h, int(view), _ptr(out)), self._h)
+        return out
 
     def _sync_input_shape(self) -> None:
         """in_h, in_w: the shape of the images process() takes, read back from
@@ -275,9 +288,7 @@ class SGM:
     def get_resized(self, view: int = 0) -> np.ndarray:
         """The last frame's resized image of `view` (0 = left, 1 = right):
         h x w uint8, a host copy (sgm_stage_resized)."""
-        out = np.empty((self.h, self.w), np.uint8)
-        check(self._lib.sgm_stage_resized(self._h, int(view), _ptr(out)), self._h)
-        return out
+        return self._input_image(self._lib.sgm_stage_resized, view)
 
     # ------------------------------------------------------ rectification
     def set_rectify(self, src_rows: int, src_cols: int, mapx_l=None, mapy_l=None,
@@ -295,11 +306,8 @@ class SGM:
                 if m.shape != (self.h, self.w):
                     raise ValueError(f"{name}: expected shape {(self.h, self.w)}, got {m.shape}")
             maps.append(m)
-        try:
-            check(self._lib.sgm_set_rectify(self._h, int(src_rows), int(src_cols), *(_ptr(m) for m in maps),
-                                            self.w), self._h)
-        finally:
-            self._sync_input_shape()
+        self._set_input(self._lib.sgm_set_rectify, int(src_rows), int(src_cols), *(_ptr(m) for m in maps),
+                        self.w)
 
     @property
     def rectify_size(self):
@@ -332,9 +340,7 @@ class SGM:
     def rectified(self, view: int = 0) -> np.ndarray:
         """The last frame's rectified image of `view` (0 = left, 1 = right):
         h x w uint8, a host copy (sgm_stage_rectified)."""
-        out = np.empty((self.h, self.w), np.uint8)
-        check(self._lib.sgm_stage_rectified(self._h, int(view), _ptr(out)), self._h)
-        return out
+        return self._input_image(self._lib.sgm_stage_rectified, view)
 
     def rectify_valid(self, view: int = 0) -> np.ndarray:
         """`view`'s valid mask (sgm_stage_rectify_valid): h x w uint8, 255
@@ -352,10 +358,7 @@ class SGM:
         8192) >> 14: inside the resize or the remap when one is
         set, else as one launch of its own.  Not inside stream capture;
         re-capture graphs."""
-        try:
-            check(self._lib.sgm_set_input_format(self._h, _fmt_code(fmt)), self._h)
-        finally:
-            self._sync_input_shape()
+        self._set_input(self._lib.sgm_set_input_format, _fmt_code(fmt))
 
     @property
     def input_format(self) -> str:
@@ -393,9 +396,7 @@ class SGM:
         """The last frame's grey image of `view` (0 = left, 1 = right) on a
         handle with a colour format: h x w uint8, a host copy
         (sgm_stage_input_gray).  What the point cloud and show_disp read."""
-        out = np.empty((self.h, self.w), np.uint8)
-        check(self._lib.sgm_stage_input_gray(self._h, int(view), _ptr(out)), self._h)
-        return out
+        return self._input_image(self._lib.sgm_stage_input_gray, view)
 
     def check(self) -> None:
         """sgm_check: wait for the frames enqueued so far and raise SGMError

@@ -65,6 +65,58 @@ def test_frame_replays_from_a_hip_graph(h, w, D, views, sky, slant, monkeypatch)
 
 
 @pytest.mark.timeout(120)
+def test_setters_are_rejected_inside_a_capture():
+    # a setter waits for the frames in flight and reallocates buffers the captured launches point
+    # into: each refuses while the handle's stream is capturing, naming itself, changes nothing,
+    # and the capture goes on to a graph that replays the frame
+    import rectify_recipe
+    from stereo_matching_amd import SGMError
+    from stereo_matching_amd._capi import check
+    h, w, D = 96, 260, 128
+    dev = torch.device("cuda", 0)
+    left, right = synthetic.stereo_pair(h, w, D, pair_index=0)
+    maps = [m for v in (0, 1) for m in rectify_recipe.maps(h, w, 37, 53, v)]
+    with SGM(h, w, 1, D, views=1) as sgm:
+        stream = torch.cuda.ExternalStream(sgm.stream, device=dev)
+        d_l = torch.from_numpy(left).to(dev)
+        d_r = torch.from_numpy(right).to(dev)
+        out_e = torch.empty((h, w), dtype=torch.float32, device=dev)
+        out_g = torch.empty_like(out_e)
+
+        def frame(out):
+            sgm.process_device(d_l.data_ptr(), d_r.data_ptr(), out.data_ptr(), stream=stream.cuda_stream)
+
+        setters = (("sgm_set_input_size", lambda: sgm.set_input_size(37, 53)),
+                   ("sgm_set_rectify", lambda: sgm.set_rectify(37, 53, *maps)),
+                   ("sgm_set_input_format", lambda: sgm.set_input_format("bgr8")),
+                   ("sgm_set_min_disp", lambda: check(sgm._lib.sgm_set_min_disp(sgm._h, 8), sgm._h)),
+                   ("sgm_set_confidence", lambda: sgm.set_confidence(True)))
+        state = lambda: (sgm.input_size, sgm.rectify_size, sgm.input_format, sgm.device_bytes)  # noqa: E731
+        with torch.cuda.stream(stream):
+            frame(out_e)  # warm-up (the capture needs no first-call work)
+        torch.cuda.synchronize(dev)
+        before = state()
+        assert before[:3] == ((0, 0), (0, 0), "gray8")
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream, capture_error_mode="relaxed"):
+            frame(out_g)
+            for name, call in setters:
+                with pytest.raises(SGMError) as err:
+                    call()
+                assert name + ":" in str(err.value) and "outside stream capture" in str(err.value)
+                assert state() == before, name
+        torch.cuda.synchronize(dev)
+        assert state() == before
+        with torch.cuda.stream(stream):
+            out_e.zero_()
+            graph.replay()
+            frame(out_e)
+        torch.cuda.synchronize(dev)
+        assert np.array_equal(out_g.cpu().numpy().view(np.uint32), out_e.cpu().numpy().view(np.uint32))
+        assert (out_e.cpu().numpy() <= D - 1).any()
+
+
+@pytest.mark.timeout(120)
 def test_capture_with_post_filter_is_rejected():
     # post_filter's median-fill launch count comes from a counter read back to
     # the host each round, which a capture never runs: the library refuses

@@ -15,15 +15,28 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import pytest
 
+import rectify_recipe
 from stereo_matching_amd import BM, SGM, synthetic
 
 pytestmark = pytest.mark.gpu
 
 SWITCHES = ("SGM_BAND_ROWS", "SGM_SLANT", "SGM_VSTRIP", "SGM_P4_HPAIR", "SGM_CONFIDENCE")
 
-# name: (h, w, D, constructor keywords, (left mask, right mask), environment)
+
+def _maps_37x53(s):
+    s.set_rectify(37, 53, *rectify_recipe.maps(s.h, s.w, 37, 53, 0), *rectify_recipe.maps(s.h, s.w, 37, 53, 1))
+
+
+def _size_and_bgr8(s):
+    s.set_input_size(37, 53)
+    s.set_input_format("bgr8")
+
+
+# name: (h, w, D, constructor keywords, (left mask, right mask), environment[, setter applied after
+# construction: the frame then takes random images of the shape the handle asks for])
 CASES = {
     "joint": (96, 260, 128, {}, (False, False), {}),
     "bands": (96, 260, 128, {}, (False, False), {"SGM_BAND_ROWS": "32"}),
@@ -41,6 +54,12 @@ CASES = {
     # 277 MB per volume: the smallest shape above the Infinity Cache, where
     # SGM_BAND_ROWS=0 runs whole-volume passes and both views' finals at once
     "whole_final2": (512, 1056, 128, {}, (False, False), {"SGM_BAND_ROWS": "0"}),
+    # the input slot (sgm_frame.hip input_slot): one launch in front of the one_view frame, whichever
+    # stages are set
+    "input_size": (96, 260, 128, {"views": 1}, (False, False), {}, lambda s: s.set_input_size(37, 53)),
+    "input_maps": (96, 260, 128, {"views": 1}, (False, False), {}, _maps_37x53),
+    "input_bgr8": (96, 260, 128, {"views": 1}, (False, False), {}, lambda s: s.set_input_format("bgr8")),
+    "input_size_bgr8": (96, 260, 128, {"views": 1}, (False, False), {}, _size_and_bgr8),
 }
 
 # the adaptive median fill's launch count depends on the map
@@ -188,15 +207,23 @@ LEDGERS = {
         "lr": (1, 540672.0),
     },
 }
+# the one_view ledger plus exactly one entry, 2 x 96 x 260 elements: both images in one launch
+for _name, _cls in (("input_size", "resize"), ("input_maps", "rectify"), ("input_bgr8", "gray"),
+                    ("input_size_bgr8", "resize")):
+    LEDGERS[_name] = dict(LEDGERS["one_view"], **{_cls: (1, 49920.0)})
 
 
 def _ledger(name):
     """One frame of case `name` under the environment as it is now."""
-    h, w, D, kw, (sky_l, sky_r), _ = CASES[name]
+    h, w, D, kw, (sky_l, sky_r), _, *setter = CASES[name]
     kw = dict(kw)
     left, right = synthetic.stereo_pair(h, w, D, pair_index=5, kind="road")
     mask = synthetic.sky_mask(h, w)
     with (BM(h, w, 1, D) if kw.pop("bm", False) else SGM(h, w, 1, D, **kw)) as s:
+        if setter:
+            setter[0](s)
+            shape = (s.in_h, s.in_w) if s.in_ch == 1 else (s.in_h, s.in_w, s.in_ch)
+            left, right = np.random.default_rng(5).integers(0, 256, (2,) + shape, dtype=np.uint8)
         s.set_profiling(True)
         s.process(left, right, mask if sky_l else None, mask if sky_r else None)
         prof = s.get_profile()
