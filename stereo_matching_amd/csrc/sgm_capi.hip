@@ -740,8 +740,10 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, cons
                                  h->g.W, view, filters & 1, h->g, h->d_ch[0], h->st));
     const float *res = h->d_ch[0];
     if (filters & 2) {  // the frame's own vfwd, in place when the frames run it so
-        HIPCHK(h, sgm::launch_vfwd(h->d_ch[0], cost_buf(h, 0), vfwd_args(h, 0), h->g, h->st));
-        res = cost_buf(h, 0);
+        const sgm::PairArgs pa = vfwd_args(h, 0);
+        float *out = cost_buf(h, 0);
+        HIPCHK(h, sgm::launch_vfwd(&res, &out, &pa, 1, nullptr, h->g, h->st));
+        res = out;
     }
     HIPCHK(h, hipMemcpyAsync(cost, res, nvol * 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));

@@ -38,6 +38,23 @@ __device__ __forceinline__ int xcd_column(int b, int n) {
     return x * q + (x < r ? x : r) + (b >> 3);
 }
 
+// The arguments of a launch that takes NV (1 or 2) views, one per workgroup y
+// (the chain kernels) or z (the final passes).  NV = 1 is the bare argument
+// struct in the kernarg segment and no select.  (A ternary, not v[id]: the
+// compiler splits the by-value struct only under constant indices.)
+enum ViewAxis { VIEW_Y, VIEW_Z };
+template <class A, int NV>
+struct Views {
+    A v[NV];
+    __device__ __forceinline__ const A &pick(ViewAxis axis = VIEW_Y) const {
+        if constexpr (NV == 1) return v[0];
+        else
+            return (axis == VIEW_Y ? __builtin_amdgcn_workgroup_id_y() : __builtin_amdgcn_workgroup_id_z()) != 0
+                       ? v[1]
+                       : v[0];
+    }
+};
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Hamming distance of two census words as an exact float.  Two 32-bit counts

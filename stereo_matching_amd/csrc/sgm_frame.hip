@@ -5,7 +5,7 @@
 // Concurrency between independent roles comes from sharing a launch (stage
 // A/B), not from streams (the runtime may map streams onto one hardware
 // queue): a frame runs on one stream, at 73.5 B of HBM traffic per
-// pixel-disparity in the per-view schedule (whole_view).
+// pixel-disparity in the per-view schedule (aggregate).
 #include "sgm_handle.h"
 
 #include <stdlib.h>
@@ -85,21 +85,15 @@ int sgm::slant_cus() {
 
 namespace {
 
-// What the aggregation launches of one view take, role by role: the H pair
-// (h1 forward, h2 backward), the diagonal pair (d6, d7), the L5 and L8 sweeps
-// and the final pass.
-struct ViewRoles {
-    PairArgs h1, h2, d6, d7, fin;
-    SweepArgs l5, l8;
-};
+using sgm::ViewRoles;
 
-// The one place that wires the roles to a view's buffers: C (cost_buf), S12
+// The one place that wires the roles (sgm_internal.h) to a view's buffers: C (cost_buf), S12
 // (d_s), T (t_buf) and the checkpoints of each pair family.  disp, sub: where
 // the final pass leaves its maps; sub_cm: sub and the confidence map beside it
 // column-major.  A schedule that has no use for a role ignores it: the 4-path
 // passes have no diagonal checkpoints and their final pass reads no acc_in
 // (pair_split_body's NOT, sgm_bodies.h); the slanted passes take the pointers
-// only.  nt_cost stays 0: only whole_view's own final launch sets it.
+// only.  nt_cost stays 0: only aggregate's one-view final launch sets it.
 ViewRoles view_roles(sgm_handle *h, int view, uint16_t *disp, float *sub, int sub_cm) {
     float **ck = h->d_ck[view];
     float *T = t_buf(h, view);
@@ -132,35 +126,40 @@ ViewRoles view_roles(sgm_handle *h, int view, uint16_t *disp, float *sub, int su
     return r;
 }
 
-// The 8-path aggregation of one view, given the final cost volume and the L3
-// checkpoints (written by vfwd, or by stage_aggregate's PAIR_V forward pass),
-// as three launches on one stream:
+// The 8-path aggregation of nv views (r[0 .. nv)), given each one's final cost
+// volume and L3 checkpoints (written by vfwd, or by stage_aggregate's PAIR_V
+// forward pass), as four launches on one stream:
 //   stage A: L1 fwd (ckpt) | L5 -> T5 | L6 fwd (ckpt)
 //   stage B: L2 bwd: S12 = L1 + L2 | L7 bwd: T = (T5 + L6) + L7
 //   L8:      T += L8
 //   final:   L4 bwd recomputing L3: total = ((S12 + L3) + L4) + T -> WTA
 // (the reference's order, SGM.cpp:386-390).  T may alias the dead
 // horizontally filtered volume.
+// nv = 2, each launch takes both views (workgroup y or z = view): for frames
+// whose two cost volumes fit the 256 MB Infinity Cache together (K64: 2 x 119
+// MB), where one view's launches hold too few chains to fill the chip (the
+// reference runs the views back to back, SGM.cpp:32-801; the results are the
+// same per view).
 // final = false: the caller launches this view's final pass with the other
 // view's.
-int whole_view(sgm_handle *h, const ViewRoles &r, hipStream_t st, bool final) {
+int aggregate(sgm_handle *h, const ViewRoles *r, int nv, hipStream_t st, bool final) {
     const Geom g = h->g;
-    const double elems = vol_elems(g);
-    HIPCHK(h, timed(h, "stage_a", elems, st, [&] { return sgm::launch_stage_a(r.h1, r.l5, r.d6, g, st); }));
-    HIPCHK(h, timed(h, "stage_b", elems, st, [&] { return sgm::launch_stage_b(r.h2, r.d7, g, st); }));
-    HIPCHK(h, timed(h, "sweep_L8_acc", elems, st,
-                    [&] { return sgm::launch_sweep(SGM_DIR_L8, sgm::SWEEP_ACC, r.l8, g, st); }));
+    const double elems = nv * vol_elems(g);
+    HIPCHK(h, timed(h, "stage_a", elems, st, [&] { return sgm::launch_stage_a(r, nv, g, st); }));
+    HIPCHK(h, timed(h, "stage_b", elems, st, [&] { return sgm::launch_stage_b(r, nv, g, st); }));
+    HIPCHK(h, timed(h, "sweep_L8_acc", elems, st, [&] { return sgm::launch_l8(r, nv, g, st); }));
     if (!final) return SGM_OK;
-    // two views: each final pass is the last read of its view's C, and the
-    // other view's volume follows it into the Infinity Cache, so C goes by
-    // non-temporal loads (K128 two views -1.0% paired).  With one view the
-    // next frame's stage A loses what the final pass gains, with one C buffer
-    // or two used alternately (profiles/r06_experiments/r06aa_final_nt.txt,
-    // r06bb_c_alternate.txt), so one-view frames keep default loads
-    PairArgs fin = r.fin;
-    fin.nt_cost = h->nviews == 2;
-    HIPCHK(h, timed(h, "pair_bwd_L4_final", elems, st,
-                    [&] { return sgm::launch_pair_bwd(sgm::PAIR_V, sgm::PAIR_FINAL, fin, g, st); }));
+    // one view of a two-view handle: its final pass is the last read of its
+    // C, and the other view's volume follows it into the Infinity Cache, so C
+    // goes by non-temporal loads (K128 two views -1.0% paired).  With one view
+    // the next frame's stage A loses what the final pass gains, with one C
+    // buffer or two used alternately (profiles/r06_experiments/
+    // r06aa_final_nt.txt, r06bb_c_alternate.txt), so one-view frames keep
+    // default loads
+    ViewRoles one = r[0];
+    one.fin.nt_cost = h->nviews == 2;
+    const ViewRoles *f = nv == 1 ? &one : r;
+    HIPCHK(h, timed(h, "pair_bwd_L4_final", elems, st, [&] { return sgm::launch_final(f, nv, false, g, st); }));
     return SGM_OK;
 }
 
@@ -173,8 +172,10 @@ int whole_view(sgm_handle *h, const ViewRoles &r, hipStream_t st, bool final) {
 int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
     const Geom g = h->g;
     const double elems = vol_elems(g);
-    PairArgs va = vfwd_args(h, view), d6 = r.d6;
-    SweepArgs l5 = r.l5;
+    PairArgs va = vfwd_args(h, view);
+    ViewRoles b = r;
+    const float *in = h->d_ch[view];
+    float *out = cost_buf(h, view);
     // band edges at H - m*BR (multiples of 16 rows from the bottom, as
     // the backward bands): whole segments of every family
     const int H = g.H, FR = h->band_rows;
@@ -183,12 +184,10 @@ int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
         const int rb = H - (m + 1) * FR > 0 ? H - (m + 1) * FR : 0, re = H - m * FR;
         const double be = (double)(re - rb) / H * elems;
         va.band = {rb, re, h->d_carry[view][2]};
-        HIPCHK(h, timed(h, "vfwd", be, st, [&] {
-                   return sgm::launch_vfwd(h->d_ch[view], cost_buf(h, view), va, g, st);
-               }));
-        l5.band = {rb, re, h->d_carry[view][0]};
-        d6.band = {rb, re, h->d_carry[view][1]};
-        HIPCHK(h, timed(h, "stage_a_d", be, st, [&] { return sgm::launch_stage_a_band(l5, d6, g, st); }));
+        HIPCHK(h, timed(h, "vfwd", be, st, [&] { return sgm::launch_vfwd(&in, &out, &va, 1, nullptr, g, st); }));
+        b.l5.band = {rb, re, h->d_carry[view][0]};
+        b.d6.band = {rb, re, h->d_carry[view][1]};
+        HIPCHK(h, timed(h, "stage_a_d", be, st, [&] { return sgm::launch_stage_a_band(&b, g, st); }));
     }
     return SGM_OK;
 }
@@ -196,44 +195,19 @@ int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
 int backward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
     const Geom g = h->g;
     const double elems = vol_elems(g);
-    PairArgs d7 = r.d7, fin = r.fin;
-    SweepArgs l8 = r.l8;
+    ViewRoles b = r;
     const int H = g.H, BR = h->band_rows;
     // bottom band first: the backward passes walk up
     for (int kb = 0; kb < H; kb += BR) {
         const int ke = kb + BR < H ? kb + BR : H;
         const double be = (double)(ke - kb) / H * elems;
-        d7.band = {kb, ke, h->d_carry[view][0]};
-        HIPCHK(h, timed(h, "stage_b_d2", be, st, [&] { return sgm::launch_stage_b(r.h2, d7, g, st); }));
-        l8.band = {kb, ke, h->d_carry[view][1]};
-        fin.band = {kb, ke, h->d_carry[view][2]};
-        HIPCHK(h, timed(h, "sweep_L8_acc", be, st,
-                        [&] { return sgm::launch_sweep(SGM_DIR_L8, sgm::SWEEP_ACC, l8, g, st); }));
-        HIPCHK(h, timed(h, "pair_bwd_L4_final", be, st, [&] {
-                   return sgm::launch_pair_bwd(sgm::PAIR_V, sgm::PAIR_FINAL, fin, g, st);
-               }));
+        b.d7.band = {kb, ke, h->d_carry[view][0]};
+        HIPCHK(h, timed(h, "stage_b_d2", be, st, [&] { return sgm::launch_stage_b(&b, 1, g, st); }));
+        b.l8.band = {kb, ke, h->d_carry[view][1]};
+        b.fin.band = {kb, ke, h->d_carry[view][2]};
+        HIPCHK(h, timed(h, "sweep_L8_acc", be, st, [&] { return sgm::launch_l8(&b, 1, g, st); }));
+        HIPCHK(h, timed(h, "pair_bwd_L4_final", be, st, [&] { return sgm::launch_final(&b, 1, false, g, st); }));
     }
-    return SGM_OK;
-}
-
-// Both views' aggregation as joint launches (grid.y = view): stage A, stage
-// B, the L8 sweep and the final pass each take both views at once.  For frames
-// whose two cost volumes fit the 256 MB Infinity Cache together (K64: 2 x 119
-// MB), where one view's launches hold too few chains to fill the chip (the
-// reference runs the views back to back, SGM.cpp:32-801; the results are the
-// same per view).
-int aggregate_joint(sgm_handle *h, const ViewRoles *r, hipStream_t st) {
-    const Geom g = h->g;
-    const double elems2 = 2.0 * vol_elems(g);
-    const PairArgs h1[2] = {r[0].h1, r[1].h1}, h2[2] = {r[0].h2, r[1].h2};
-    const PairArgs d6[2] = {r[0].d6, r[1].d6}, d7[2] = {r[0].d7, r[1].d7};
-    const SweepArgs l5[2] = {r[0].l5, r[1].l5};
-    HIPCHK(h, timed(h, "stage_a", elems2, st, [&] { return sgm::launch_stage_a2(h1, l5, d6, g, st); }));
-    HIPCHK(h, timed(h, "stage_b", elems2, st, [&] { return sgm::launch_stage_b2(h2, d7, g, st); }));
-    HIPCHK(h, timed(h, "sweep_L8_acc", elems2, st,
-                    [&] { return sgm::launch_sweep2_l8(r[0].l8, r[1].l8, g, st); }));
-    HIPCHK(h, timed(h, "pair_bwd_L4_final", elems2, st,
-                    [&] { return sgm::launch_final2(r[0].fin, r[1].fin, g, st); }));
     return SGM_OK;
 }
 
@@ -249,18 +223,16 @@ int aggregate_joint(sgm_handle *h, const ViewRoles *r, hipStream_t st) {
 int aggregate4(sgm_handle *h, int nv, const ViewRoles *r, hipStream_t st) {
     const Geom g = h->g;
     const double elems = vol_elems(g);
-    const ViewRoles &r1 = r[nv - 1];  // (one view: the second slot repeats the first, unused)
-    const PairArgs h1[2] = {r[0].h1, r1.h1}, h2[2] = {r[0].h2, r1.h2}, fin[2] = {r[0].fin, r1.fin};
     if (h->p4_split) {
         HIPCHK(h, timed(h, "hpair4_fwd", nv * elems, st,
-                        [&] { return sgm::launch_h_fwd4(h1, nv, g, st); }));
+                        [&] { return sgm::launch_h_fwd4(r, nv, g, st); }));
         HIPCHK(h, timed(h, "hpair4_bwd", nv * elems, st,
-                        [&] { return sgm::launch_h_bwd4(h2, nv, g, st); }));
+                        [&] { return sgm::launch_h_bwd4(r, nv, g, st); }));
     } else {
         HIPCHK(h, timed(h, "hpair4", nv * elems, st,
-                        [&] { return sgm::launch_hpair4(h1, h2, nv, g, st); }));
+                        [&] { return sgm::launch_hpair(r, nv, false, g, st); }));
     }
-    HIPCHK(h, timed(h, "final4", nv * elems, st, [&] { return sgm::launch_final4(fin, nv, g, st); }));
+    HIPCHK(h, timed(h, "final4", nv * elems, st, [&] { return sgm::launch_final(r, nv, true, g, st); }));
     return SGM_OK;
 }
 
@@ -276,9 +248,9 @@ int cost_view(sgm_handle *h, int view, int dsi, const uint8_t *sky, int sky_pitc
            }));
     if (!vfwd) return SGM_OK;
     const PairArgs pa = vfwd_args(h, view);
-    HIPCHK(h, timed(h, "vfwd", elems, st, [&] {
-               return sgm::launch_vfwd(h->d_ch[view], cost_buf(h, view), pa, h->g, st);
-           }));
+    const float *in = h->d_ch[view];
+    float *out = cost_buf(h, view);
+    HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &out, &pa, 1, nullptr, h->g, st); }));
     return SGM_OK;
 }
 
@@ -343,19 +315,11 @@ int slant_views(sgm_handle *h, const ViewRoles *r, hipStream_t st, bool have_c) 
     const Geom g = h->g;
     const int nv = h->nviews;
     const double elems = vol_elems(g);
-    const PairArgs hp1[2] = {r[0].h1, r[nv - 1].h1}, hp2[2] = {r[0].h2, r[nv - 1].h2};
     sgm::SlantArgs sa{};
-    if (have_c) {
-    } else if (nv == 2) {  // both views in one launch
-        const sgm::PairArgs pa[2] = {pair_args(h), pair_args(h)};
-        const float *in[2] = {h->d_ch[0], h->d_ch[1]};
-        float *out[2] = {h->d_c[0], h->d_c[1]}, *l3[2] = {h->d_l3[0], h->d_l3[1]};
-        HIPCHK(h, timed(h, "vfwd_l3", 2 * elems, st, [&] { return sgm::launch_vfwd2_l3(in, out, l3, pa, g, st); }));
-    } else {
-        const sgm::PairArgs pa = pair_args(h);
-        HIPCHK(h, timed(h, "vfwd_l3", elems, st, [&] {
-                   return sgm::launch_vfwd_l3(h->d_ch[0], h->d_c[0], h->d_l3[0], pa, g, st);
-               }));
+    if (!have_c) {  // the views in one launch
+        const PairArgs pa[2] = {pair_args(h), pair_args(h)};
+        HIPCHK(h, timed(h, "vfwd_l3", nv * elems, st,
+                        [&] { return sgm::launch_vfwd(h->d_ch, h->d_c, pa, nv, h->d_l3, g, st); }));
     }
     for (int v = 0; v < nv; ++v) {
         const PairArgs &fin = r[v].fin;
@@ -400,7 +364,7 @@ int slant_views(sgm_handle *h, const ViewRoles *r, hipStream_t st, bool have_c) 
             HIPCHK(h, timed(h, "slant_down", nv * elems, st, [&] { return sgm::launch_slant_down(sa, g, st); }));
         if (strcmp(solo, "down") != 0)
             HIPCHK(h, timed(h, "stage_a_h", nv * elems, st,
-                            [&] { return sgm::launch_stage_a_hpair(hp1, hp2, nv, g, st); }));
+                            [&] { return sgm::launch_hpair(r, nv, true, g, st); }));
         HIPCHK(h, timed(h, "slant_up", nv * elems, st, [&] { return sgm::launch_slant_up(sa, g, st); }));
         return SGM_OK;
     }
@@ -412,7 +376,7 @@ int slant_views(sgm_handle *h, const ViewRoles *r, hipStream_t st, bool have_c) 
             e = timed(h, "slant_down", nv * elems, st, [&] { return sgm::launch_slant_down(sa, g, st); });
         if (e == hipSuccess)
             e = timed(h, "stage_a_h", nv * elems, h->st_h,
-                      [&] { return sgm::launch_stage_a_hpair(hp1, hp2, nv, g, h->st_h); });
+                      [&] { return sgm::launch_hpair(r, nv, true, g, h->st_h); });
         if (e == hipSuccess) e = hipEventRecord(h->ev_join, h->st_h);
         if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_join, 0);
         return e;
@@ -520,7 +484,8 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
             const PairArgs pa[2] = {vfwd_args(h, v0), vfwd_args(h, v1)};
             const float *in[2] = {h->d_ch[v0], h->d_ch[v1]};
             float *out[2] = {cost_buf(h, v0), cost_buf(h, v1)};
-            HIPCHK(h, timed(h, "vfwd", 2.0 * npx * g.D, st, [&] { return sgm::launch_vfwd2(in, out, pa, g, st); }));
+            HIPCHK(h, timed(h, "vfwd", 2.0 * npx * g.D, st,
+                            [&] { return sgm::launch_vfwd(in, out, pa, 2, nullptr, g, st); }));
         }
     } else {
         if (h->nviews == 2 && (rc = cost_view(h, 1, 1, d_sky_r, sky_pitch, st, vfwd_here)) != SGM_OK)
@@ -585,7 +550,7 @@ int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
     // the L3 checkpoints from the final volume (frames get them from vfwd)
     HIPCHK(h, timed(h, "pair_fwd_L3", vol_elems(h->g), st,
                     [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r.fin, h->g, st); }));
-    return h->paths4 ? aggregate4(h, 1, &r, st) : whole_view(h, r, st, true);
+    return h->paths4 ? aggregate4(h, 1, &r, st) : aggregate(h, &r, 1, st, true);
 }
 
 int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
@@ -614,15 +579,13 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
     switch (h->sched) {
     case SCHED_PATHS4: rc = aggregate4(h, nv, r, st); break;
     case SCHED_SLANT: rc = slant_views(h, r, st, have_c); break;
-    case SCHED_JOINT: rc = aggregate_joint(h, r, st); break;
+    case SCHED_JOINT: rc = aggregate(h, r, 2, st, true); break;
     case SCHED_BANDS: {
         // the views' forward bands, then their H pairs in one launch, then
         // each view's backward bands
         for (int v = 0; v < nv; ++v)
             if ((rc = forward_bands(h, v, r[v], st)) != SGM_OK) return rc;
-        const PairArgs h1[2] = {r[0].h1, r[nv - 1].h1}, h2[2] = {r[0].h2, r[nv - 1].h2};
-        HIPCHK(h, timed(h, "stage_a_h", nv * elems, st,
-                        [&] { return sgm::launch_stage_a_hpair(h1, h2, nv, g, st); }));
+        HIPCHK(h, timed(h, "stage_a_h", nv * elems, st, [&] { return sgm::launch_hpair(r, nv, true, g, st); }));
         for (int v = 0; v < nv; ++v)
             if ((rc = backward_bands(h, v, r[v], st)) != SGM_OK) return rc;
         break;
@@ -632,12 +595,12 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
         // nothing is gained by finishing the left view first, so both
         // views' final passes run as one launch (fewer workgroup rounds)
         for (int v = 0; v < 2; ++v)
-            if ((rc = whole_view(h, r[v], st, false)) != SGM_OK) return rc;
+            if ((rc = aggregate(h, &r[v], 1, st, false)) != SGM_OK) return rc;
         HIPCHK(h, timed(h, "pair_bwd_L4_final", 2.0 * elems, st,
-                        [&] { return sgm::launch_final2(r[0].fin, r[1].fin, g, st); }));
+                        [&] { return sgm::launch_final(r, 2, false, g, st); }));
         break;
     case SCHED_PER_VIEW:
-        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = whole_view(h, r[v], st, true);
+        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
         break;
     }
     if (rc != SGM_OK) return rc;

@@ -1,5 +1,6 @@
-// sgm_internal.h -- kernel launchers shared by the host side (sgm_capi.hip,
-// sgm_frame.hip) and the kernel files.  Not part of the public interface.
+// sgm_internal.h -- kernel launchers and their argument structs (one view's
+// roles: ViewRoles) shared by the host side (sgm_capi.hip, sgm_frame.hip) and
+// the kernel files.  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,52 +107,52 @@ struct PairArgs {
                          // last read of a view's C when the other view's follows
 };
 
+// What the aggregation launches of one view take, role by role: the H pair
+// (h1 forward, h2 backward), the diagonal pair (d6, d7), the L5 and L8 sweeps
+// and the final pass (sgm_frame.hip's view_roles wires them to the buffers).
+struct ViewRoles {
+    PairArgs h1, h2, d6, d7, fin;
+    SweepArgs l5, l8;
+};
+
 // floats of checkpoint storage a family needs
 size_t pair_ckpt_floats(int family, Geom g);
+// single roles (the sgm_stage_* parity entry points)
 hipError_t launch_pair_fwd(int family, const PairArgs &a, Geom g, hipStream_t st);
 hipError_t launch_pair_bwd(int family, int mode, const PairArgs &a, Geom g, hipStream_t st);
-// both views' vfwd writing C and L3 (the slanted schedule), workgroup y = view
-hipError_t launch_vfwd2_l3(const float *const *in, float *const *out, float *const *l3, const PairArgs *a,
-                           Geom g, hipStream_t st);
-// both views' vfwd (C and the L3 checkpoints, a[v].ckpt) in one launch
-hipError_t launch_vfwd2(const float *const *in, float *const *out, const PairArgs *a, Geom g, hipStream_t st);
-// the PAIR_V/PAIR_FINAL pass of two views in one launch
-hipError_t launch_final2(const PairArgs &a0, const PairArgs &a1, Geom g, hipStream_t st);
-// Multi-role launches of the frame schedule (sgm_pair.hip); banded stage B
-// launches (d7.band) run no H rows (the banded schedule's H pair is its own
-// launch)
-hipError_t launch_stage_a(const PairArgs &h1, const SweepArgs &l5, const PairArgs &d6, Geom g,
-                          hipStream_t st);
-hipError_t launch_stage_b(const PairArgs &h2, const PairArgs &d7, Geom g, hipStream_t st);
-// both views' stage A / stage B / L8 sweep in one launch each (grid.y = view;
-// arrays of two)
-hipError_t launch_stage_a2(const PairArgs *h1, const SweepArgs *l5, const PairArgs *d6, Geom g,
-                           hipStream_t st);
-hipError_t launch_stage_b2(const PairArgs *h2, const PairArgs *d7, Geom g, hipStream_t st);
-hipError_t launch_sweep2_l8(const SweepArgs &a0, const SweepArgs &a1, Geom g, hipStream_t st);
-// the forward bands (DESIGN.md "Bands"): the whole H pair (L1 fwd, then L2
-// bwd -> h2[v].out) of nviews views as one launch, and one band (l5.band, d6.band)
-// of stage A's diagonal roles (L5 -> T5, L6 fwd)
-hipError_t launch_stage_a_hpair(const PairArgs *h1, const PairArgs *h2, int nviews, Geom g,
-                                hipStream_t st);
-hipError_t launch_stage_a_band(const SweepArgs &l5, const PairArgs &d6, Geom g, hipStream_t st);
-// 4-path frames (params.paths == 4), nviews views per launch, C
-// by default loads.  The H pair as one launch (one wave per row: L1 forward,
-// then L2 backward -> h2[v].out), or as a forward launch and a two-wave
-// backward launch; the final pass without the T stream (a[v].acc_in unused):
-// total = (s_in + L3) + L4 -> WTA, sub-pixel
-hipError_t launch_hpair4(const PairArgs *h1, const PairArgs *h2, int nviews, Geom g, hipStream_t st);
-hipError_t launch_h_fwd4(const PairArgs *h1, int nviews, Geom g, hipStream_t st);
-hipError_t launch_h_bwd4(const PairArgs *h2, int nviews, Geom g, hipStream_t st);
-hipError_t launch_final4(const PairArgs *a, int nviews, Geom g, hipStream_t st);
-// cost_vertical_filter (Solver.cpp:333-368) fused with the L3 forward pass:
-// in = horizontally filtered volume, out = final cost volume, a.ckpt = L3
-// checkpoints.
-hipError_t launch_vfwd(const float *in, float *out, const PairArgs &a, Geom g, hipStream_t st);
-// the same vertical IIR + L3, writing every row's L3 to the volume l3 (the
-// slanted schedule's bottom-up pass reads it) instead of checkpoints
-hipError_t launch_vfwd_l3(const float *in, float *out, float *l3, const PairArgs &a, Geom g,
-                          hipStream_t st);
+// The launches of the frame schedules (sgm_pair.hip, sgm_sweep.hip), each over
+// the nviews (1 or 2) views r[0 .. nviews): one launcher per role, workgroup y
+// (the final passes: z) = view.
+// Stage A: L1 fwd | L5 -> T5 | L6 fwd; stage B: L2 bwd -> S12 | L7 bwd -> T.
+// A banded stage B (r->d7.band, one view) runs no H rows: the banded
+// schedule's H pair is its own launch.
+hipError_t launch_stage_a(const ViewRoles *r, int nviews, Geom g, hipStream_t st);
+hipError_t launch_stage_b(const ViewRoles *r, int nviews, Geom g, hipStream_t st);
+// one forward band (r->l5.band, r->d6.band) of stage A's diagonal roles
+// (DESIGN.md "Bands")
+hipError_t launch_stage_a_band(const ViewRoles *r, Geom g, hipStream_t st);
+// T += L8 (one view: launch_sweep's choice of body, bands included)
+hipError_t launch_l8(const ViewRoles *r, int nviews, Geom g, hipStream_t st);
+// The final pass, total = ((s_in + L3) + L4) + acc_in -> WTA, sub-pixel.  One
+// view: banded by r->fin.band, C by non-temporal loads by r->fin.nt_cost.
+// paths4 (params.paths == 4): without the T stream (acc_in
+// unused), total = (s_in + L3) + L4.
+hipError_t launch_final(const ViewRoles *r, int nviews, bool paths4, Geom g, hipStream_t st);
+// The whole H pair as one launch (one wave per row: L1 forward, then L2
+// backward -> r[v].h2.out); nt_cost: C by non-temporal loads (the banded and
+// slanted schedules) or default loads (4-path frames)
+hipError_t launch_hpair(const ViewRoles *r, int nviews, bool nt_cost, Geom g, hipStream_t st);
+// 4-path frames: the H pair as a forward launch and a two-wave backward
+// launch, C by default loads
+hipError_t launch_h_fwd4(const ViewRoles *r, int nviews, Geom g, hipStream_t st);
+hipError_t launch_h_bwd4(const ViewRoles *r, int nviews, Geom g, hipStream_t st);
+// cost_vertical_filter (Solver.cpp:333-368) fused with the L3 forward pass of
+// nviews views: in[v] = horizontally filtered volume, out[v] = final cost
+// volume; a[v].ckpt takes the L3 checkpoints (l3 null; one view: banded by
+// a->band), or l3[v] every row's L3 (the slanted schedule's bottom-up pass
+// reads the volume)
+hipError_t launch_vfwd(const float *const *in, float *const *out, const PairArgs *a, int nviews,
+                       float *const *l3, Geom g, hipStream_t st);
 
 // ----------------------------------------------- slanted tiles (sgm_slant.hip)
 // Compute waves per tile; one more wave per workgroup, the receiver, turns

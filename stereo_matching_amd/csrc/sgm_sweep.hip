@@ -22,24 +22,11 @@
 
 namespace sgm {
 
-template <int DIR, int V, int MODE, bool FULL, int PF, bool BAND = false>
-__global__ __launch_bounds__(64) void sweep_kernel(SweepArgs a, Geom g) {
-    sweep_body<DIR, V, MODE, FULL, PF, BAND>(a, g, bid_x());
-}
-
-// The same sweep over both views' volumes (workgroup y = view): the L8 pass
-// of frames whose two cost volumes fit the Infinity Cache together (K64).
-template <int DIR, int V, int MODE, bool FULL, int PF>
-__global__ __launch_bounds__(64) void sweep2_kernel(SweepArgs a0, SweepArgs a1, Geom g) {
-    sweep_body<DIR, V, MODE, FULL, PF>(__builtin_amdgcn_workgroup_id_y() != 0 ? a1 : a0, g, bid_x());
-}
-
-hipError_t launch_sweep2_l8(const SweepArgs &a0, const SweepArgs &a1, Geom g, hipStream_t st) {
-    const dim3 grid(g.W, 2);
-    for_width(g.D, [&](auto V, auto FULL) {
-        sweep2_kernel<7, V, SWEEP_ACC, FULL, pf_cols<V>()><<<grid, 64, 0, st>>>(a0, a1, g);
-    });
-    return hipGetLastError();
+// NV = 2: the same sweep over both views' volumes (workgroup y = view), the L8
+// pass of frames whose two cost volumes fit the Infinity Cache together (K64).
+template <int DIR, int V, int MODE, bool FULL, int PF, int NV = 1, bool BAND = false>
+__global__ __launch_bounds__(64) void sweep_kernel(Views<SweepArgs, NV> a, Geom g) {
+    sweep_body<DIR, V, MODE, FULL, PF, BAND>(a.pick(), g, bid_x());
 }
 
 // Diagonal INIT/ACC sweeps (the L8 pass): memory wave + DP wave
@@ -76,11 +63,11 @@ static void launch_sweep_v(const SweepArgs &a, Geom g, hipStream_t st) {
                 return;
             }
             if (a.band.ke > 0) {  // one band (L7/L8: backward bands; L5/L6: forward bands)
-                sweep_kernel<DIR, V, MODE, FULL, PF, true><<<grid, 64, 0, st>>>(a, g);
+                sweep_kernel<DIR, V, MODE, FULL, PF, 1, true><<<grid, 64, 0, st>>>({{a}}, g);
                 return;
             }
         }
-        sweep_kernel<DIR, V, MODE, FULL, PF><<<grid, 64, 0, st>>>(a, g);
+        sweep_kernel<DIR, V, MODE, FULL, PF><<<grid, 64, 0, st>>>({{a}}, g);
     });
 }
 
@@ -105,6 +92,15 @@ hipError_t launch_sweep(int dir, int mode, const SweepArgs &a, Geom g, hipStream
     case SWEEP_ACC: launch_sweep_m<SWEEP_ACC>(dir, a, g, st); break;
     default: return hipErrorInvalidValue;  // the final pass is pair_final_kernel
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_l8(const ViewRoles *r, int nviews, Geom g, hipStream_t st) {
+    if (nviews == 1) return launch_sweep(7, SWEEP_ACC, r->l8, g, st);
+    const dim3 grid(g.W, 2);
+    for_width(g.D, [&](auto V, auto FULL) {
+        sweep_kernel<7, V, SWEEP_ACC, FULL, pf_cols<V>(), 2><<<grid, 64, 0, st>>>({{r[0].l8, r[1].l8}}, g);
+    });
     return hipGetLastError();
 }
 

@@ -72,9 +72,8 @@ def test_gpus_must_match_world_size():
 # instantiation the library holds must map to a profiler name, so that the PMC
 # passes (tools/pmc_reduce.py) and the timer check see each launch of a frame
 FRAME_KERNELS = ("census_kernel<", "cost_h_kernel<", "cost_h2_kernel<", "cost_h_global_kernel<",
-                 "vfwd_kernel<", "vfwd2_kernel<", "stage_a_kernel<", "stage_a2_kernel<", "stage_b_kernel<",
-                 "stage_b2_kernel<", "hpair_kernel<", "sweep_kernel<7", "sweep2_kernel<7",
-                 "sweep_split_kernel<7", "pair_final_kernel<", "pair_final2_kernel<", "slant_kernel<",
+                 "vfwd_kernel<", "vfwd2_kernel<", "stage_a_kernel<", "stage_b_kernel<", "stage_b2_kernel<",
+                 "hpair_kernel<", "h_fwd_kernel<", "h_bwd2_kernel<", "sweep_kernel<7", "sweep_split_kernel<7", "pair_final_kernel<", "slant_kernel<",
                  "lr_kernel(", "lr_cm_kernel(", "lk_refine_kernel(", "median_fill_kernel<",
                  "cost_ck_kernel<", "vstrip_kernel<")
 

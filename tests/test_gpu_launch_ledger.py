@@ -9,7 +9,9 @@ shape that reaches it.  The bit-exact tests pin what the launches compute;
 this one pins which launches run.
 
 The table was recorded from the library as it was before the schedules moved
-out of sgm_capi.hip (`python tests/test_gpu_launch_ledger.py` prints it).
+out of sgm_capi.hip (`python tests/test_gpu_launch_ledger.py` prints it);
+slant_v1_cost_h and per_view_v2 from the library as it was before the one- and
+two-view launchers became one per role.
 """
 from __future__ import annotations
 
@@ -44,6 +46,8 @@ CASES = {
     "one_view_bands": (96, 260, 128, {"views": 1}, (False, False), {"SGM_BAND_ROWS": "32"}),
     "slant_strips": (80, 240, 256, {}, (True, True), {"SGM_SLANT": "1"}),
     "slant_cost_h": (80, 240, 256, {}, (True, True), {"SGM_SLANT": "1", "SGM_VSTRIP": "0"}),
+    # one view: the same vfwd_l3 launch with one view
+    "slant_v1_cost_h": (80, 240, 256, {"views": 1}, (False, False), {"SGM_SLANT": "1", "SGM_VSTRIP": "0"}),
     "left_mask": (100, 300, 64, {}, (True, False), {}),
     "paths4_v1_one_launch": (96, 260, 128, {"paths": 4, "views": 1}, (False, False), {"SGM_P4_HPAIR": "0"}),
     "paths4_v1_split": (96, 260, 128, {"paths": 4, "views": 1}, (False, False), {"SGM_P4_HPAIR": "1"}),
@@ -54,6 +58,9 @@ CASES = {
     # 277 MB per volume: the smallest shape above the Infinity Cache, where
     # SGM_BAND_ROWS=0 runs whole-volume passes and both views' finals at once
     "whole_final2": (512, 1056, 128, {}, (False, False), {"SGM_BAND_ROWS": "0"}),
+    # 135.2 MB per volume: the smallest shape whose volumes fit the Infinity Cache one at a time
+    # but not together, where two views run whole-volume passes view after view
+    "per_view_v2": (264, 500, 256, {}, (False, False), {}),
     # the input slot (sgm_frame.hip input_slot): one launch in front of the one_view frame, whichever
     # stages are set
     "input_size": (96, 260, 128, {"views": 1}, (False, False), {}, lambda s: s.set_input_size(37, 53)),
@@ -126,6 +133,15 @@ LEDGERS = {
         "slant_down_hpair": (1, 9830400.0),
         "slant_up": (1, 9830400.0),
         "lr": (1, 19200.0),
+    },
+    "slant_v1_cost_h": {
+        "census": (1, 38400.0),
+        "cost_h": (1, 4915200.0),
+        "vfwd_l3": (1, 4915200.0),
+        "slant_down": (1, 4915200.0),
+        "stage_a_h": (1, 4915200.0),
+        "slant_down_hpair": (1, 4915200.0),
+        "slant_up": (1, 4915200.0),
     },
     "left_mask": {
         "census": (1, 60000.0),
@@ -205,6 +221,16 @@ LEDGERS = {
         "sweep_L8_acc": (2, 69206016.0),
         "pair_bwd_L4_final": (1, 138412032.0),
         "lr": (1, 540672.0),
+    },
+    "per_view_v2": {
+        "census": (1, 264000.0),
+        "cost_h": (1, 67584000.0),
+        "vfwd": (1, 67584000.0),
+        "stage_a": (2, 33792000.0),
+        "stage_b": (2, 33792000.0),
+        "sweep_L8_acc": (2, 33792000.0),
+        "pair_bwd_L4_final": (2, 33792000.0),
+        "lr": (1, 132000.0),
     },
 }
 # the one_view ledger plus exactly one entry, 2 x 96 x 260 elements: both images in one launch

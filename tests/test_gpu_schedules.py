@@ -60,7 +60,7 @@ def test_schedules_match_default(h, w, D, sky_l, sky_r, env):
 def test_whole_volume_joint_final_matches_bands():
     # 512 x 1056 x 128 f32 = 277 MB per volume: above the Infinity Cache, so
     # the default runs bands; SGM_BAND_ROWS=0 runs whole-volume passes with
-    # both views' final passes in one launch (pair_final2_kernel)
+    # both views' final passes in one launch (pair_final_kernel, NV = 2)
     h, w, D = 512, 1056, 128
     assert h * w * D * 4 > 256 * 1024 * 1024
     base = _run(h, w, D, False, False, {})

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # kernel symbol -> name used by the library's in-process profiler (bench.py)
 NAMES = [("hpair_kernel", "stage_a_h"), ("stage_a_kernel", "stage_a"), ("stage_b_kernel", "stage_b"),
-         ("pair_final_kernel", "pair_bwd_L4_final"), ("pair_final2_kernel", "pair_bwd_L4_final"),
+         ("pair_final_kernel", "pair_bwd_L4_final"),
          ("vfwd_kernel", "vfwd"), ("cost_h_kernel", "cost_h"), ("cost_h2_kernel", "cost_h"),
          ("cost_h_global_kernel", "cost_h"), ("cost_ck_kernel", "cost_ck"), ("vstrip_kernel", "vstrip"),
          ("sky_words_kernel", "sky_words"),
@@ -27,36 +27,40 @@ NAMES = [("hpair_kernel", "stage_a_h"), ("stage_a_kernel", "stage_a"), ("stage_b
          ("cc_apply_kernel", "post_cc_apply"), ("pf_prep_kernel", "post_prep"),
          ("lk_refine_kernel", "lk_refine"), ("sky_columns_kernel", "sky_columns"),
          ("sky_gray_kernel", "sky_gray"), ("bm_wta_kernel", "bm_wta"),
-         # joint two-view launches (K64)
-         ("stage_a2_kernel", "stage_a"), ("stage_b2_kernel", "stage_b"), ("sweep2_kernel<7", "sweep_L8_acc")]
+         # 4-path frames' split H pair
+         ("h_fwd_kernel", "hpair4_fwd"), ("h_bwd2_kernel", "hpair4_bwd"),
+         # two-view kernels of their own
+         ("stage_b2_kernel", "stage_b")]
+
+
+def targ(name, key, i):
+    """Template argument i of kernel `key` in a demangled symbol (None: another kernel, or fewer arguments)."""
+    if key not in name:
+        return None
+    args = name[name.index(key) + len(key):].split(">")[0].split(", ")
+    return args[i] if i < len(args) else None
 
 
 def short(name):
-    # the forward bands' diagonal stage A launches (template ROLES 1)
-    key = "stage_a_kernel<"
-    if key in name:
-        args = name[name.index(key) + len(key):].split(">")[0].split(", ")
-        if len(args) == 4 and args[3] == "1":
-            return "stage_a_d"
-        if len(args) == 4 and args[2] == "true":
-            return "stage_a_hp"
-    # the banded schedule's stage kernels (template flag HP / HROWS)
-    for key, flag, val in (("stage_a_kernel<", "true", "stage_a_hp"), ("stage_b_kernel<", "false", "stage_b_d2")):
-        if key in name:
-            args = name[name.index(key) + len(key):].split(">")[0].split(", ")
-            if len(args) == 3 and args[2] == flag:
-                return val
-    # the slanted passes, and vfwd writing the whole L3 volume (template L3OUT)
+    # (stage A, the finals, the L8 sweep and h_fwd carry the view count NV: one name for both)
+    # stage_a_kernel<V, FULL, NV, ROLES>: ROLES 1 the forward bands' diagonal launches
+    if targ(name, "stage_a_kernel<", 3) == "1":
+        return "stage_a_d"
+    # stage_b_kernel<V, FULL, HROWS>: without H rows the banded schedule's
+    if targ(name, "stage_b_kernel<", 2) == "false":
+        return "stage_b_d2"
+    # the slanted passes
     if "slant_kernel<" in name:
         return "slant_up" if name.split("slant_kernel<")[1].startswith("true") else "slant_down"
-    # (vfwd2_kernel<V, FULL, WIN, PF, L3OUT>: both views in one launch)
+    # vfwd_kernel<V, FULL, WIN, PF, BAND, L3OUT>, vfwd2_kernel<V, FULL, WIN, PF, L3OUT> (both views in one
+    # launch): L3OUT writes the whole L3 volume
+    if targ(name, "vfwd_kernel<", 5) == "true" or targ(name, "vfwd2_kernel<", 4) == "true":
+        return "vfwd_l3"
     if "vfwd2_kernel<" in name:
-        args = name[name.index("vfwd2_kernel<") + len("vfwd2_kernel<"):].split(">")[0].split(", ")
-        return "vfwd_l3" if len(args) >= 5 and args[4] == "true" else "vfwd"
-    if "vfwd_kernel<" in name:
-        args = name[name.index("vfwd_kernel<") + len("vfwd_kernel<"):].split(">")[0].split(", ")
-        if len(args) >= 6 and args[5] == "true":
-            return "vfwd_l3"
+        return "vfwd"
+    # pair_final_kernel<V, FULL, NV, BAND, NTC, NOT>: NOT the 4-path frames' final
+    if targ(name, "pair_final_kernel<", 5) == "true":
+        return "final4"
     for key, val in NAMES:
         if key in name:
             return val
