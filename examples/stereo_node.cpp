@@ -10,6 +10,7 @@
 //   get_disp()                    node.cpp:104     -> OUT_disp.f32 (raw float32 rows)
 //   show_disp(debug_view)         node.cpp:107-110 -> OUT_debug.ppm (the node's imwrite)
 //   point cloud                   node.cpp:113-143 -> OUT_cloud.bin (N x 3 float64 + N u8)
+//   reprojection (Q.f64)          (not in the node) -> OUT_xyz.f32, OUT_depth.f32 (set_reproject)
 //
 // The configured size (node.cpp:19-20 g_img_w, g_img_h) is the images' size
 // unless img_w img_h are given: then the solver is built at that size and both
@@ -29,8 +30,16 @@
 // the remap when one is on.  The sky detector sees HipSolver::gray's images, the
 // debug view and the cloud read the grey image the frame matched.
 //
+// With max_range Q.f64 -- stereoRectify's 4 x 4 Q as 16 doubles, row-major, the
+// fifteenth argument, after the range beyond which a depth is missing (0: none)
+// -- every frame also reprojects its map on the GPU, and the node writes the
+// organized XYZ image (float32 x 3 per pixel, NaN where missing) and the depth
+// image (float32) it would publish as PointCloud2 and sensor_msgs/Image 32FC1
+// (INTEGRATION.md).  In that form img_w img_h may be 0 0 (the images' size) and
+// MAPS.f32 may be - (no maps).
+//
 // usage: stereo_node LEFT.pgm RIGHT.pgm OUT_PREFIX
-//                    [scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32]]]]]
+//                    [scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32 [max_range Q.f64]]]]]]
 // min_disp (not in the node): search disparities [min_disp, min_disp + max_disp);
 // the map, the debug view and the cloud are then in true disparity.
 #include "sgm_amd/SGM.h"
@@ -78,10 +87,10 @@ static bool write_ppm(const std::string &path, const Mat &bgr) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 4 && argc != 6 && argc != 10 && argc != 11 && argc != 13 && argc != 14) {
+    if (argc != 4 && argc != 6 && argc != 10 && argc != 11 && argc != 13 && argc != 14 && argc != 16) {
         std::fprintf(stderr,
                      "usage: %s LEFT.pgm RIGHT.pgm OUT_PREFIX "
-                     "[scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32]]]]]\n",
+                     "[scale max_disp [fx fy cx cy [min_disp [img_w img_h [MAPS.f32 [max_range Q.f64]]]]]]\n",
                      argv[0]);
         return 2;
     }
@@ -104,8 +113,11 @@ int main(int argc, char **argv) {
         return 2;
     }
     // node.cpp:19-20 g_img_w, g_img_h (default: the images' size, nothing to resize)
-    const int w = argc > 12 ? std::atoi(argv[11]) : img_l.cols;
-    const int h = argc > 12 ? std::atoi(argv[12]) : img_l.rows;
+    // (with a Q.f64: 0 0 = the images' size, and - for MAPS.f32 = no maps)
+    const bool sized = argc > 12 && !(argc > 15 && std::atoi(argv[11]) == 0 && std::atoi(argv[12]) == 0);
+    const bool rectify = argc > 13 && !(argc > 15 && std::string(argv[13]) == "-");
+    const int w = sized ? std::atoi(argv[11]) : img_l.cols;
+    const int h = sized ? std::atoi(argv[12]) : img_l.rows;
     std::printf("left size: %d, %d\nright size: %d, %d\n", img_l.rows, img_l.cols, img_r.rows,
                 img_r.cols);
 
@@ -121,7 +133,7 @@ int main(int argc, char **argv) {
         sgm->gray(raw_l, img_l, SGM_PIX_RGB8);
         sgm->gray(raw_r, img_r, SGM_PIX_RGB8);
     }
-    if (argc > 13) {  // rectify instead: the maps are at the configured size
+    if (rectify) {  // rectify instead: the maps are at the configured size
         sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
         Mat maps[4];
         std::ifstream f(argv[13], std::ios::binary);
@@ -138,7 +150,7 @@ int main(int argc, char **argv) {
         sgm->remap(img_r, img_r, 1);
         std::printf("rectified left size: %d, %d\n", img_l.rows, img_l.cols);
         std::printf("rectified right size: %d, %d\n", img_r.rows, img_r.cols);
-    } else if (argc > 12) {  // node.cpp:75-78, on the GPU
+    } else if (sized) {  // node.cpp:75-78, on the GPU
         sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
         if (colour) sgm->set_input_size(img_l.rows, img_l.cols);  // (the frame resizes the colour pair itself)
         sgm->resize(img_l, img_l);
@@ -149,6 +161,17 @@ int main(int argc, char **argv) {
             raw_l = img_l;
             raw_r = img_r;
         }
+    }
+
+    if (argc > 15) {  // max_range Q.f64: XYZ and depth of every frame's map, on the GPU
+        double q[16];
+        std::ifstream f(argv[15], std::ios::binary);
+        if (!f.read(reinterpret_cast<char *>(q), sizeof(q)) || f.peek() != std::ifstream::traits_type::eof()) {
+            std::fprintf(stderr, "%s does not hold 16 float64 values\n", argv[15]);
+            return 2;
+        }
+        static_cast<sgm_amd::SGM *>(sv.get())->set_reproject(q, SGM_REPROJECT_XYZ | SGM_REPROJECT_DEPTH,
+                                                                 (float)std::atof(argv[14]));
     }
 
     Mat sky_mask, sky_mask_beta;  // node.cpp:80-87 (no debug image is written)
@@ -167,6 +190,15 @@ int main(int argc, char **argv) {
         for (int i = 0; i < disp.rows; ++i)
             f.write(reinterpret_cast<const char *>(disp.ptr<float>(i)), (std::streamsize)disp.cols * 4);
     }
+    if (argc > 15) {  // what the node would publish as PointCloud2 (organized) and Image 32FC1
+        const sgm_amd::SGM *sgm = static_cast<sgm_amd::SGM *>(sv.get());
+        std::ofstream fx(out + "_xyz.f32", std::ios::binary), fd(out + "_depth.f32", std::ios::binary);
+        for (int i = 0; i < disp.rows; ++i) {
+            fx.write(reinterpret_cast<const char *>(sgm->xyz().ptr<float>(i)), (std::streamsize)disp.cols * 12);
+            fd.write(reinterpret_cast<const char *>(sgm->depth().ptr<float>(i)), (std::streamsize)disp.cols * 4);
+        }
+        if (!fx || !fd) return 3;
+    }
     Mat debug_view;  // node.cpp:107-110
     sv->show_disp(debug_view);
     if (!write_ppm(out + "_debug.ppm", debug_view)) return 3;
@@ -178,7 +210,7 @@ int main(int argc, char **argv) {
     std::vector<unsigned char> pix(npx);
     int n = 0;
     Mat packed = disp.clone();
-    if (argc > 13) img_l = static_cast<sgm_amd::SGM *>(sv.get())->rectified(0);  // what the frame matched
+    if (rectify) img_l = static_cast<sgm_amd::SGM *>(sv.get())->rectified(0);  // what the frame matched
     else if (colour) img_l = static_cast<sgm_amd::SGM *>(sv.get())->input_gray(0);
     const int rc = sgm_stage_point_cloud(static_cast<sgm_amd::SGM *>(sv.get())->handle(),
                                          packed.ptr<float>(0), img_l.data, (int)img_l.step, &cam,

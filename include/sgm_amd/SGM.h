@@ -31,6 +31,10 @@
  *   gray(src, dst, fmt)          node.cpp:69-70     the decoder's / cvtColor's grey conversion
  *                                on the GPU, Y = (4899 R + 9617 G + 1868 B + 8192) >> 14
  *   input_gray(view)             the grey image the last process() matched
+ *   set_reproject(q, outputs)    (not in the reference) every process() also reprojects its map
+ *                                through stereoRectify's Q on the GPU: xyz() (CV_32FC3, what
+ *                                cv::reprojectImageTo3D gives), depth() (CV_32FC1), depth16()
+ *                                (CV_16UC1, REP 118's millimetres); reproject(disp, ...) on any map
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -67,6 +71,12 @@ typedef cv::Vec3b Vec3b;
 #ifndef CV_8UC3
 #define CV_8UC3 16
 #endif
+#ifndef CV_16UC1
+#define CV_16UC1 2
+#endif
+#ifndef CV_32FC3
+#define CV_32FC3 21
+#endif
 #ifndef CV_8UC4
 #define CV_8UC4 24
 #endif
@@ -102,7 +112,7 @@ public:
     }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     int type() const { return type_; }
-    int channels() const { return type_ == CV_8UC3 ? 3 : (type_ == CV_8UC4 ? 4 : 1); }
+    int channels() const { return type_ == CV_8UC3 || type_ == CV_32FC3 ? 3 : (type_ == CV_8UC4 ? 4 : 1); }
     Mat clone() const {  // packed copy (step = cols * elem), row by row as cv::Mat::clone
         Mat m(rows, cols, type_);
         for (int i = 0; i < rows && !empty(); ++i)
@@ -117,7 +127,9 @@ public:
     template <typename T> const T &at(int i, int j) const { return ptr<T>(i)[j]; }
 
 private:
-    static size_t elem_size(int t) { return t == CV_32FC1 || t == CV_8UC4 ? 4 : (t == CV_8UC3 ? 3 : 1); }
+    static size_t elem_size(int t) {
+        return t == CV_32FC3 ? 12 : t == CV_32FC1 || t == CV_8UC4 ? 4 : t == CV_8UC3 ? 3 : t == CV_16UC1 ? 2 : 1;
+    }
     int type_ = -1;
     std::shared_ptr<unsigned char> buf_;
 };
@@ -292,7 +304,64 @@ public:
             this->img_r = resized_[1];
         }
         if (scale > 1) decimate_left();
+        // the products of this frame's map (sgm_set_reproject), as host copies
+        if ((rp_outputs_ & SGM_REPROJECT_XYZ) && sgm_stage_reprojected(handle_, SGM_REPROJECT_XYZ, xyz_.data) != SGM_OK)
+            fail("process", sgm_last_error(handle_));
+        if ((rp_outputs_ & SGM_REPROJECT_DEPTH) &&
+            sgm_stage_reprojected(handle_, SGM_REPROJECT_DEPTH, depth_.data) != SGM_OK)
+            fail("process", sgm_last_error(handle_));
+        if ((rp_outputs_ & SGM_REPROJECT_DEPTH16) &&
+            sgm_stage_reprojected(handle_, SGM_REPROJECT_DEPTH16, depth16_.data) != SGM_OK)
+            fail("process", sgm_last_error(handle_));
     }
+
+    // Reprojection through stereoRectify's Q (sgm_set_reproject; 16 doubles,
+    // row-major): every process() then also writes the products named in
+    // `outputs` (SGM_REPROJECT_XYZ | SGM_REPROJECT_DEPTH | SGM_REPROJECT_DEPTH16)
+    // from its final map, on the GPU, for xyz(), depth() and depth16().
+    // max_range > 0: pixels with Z outside (0, max_range] are missing;
+    // depth16 = rint(Z * depth_scale).  Missing pixels hold NaN (0 in depth16).
+    void set_reproject(const double q[16], int outputs, float max_range = 0, float depth_scale = 1000) {
+        sgm_reproject r;
+        std::memcpy(r.q, q, sizeof(r.q));
+        r.outputs = outputs;
+        r.max_range = max_range;
+        r.depth_scale = depth_scale;
+        if (sgm_set_reproject(handle_, &r) != SGM_OK) fail("set_reproject", sgm_last_error(handle_));
+        rp_outputs_ = outputs;
+        xyz_ = (outputs & SGM_REPROJECT_XYZ) ? Mat(img_h, img_w, CV_32FC3) : Mat();
+        depth_ = (outputs & SGM_REPROJECT_DEPTH) ? Mat(img_h, img_w, CV_32FC1) : Mat();
+        depth16_ = (outputs & SGM_REPROJECT_DEPTH16) ? Mat(img_h, img_w, CV_16UC1) : Mat();
+    }
+    void clear_reproject() {
+        if (sgm_set_reproject(handle_, nullptr) != SGM_OK) fail("clear_reproject", sgm_last_error(handle_));
+        rp_outputs_ = 0;
+        xyz_ = depth_ = depth16_ = Mat();
+    }
+    // A working-grid CV_32FC1 map reprojected on the GPU through the Q set
+    // (sgm_stage_reproject): each product whose pointer is not null is created
+    // and filled (CV_32FC3, CV_32FC1, CV_16UC1).
+    void reproject(const Mat &disp, Mat *xyz, Mat *depth, Mat *depth16) {
+        if (disp.type() != CV_32FC1 || disp.rows != img_h || disp.cols != img_w)
+            fail("reproject", "disp must be CV_32FC1 on the working grid");
+        const Mat d = disp.step == (size_t)img_w * sizeof(float) ? disp : disp.clone();
+        Mat x, z, u;
+        if (xyz) x = Mat(img_h, img_w, CV_32FC3);
+        if (depth) z = Mat(img_h, img_w, CV_32FC1);
+        if (depth16) u = Mat(img_h, img_w, CV_16UC1);
+        if (sgm_stage_reproject(handle_, d.template ptr<float>(0), xyz ? x.template ptr<float>(0) : nullptr,
+                                depth ? z.template ptr<float>(0) : nullptr,
+                                depth16 ? u.template ptr<unsigned short>(0) : nullptr) != SGM_OK)
+            fail("reproject", sgm_last_error(handle_));
+        if (xyz) *xyz = x;
+        if (depth) *depth = z;
+        if (depth16) *depth16 = u;
+    }
+    // The last process()'s products on the working grid; a product that
+    // set_reproject was not asked for fails
+    const Mat &xyz() const { return product(SGM_REPROJECT_XYZ, xyz_, "xyz"); }
+    const Mat &depth() const { return product(SGM_REPROJECT_DEPTH, depth_, "depth"); }
+    const Mat &depth16() const { return product(SGM_REPROJECT_DEPTH16, depth16_, "depth16"); }
 
     // The pixel format of the images process() takes (sgm_set_input_format):
     // SGM_PIX_BGR8 / SGM_PIX_RGB8 take CV_8UC3 Mats, SGM_PIX_BGRA8 /
@@ -463,6 +532,13 @@ private:
     int format_ = SGM_PIX_GRAY8;  // set_input_format
     Mat resized_[2];         // the resized, rectified or converted pair of the last process()
     Mat none_;
+    int rp_outputs_ = 0;     // set_reproject: the products process() downloads
+    Mat xyz_, depth_, depth16_;
+
+    const Mat &product(int which, const Mat &m, const char *what) const {
+        if (!(rp_outputs_ & which)) fail(what, "set_reproject was not asked for this product");
+        return m;
+    }
 
     // resizing_, rectifying_ and the size process() takes, read back from the
     // handle (sgm_last_error is untouched): at most one of the two stages is

@@ -372,6 +372,95 @@ int sgm_get_input_gray(sgm_handle *h, int view, const uint8_t **d_img, int *pitc
 /* The same image copied to a HOST buffer (height x width, dense); synchronous. */
 int sgm_stage_input_gray(sgm_handle *h, int view, uint8_t *img);
 
+/* ---- reprojection: the disparity map through stereoRectify's Q, on the GPU ----
+ *
+ * What cv::reprojectImageTo3D, stereo_image_proc and depth consumers work on:
+ * an organized float32 XYZ image on the pixel grid and a depth image, float32
+ * or 16-bit (ROS REP 118's millimetres), from the frame's final map.  Pinned as
+ * DESIGN.md 5m states it and bit-exact against tests/reproject_recipe.py.  Q is
+ * 16 doubles, row-major; for working-grid pixel (i, j) of a handle with scale s,
+ * x = (double)(j * s), y = (double)(i * s) (node.cpp:133-134), d =
+ * (double)disp[i, j] (true disparity, as every map that leaves the library):
+ *   X' = ((q0 x + q1 y) + q2 d) + q3      Y' = ((q4 x + q5 y) + q6 d) + q7
+ *   Z' = ((q8 x + q9 y) + q10 d) + q11    W' = ((q12 x + q13 y) + q14 d) + q15
+ *   iW = 1.0 / W',  X = (float)(X' iW),  Y = (float)(Y' iW),  Z = (float)(Z' iW)
+ * each one IEEE double operation in the order written (no FMA, a correctly
+ * rounded division, conversions to nearest): OpenCV's reprojectImageTo3D
+ * arithmetic without its running sum along the row.  Parity with a particular
+ * OpenCV build is not pinned at this boundary, as for the pre-blur, the resize,
+ * the remap and the grey conversion.  A pixel is MISSING when disp[i, j] ==
+ * (float)(D + min_disp + 1) (sgm_get_invalid_disp; node.cpp:129's exact
+ * compare), or W' == 0.0, or max_range > 0 and not (0 < Z && Z <= max_range)
+ * (fp32 compares on the rounded Z; max_range == 0: no range test).
+ *   xyz     rows x cols x 3 f32, interleaved (CV_32FC3); missing: three times
+ *           the bit pattern 0x7FC00000 (a quiet NaN)
+ *   depth   rows x cols f32 = Z; missing: 0x7FC00000
+ *   depth16 rows x cols u16: r = rintf(Z * depth_scale) (one fp32 multiply,
+ *           ties to even) when 1 <= r <= 65535, else 0; missing: 0.
+ *           depth_scale = 1000 gives millimetres when Q is in metres
+ * A pixel whose W' is subnormal (iW overflows) is not pinned. */
+enum { SGM_REPROJECT_XYZ = 1, SGM_REPROJECT_DEPTH = 2, SGM_REPROJECT_DEPTH16 = 4 };
+typedef struct sgm_reproject {
+    double q[16];        /* row-major Q */
+    int outputs;         /* OR of the three bits: what a frame produces */
+    float max_range;     /* 0 = no range test */
+    float depth_scale;   /* depth16 = rint(Z * depth_scale) */
+} sgm_reproject;
+
+/* Reprojection is a property of the handle, like sgm_set_min_disp and
+ * sgm_set_rectify (sgm_params and SGM_HIP_VERSION are unchanged).  NULL = off
+ * (default): frames enqueue exactly the launches they did before.  With it set,
+ * sgm_process and sgm_process_device end with one launch more, on the frame's
+ * stream, after the frame's last map stage (the LR check, post_filter or
+ * LKRefine; a BM handle's own last stage): it reads the frame's output map and
+ * writes the products named in `outputs` into handle-owned buffers
+ * (sgm_get_reprojected).  No host wait and no allocation: a frame with a fill
+ * budget still captures into a HIP graph.  Allocates the products named in
+ * `outputs` (12, 4 and 2 bytes per working-grid pixel), counted in
+ * sgm_device_bytes; off frees them.  outputs == 0 is allowed on an aux_only
+ * handle only: it runs no frames, holds Q for sgm_reproject_device and allocates
+ * nothing (whatever `outputs` says).  Synchronises the handle's last work
+ * first; call it outside stream capture, and re-capture graphs afterwards.
+ * SGM_ERR_INVALID_ARG, with a message, for a non-finite q, unknown bits in
+ * outputs, outputs == 0 on a handle that is not aux_only, a negative or
+ * non-finite max_range, depth_scale not finite or <= 0 when DEPTH16 is asked
+ * for, and a SGM_VIEW_RIGHT handle (Q belongs to the left camera); a refused
+ * call changes nothing. */
+int sgm_set_reproject(sgm_handle *h, const sgm_reproject *r);
+/* r->outputs == 0 (and everything else 0) when off. */
+int sgm_get_reproject(const sgm_handle *h, sgm_reproject *r);
+/* The same launch on the caller's DEVICE buffers: d_disp a working-grid map
+ * (rows x cols f32, pitch in floats); a NULL product pointer skips that
+ * product; max_range and depth_scale come from the setter.  Pitches are in
+ * elements of each product's type (xyz_pitch >= 3 * cols); padding is untouched;
+ * pointers of any alignment their type allows are accepted.  One launch on
+ * `stream` (NULL = the handle's stream), no host wait, no allocation:
+ * capturable.  Any handle of the working size with Q set serves, aux_only
+ * included.  SGM_ERR_INVALID_ARG, with a message, for no Q set, a NULL map, all
+ * three products NULL, or a pitch too small. */
+int sgm_reproject_device(sgm_handle *h, const float *d_disp, int pitch,
+                         float *d_xyz, int xyz_pitch, float *d_depth, int depth_pitch,
+                         uint16_t *d_depth16, int depth16_pitch, void *stream);
+/* The same with HOST buffers (all dense; NULL products skipped); synchronous. */
+int sgm_stage_reproject(sgm_handle *h, const float *disp, float *xyz, float *depth, uint16_t *depth16);
+/* The last frame's product `which` (one SGM_REPROJECT_* bit): handle-owned
+ * DEVICE memory, *pitch in elements of its type (3 * cols for XYZ, else cols);
+ * valid until the next frame, sgm_set_reproject or sgm_destroy.  Reads of it
+ * are ordered after the frame on the frame's stream only.
+ * SGM_ERR_INVALID_ARG before any frame, for a product not in `outputs`, or a
+ * NULL pointer. */
+int sgm_get_reprojected(sgm_handle *h, int which, const void **d_img, int *pitch);
+/* The same product copied to a HOST buffer (dense); synchronous. */
+int sgm_stage_reprojected(sgm_handle *h, int which, void *img);
+/* The pinhole Q of a camera, row-major:
+ *   [1 0 0 -cx] [0 1 0 -cy] [0 0 0 f] [0 0 1/baseline 0],  f = ((double)fx + fy) / 2
+ * so Z = f * baseline / d.  This is NOT the node's cloud (sgm_point_cloud_device,
+ * node.cpp:119-143): one focal length for X and Y, and no 1e-6 added to the
+ * disparity.  cam->max_range is not used (the range is sgm_reproject's).
+ * SGM_ERR_INVALID_ARG for a NULL pointer, a zero baseline or a non-finite
+ * field. */
+int sgm_camera_q(const sgm_camera *cam, double q[16]);
+
 /* Bytes of device memory the handle holds. */
 size_t sgm_device_bytes(const sgm_handle *h);
 /* The handle's own stream (a hipStream_t; what a NULL stream argument

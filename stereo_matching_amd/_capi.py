@@ -46,10 +46,14 @@ EXPORTS = (
     "sgm_get_rectified", "sgm_stage_rectified", "sgm_stage_rectify_valid",
     "sgm_set_input_format", "sgm_get_input_format", "sgm_gray_device", "sgm_stage_gray",
     "sgm_get_input_gray", "sgm_stage_input_gray",
+    "sgm_set_reproject", "sgm_get_reproject", "sgm_reproject_device", "sgm_stage_reproject",
+    "sgm_get_reprojected", "sgm_stage_reprojected", "sgm_camera_q",
 )
 # sgm_set_input_format's pixel formats (SGM_PIX_*), by their ROS encoding names
 PIX_FORMATS = {"gray8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4}
 PIX_BYTES = {0: 1, 1: 3, 2: 3, 3: 4, 4: 4}
+# sgm_set_reproject's products (SGM_REPROJECT_*), by name
+REPROJECT_OUTPUTS = {"xyz": 1, "depth": 2, "depth16": 4}
 SGM_COMM_ID_BYTES = 128
 
 
@@ -77,6 +81,13 @@ class Camera(ctypes.Structure):
     _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
                 ("cy", ctypes.c_float), ("baseline", ctypes.c_double),
                 ("max_range", ctypes.c_float)]
+
+
+class Reproject(ctypes.Structure):
+    """sgm_reproject: row-major Q, the products a frame writes, the range test
+    and depth16's scale."""
+    _fields_ = [("q", ctypes.c_double * 16), ("outputs", ctypes.c_int),
+                ("max_range", ctypes.c_float), ("depth_scale", ctypes.c_float)]
 
 
 class KernelStat(ctypes.Structure):
@@ -181,6 +192,14 @@ def lib():
     L.sgm_stage_gray.argtypes = [P, I, P, I, I, I, P]
     L.sgm_get_input_gray.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
     L.sgm_stage_input_gray.argtypes = [P, I, P]
+    RP = ctypes.POINTER(Reproject)
+    L.sgm_set_reproject.argtypes = [P, RP]
+    L.sgm_get_reproject.argtypes = [P, RP]
+    L.sgm_reproject_device.argtypes = [P, P, I, P, I, P, I, P, I, P]
+    L.sgm_stage_reproject.argtypes = [P, P, P, P, P]
+    L.sgm_get_reprojected.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
+    L.sgm_stage_reprojected.argtypes = [P, I, P]
+    L.sgm_camera_q.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(ctypes.c_double)]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

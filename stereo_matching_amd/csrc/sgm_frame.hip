@@ -543,17 +543,9 @@ int input_slot(sgm_handle *h, FrameIO *f, hipStream_t st) {
     return SGM_OK;
 }
 
-}  // namespace
-
-int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
-    const ViewRoles r = view_roles(h, 0, h->d_disp[0], h->d_sub[0], 0);
-    // the L3 checkpoints from the final volume (frames get them from vfwd)
-    HIPCHK(h, timed(h, "pair_fwd_L3", vol_elems(h->g), st,
-                    [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r.fin, h->g, st); }));
-    return h->paths4 ? aggregate4(h, 1, &r, st) : aggregate(h, &r, 1, st, true);
-}
-
-int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
+// The frame up to its last map stage: the input slot, the solver, the LR check, post_filter and
+// LKRefine (run_frame, below, follows it with the output slot).
+int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
     const Geom g = h->g;
     const int nv = h->nviews;
     const double elems = vol_elems(g);
@@ -618,6 +610,24 @@ int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
                                    hipMemcpyDeviceToDevice, st));
     }
     return finish_frame(h, f, st);
+}
+
+}  // namespace
+
+int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
+    const ViewRoles r = view_roles(h, 0, h->d_disp[0], h->d_sub[0], 0);
+    // the L3 checkpoints from the final volume (frames get them from vfwd)
+    HIPCHK(h, timed(h, "pair_fwd_L3", vol_elems(h->g), st,
+                    [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r.fin, h->g, st); }));
+    return h->paths4 ? aggregate4(h, 1, &r, st) : aggregate(h, &r, 1, st, true);
+}
+
+int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
+    if (int rc = frame_maps(h, f, st)) return rc;
+    // The output slot: with reprojection set, one launch more reads the frame's
+    // final map and writes the products the handle was asked for
+    if (h->rp_on && h->rp.outputs) return sgm::reproject_frame(h, f.out, f.out_pitch, st);
+    return SGM_OK;
 }
 
 // post_filter() (Solver.cpp:600-649) in place on a device map (sgm_post.hip):

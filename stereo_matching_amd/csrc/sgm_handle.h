@@ -106,6 +106,13 @@ struct sgm_handle {
     float *d_lk_in;       // LKRefine input copy (the kernel refines the map in place)
     uint8_t *d_sky_scratch;  // sky detector scratch (sgm_sky.hip)
     int *d_cloud_counts;  // point cloud: per-row counts -> offsets, then the total
+    sgm_reproject rp;     // sgm_set_reproject: Q, the products a frame writes, the range and the scale
+    bool rp_on;           //   rp is set (off: frames end as before, sgm_reproject_device refuses)
+    bool rp_valid;        //   a frame has filled the products since the setter last changed them
+    int rp_form;          //   the XYZ store form (sgm_reproject.hip; SGM_REPROJECT_STORE picks the other)
+    float *d_rp_xyz;      //   the frame's products (null: not asked for): rows x cols x 3 f32,
+    float *d_rp_depth;    //   rows x cols f32,
+    uint16_t *d_rp_d16;   //   rows x cols u16
     uint8_t *h_pin;       // pinned host staging for sgm_process (allocated on first use)
     size_t h_pin_bytes;
     char err[512];
@@ -334,4 +341,7 @@ int stage_aggregate(sgm_handle *h, hipStream_t st);
 bool slant_default(Geom g, int nviews);
 int band_rows_for(Geom g);
 int slant_cus();
+// sgm_reproject.hip: the frame's last launch on a handle with reprojection set
+// (the products of the frame's map into the handle's buffers)
+int reproject_frame(sgm_handle *h, const float *d_map, int pitch, hipStream_t st);
 }  // namespace sgm

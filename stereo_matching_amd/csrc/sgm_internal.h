@@ -314,6 +314,12 @@ hipError_t launch_rectify(const uint8_t *const *src, int src_rows, int src_cols,
 // (src_pitch bytes) -> dst[v] rows x cols u8 (dst_pitch bytes, padding untouched).
 hipError_t launch_gray(int fmt, const uint8_t *const *src, int rows, int cols, int src_pitch,
                        uint8_t *const *dst, int dst_pitch, int nviews, hipStream_t st);
+// reprojection through Q (sgm_reproject.hip): the products whose pointers are not
+// null, pitches in elements; invalid: the map's invalid marker; form: the XYZ store form (0 | 1)
+hipError_t launch_reproject(const double *q, const float *disp, int pitch, float *xyz, int xyz_pitch,
+                            float *depth, int depth_pitch, uint16_t *depth16, int depth16_pitch,
+                            float invalid, float max_range, float depth_scale, int form, Geom g,
+                            hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

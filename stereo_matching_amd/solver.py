@@ -69,7 +69,7 @@ class SGM:
                  lk_refine: bool = False, sky_detect: bool = False,
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
-                 input_size=None, rectify=None, input_format: str = "gray8",
+                 input_size=None, rectify=None, input_format: str = "gray8", reproject=None,
                  _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
@@ -136,6 +136,9 @@ class SGM:
         # takes (in_h, in_w, channels) colour images and the frame converts
         # them to grey on the GPU first, inside the resize or the remap when one
         # is set (set_input_format)
+        # reproject = Q (16 values, stereoRectify's 4 x 4 matrix row-major): every
+        # frame also writes the organized XYZ image and the depth image of its
+        # final map (set_reproject; get_xyz(), get_depth())
         self.in_h, self.in_w, self.in_ch = h, w, 1
         try:
             if _fmt_code(input_format):
@@ -148,6 +151,8 @@ class SGM:
                 self.set_input_size(*input_size)
             if rectify is not None:
                 self.set_rectify(*rectify)
+            if reproject is not None:
+                self.set_reproject(reproject)
         except Exception:
             self.close()
             raise
@@ -398,6 +403,105 @@ class SGM:
         (sgm_stage_input_gray).  What the point cloud and show_disp read."""
         return self._input_image(self._lib.sgm_stage_input_gray, view)
 
+    # ------------------------------------------------------- reprojection
+    def set_reproject(self, q, outputs=("xyz", "depth"), max_range: float = 0.0,
+                      depth_scale: float = 1000.0) -> None:
+        """sgm_set_reproject: every later frame ends with one launch more that
+        reprojects its final map through Q (16 values, stereoRectify's 4 x 4
+        matrix row-major) into the products named in `outputs`
+        ("xyz", "depth", "depth16", or the OR of their bits): get_xyz(),
+        get_depth(), get_depth16().  max_range > 0: pixels with Z outside
+        (0, max_range] are missing; depth16 = rint(Z * depth_scale).
+        set_reproject(None) switches it off.  An aux_only handle may pass
+        outputs=() and keep Q for reproject() / reproject_device() alone.  Not
+        inside stream capture; re-capture graphs."""
+        if q is None:
+            check(self._lib.sgm_set_reproject(self._h, None), self._h)
+            return
+        qa = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+        if qa.size != 16:
+            raise ValueError(f"q: expected 16 values (a 4 x 4 matrix), got {qa.size}")
+        if isinstance(outputs, str):
+            outputs = (outputs,)
+        bits = 0
+        for o in ([outputs] if isinstance(outputs, int) else outputs):
+            if isinstance(o, str) and o not in _capi.REPROJECT_OUTPUTS:
+                raise ValueError(f"outputs must name {sorted(_capi.REPROJECT_OUTPUTS)}, got {o!r}")
+            bits |= _capi.REPROJECT_OUTPUTS[o] if isinstance(o, str) else int(o)
+        r = _capi.Reproject((ctypes.c_double * 16)(*qa), bits, max_range, depth_scale)
+        check(self._lib.sgm_set_reproject(self._h, ctypes.byref(r)), self._h)
+
+    @property
+    def reprojection(self):
+        """(Q as a 4 x 4 float64 array, outputs bits, max_range, depth_scale) as
+        the handle holds them; None while reprojection is off."""
+        r = _capi.Reproject()
+        check(self._lib.sgm_get_reproject(self._h, ctypes.byref(r)), self._h)
+        if not r.outputs and not any(r.q):
+            return None
+        return np.array(list(r.q), np.float64).reshape(4, 4), r.outputs, r.max_range, r.depth_scale
+
+    def reproject(self, disp, outputs=("xyz", "depth", "depth16")) -> dict:
+        """A rows x cols map reprojected on the GPU through the Q set
+        (sgm_stage_reproject; synchronous): {"xyz": rows x cols x 3 float32,
+        "depth": rows x cols float32, "depth16": rows x cols uint16} for the
+        names in `outputs`.  Missing pixels hold NaN (0 in depth16)."""
+        f = np.ascontiguousarray(disp, dtype=np.float32)
+        if f.shape != (self.rows, self.cols):
+            raise ValueError(f"disp: expected shape {(self.rows, self.cols)}, got {f.shape}")
+        shapes = {"xyz": ((self.rows, self.cols, 3), np.float32), "depth": ((self.rows, self.cols), np.float32),
+                  "depth16": ((self.rows, self.cols), np.uint16)}
+        for o in outputs:
+            if o not in shapes:
+                raise ValueError(f"outputs must name {sorted(shapes)}, got {o!r}")
+        out = {o: np.empty(*shapes[o]) for o in outputs}
+        check(self._lib.sgm_stage_reproject(self._h, _ptr(f), _ptr(out.get("xyz")), _ptr(out.get("depth")),
+                                            _ptr(out.get("depth16"))), self._h)
+        return out
+
+    def reproject_device(self, d_disp: int, *, d_xyz: int = 0, d_depth: int = 0, d_depth16: int = 0,
+                         pitch: int | None = None, xyz_pitch: int | None = None,
+                         depth_pitch: int | None = None, depth16_pitch: int | None = None,
+                         stream: int | None = None) -> None:
+        """The same on device buffers (sgm_reproject_device: one launch,
+        enqueue only, capturable); a product whose pointer is 0 is skipped;
+        pitches in elements of each buffer's type."""
+        check(self._lib.sgm_reproject_device(
+            self._h, ctypes.c_void_p(d_disp or None), self.cols if pitch is None else pitch,
+            ctypes.c_void_p(d_xyz or None), 3 * self.cols if xyz_pitch is None else xyz_pitch,
+            ctypes.c_void_p(d_depth or None), self.cols if depth_pitch is None else depth_pitch,
+            ctypes.c_void_p(d_depth16 or None), self.cols if depth16_pitch is None else depth16_pitch,
+            _stream(stream)), self._h)
+
+    def _reprojected(self, which: int, shape, dtype) -> np.ndarray:
+        out = np.empty(shape, dtype)
+        check(self._lib.sgm_stage_reprojected(self._h, which, _ptr(out)), self._h)
+        return out
+
+    def get_xyz(self) -> np.ndarray:
+        """The last frame's organized XYZ image: rows x cols x 3 float32, NaN
+        where missing; a host copy (sgm_stage_reprojected)."""
+        return self._reprojected(_capi.REPROJECT_OUTPUTS["xyz"], (self.rows, self.cols, 3), np.float32)
+
+    def get_depth(self) -> np.ndarray:
+        """The last frame's depth image Z: rows x cols float32, NaN where missing."""
+        return self._reprojected(_capi.REPROJECT_OUTPUTS["depth"], (self.rows, self.cols), np.float32)
+
+    def get_depth16(self) -> np.ndarray:
+        """The last frame's 16-bit depth image rint(Z * depth_scale): rows x
+        cols uint16, 0 where missing or outside [1, 65535]."""
+        return self._reprojected(_capi.REPROJECT_OUTPUTS["depth16"], (self.rows, self.cols), np.uint16)
+
+    @staticmethod
+    def camera_q(fx, fy, cx, cy, baseline) -> np.ndarray:
+        """sgm_camera_q: the pinhole Q [1 0 0 -cx; 0 1 0 -cy; 0 0 0 f; 0 0
+        1/baseline 0] with f = (fx + fy) / 2, as a 4 x 4 float64 array.  Not
+        the node's cloud (point_cloud): one focal length and no 1e-6."""
+        cam = _capi.Camera(fx, fy, cx, cy, baseline, 0.0)
+        q = (ctypes.c_double * 16)()
+        check(lib().sgm_camera_q(ctypes.byref(cam), q))
+        return np.array(list(q), np.float64).reshape(4, 4)
+
     def check(self) -> None:
         """sgm_check: wait for the frames enqueued so far and raise SGMError
         (SGM_ERR_HIP) if a slanted-pass hand-off gave up, or a fixed-budget
@@ -633,11 +737,12 @@ class BM(SGM):
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
                  post_filter_launches: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8"):
+                 input_format: str = "gray8", reproject=None):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
                          post_filter_launches=post_filter_launches, input_size=input_size,
-                         rectify=rectify, input_format=input_format, _solver=_capi.SGM_SOLVER_BM)
+                         rectify=rectify, input_format=input_format, reproject=reproject,
+                         _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -651,7 +756,12 @@ class GPU_SGM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8"):
+                 input_format: str = "gray8", reproject=None):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
                          post_filter_launches=post_filter_launches, min_disp=min_disp,
-                         input_size=input_size, rectify=rectify, input_format=input_format)
+                         input_size=input_size, rectify=rectify, input_format=input_format,
+                         reproject=reproject)
+
+
+# sgm_camera_q without a handle: the pinhole Q of a camera, 4 x 4 float64
+camera_q = SGM.camera_q

@@ -1,0 +1,80 @@
+"""examples/stereo_node.cpp with a Q: given a fifteenth argument Q.f64 (16
+doubles; the fourteenth is the range test's max_range) it sets XYZ and depth on the solver and writes OUT_xyz.f32 and
+OUT_depth.f32 after the frame, equal to the recipe (tests/reproject_recipe.py)
+on its own OUT_disp.f32; without the argument it writes neither file."""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import reproject_recipe as rp
+from stereo_matching_amd import _capi, synthetic
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "examples", "stereo_node.cpp")
+CAM = ("721.5377", "721.5377", "609.5593", "172.854")
+MR = "20.5"
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    if not os.path.exists(_capi.LIB_PATH):
+        _capi.build()
+    out = str(tmp_path_factory.mktemp("node") / "stereo_node")
+    libdir = os.path.dirname(_capi.LIB_PATH)
+    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-o", out],
+                   check=True, capture_output=True, text=True)
+    return out
+
+
+def _pgm(path, img):
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(np.ascontiguousarray(img, np.uint8).tobytes())
+
+
+def test_usage_names_the_q_file(exe):
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 2 and "Q.f64" in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scale,m", [(1, 0), (2, 16)])
+def test_example_node_writes_xyz_and_depth_of_its_own_map(exe, tmp_path, scale, m):
+    D = 64
+    h, w = 60 * scale, 200 * scale
+    left, right = synthetic.stereo_pair(h, w, D, pair_index=0, kind="road")
+    _pgm(tmp_path / "l.pgm", left)
+    _pgm(tmp_path / "r.pgm", right)
+    q = rp.camera_q(721.5377, 721.5377, 609.5593, 172.854, 0.54)
+    q.tofile(tmp_path / "Q.f64")
+    prefix = str(tmp_path / "out")
+    head = [exe, str(tmp_path / "l.pgm"), str(tmp_path / "r.pgm")]
+    r = subprocess.run(head + [prefix, str(scale), str(D), *CAM, str(m), "0", "0", "-", MR, str(tmp_path / "Q.f64")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    H, W = h // scale, w // scale
+    disp = np.fromfile(prefix + "_disp.f32", np.float32).reshape(H, W)
+    want = rp.reproject(disp, q, D + m + 1, scale, float(MR))
+    free = rp.reproject(disp, q, D + m + 1, scale)
+    assert (want["missing"] & ~free["missing"]).any()          # the range test took some
+    assert want["missing"].any() and not want["missing"].all()
+    assert np.array_equal(np.fromfile(prefix + "_xyz.f32", np.uint32).reshape(H, W, 3), rp.bits(want["xyz"]))
+    assert np.array_equal(np.fromfile(prefix + "_depth.f32", np.uint32).reshape(H, W), rp.bits(want["depth"]))
+    # without the argument: the same map, and neither file
+    prefix2 = str(tmp_path / "plain")
+    r = subprocess.run(head + [prefix2, str(scale), str(D), *CAM, str(m)], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert open(prefix2 + "_disp.f32", "rb").read() == open(prefix + "_disp.f32", "rb").read()
+    assert open(prefix2 + "_cloud.bin", "rb").read() == open(prefix + "_cloud.bin", "rb").read()
+    assert not os.path.exists(prefix2 + "_xyz.f32") and not os.path.exists(prefix2 + "_depth.f32")
+    # a Q file of the wrong size is refused
+    np.zeros(15).tofile(tmp_path / "short.f64")
+    r = subprocess.run(head + [prefix, str(scale), str(D), *CAM, str(m), "0", "0", "-", MR, str(tmp_path / "short.f64")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "16 float64" in r.stderr
