@@ -735,9 +735,9 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, cons
     HIPCHK(h, hipMemcpyAsync(h->d_ct[1], ctr, npx * 8, hipMemcpyHostToDevice, h->st));
     if (sky) HIPCHK(h, hipMemcpyAsync(h->d_sky[0], sky, npx, hipMemcpyHostToDevice, h->st));
     // (min_disp: the view's shift applied to the tables as handed in)
-    if (int rc = shift_tables(h, view == 1, view == 0, h->st)) return rc;
-    HIPCHK(h, sgm::launch_cost_h(ct_left(h, view), ct_right(h, view), sky ? h->d_sky[0] : nullptr,
-                                 h->g.W, view, filters & 1, h->g, h->d_ch[0], h->st));
+    const sgm::CostSlot s = sgm::cost_slot(h, 0, view, sky ? h->d_sky[0] : nullptr);
+    if (int rc = shift_tables(h, &s, 1, h->st)) return rc;
+    HIPCHK(h, sgm::launch_cost_h(&s, 1, h->g.W, filters & 1, h->g, h->st));
     const float *res = h->d_ch[0];
     if (filters & 2) {  // the frame's own vfwd, in place when the frames run it so
         const sgm::PairArgs pa = vfwd_args(h, 0);

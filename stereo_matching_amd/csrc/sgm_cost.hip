@@ -5,8 +5,11 @@
 // Stage map (reference -> kernel), full design in DESIGN.md:
 //   cv::GaussianBlur + CT_pts     Solver.cpp:120-140, cost.cpp:99-129  -> census_kernel
 //   build_dsi_from_table[_beta]   Solver.cpp:143-248
-//     + cost_horizontal_filter    Solver.cpp:296-330                   -> cost_h_kernel,
-//                                                                         cost_h2_kernel (both views)
+//     + cost_horizontal_filter    Solver.cpp:296-330                   -> cost_h_kernel (one view slot),
+//                                                                         cost_h2_kernel (both),
+//                                                                         cost_h_global_kernel (wide rows);
+//                                                                         slanted frames: cost_ck_kernel
+//                                                                         + vstrip_kernel (sgm_vstrip.hip)
 //   cost_vertical_filter          Solver.cpp:333-368                   -> vfwd_kernel (sgm_pair.hip)
 //   L1..L8 path DP                SGM.cpp:81-369                       -> stage_a/stage_b kernels,
 //                                                                         sweep_kernel (sgm_sweep.hip)
@@ -18,6 +21,8 @@
 // no fast-math, correctly rounded f32 division; every float expression keeps
 // the reference's association order.
 #include "sgm_device.h"
+
+#include <type_traits>
 
 namespace sgm {
 
@@ -371,12 +376,15 @@ __global__ __launch_bounds__(256) void cost_h_kernel(const uint64_t *__restrict_
                                              bid_x(), smem);
 }
 
-// Both views in one launch (workgroup z = view): the DSI of
+// Both view slots in one launch (workgroup z = slot): the DSI of
 // build_dsi_from_table into out0 and of build_dsi_from_table_beta into out1,
 // each with its own sky mask.  A view's H*D chains fill less than the chip at
-// KITTI sizes, so the two views' chains run side by side.  Each view reads its
-// own table pair: view 0 (ctl, ctr_s), view 1 (ctl_s, ctr) (launch_ct_shift;
-// the same two tables when min_disp = 0).
+// KITTI sizes, so the two views' chains run side by side.  Each slot reads its
+// own table pair: slot 0 (ctl, ctr_s), slot 1 (ctl_s, ctr) (census_tables,
+// sgm_internal.h).  A kernel of its own beside cost_h_kernel, and bare pointer
+// parameters in both: as one template over Views<CostSlot, NV> the
+// uniform-operand forms lost scalar loads to vector ones
+// (profiles/cost_stage_merge_codegen.txt).
 template <int WIN, bool SKY, bool FILTER, bool UNI, int DC>
 __global__ __launch_bounds__(256) void cost_h2_kernel(const uint64_t *__restrict__ ctl,
                                                       const uint64_t *__restrict__ ctr,
@@ -447,96 +455,90 @@ __global__ __launch_bounds__(256) void cost_h_global_kernel(const uint64_t *__re
     for (int p = LAG + T; p < W; ++p) costh_store(raw(p), o + (size_t)p * D);
 }
 
-// rows per block and LDS bytes of the staged cost_h_kernel (R = 0: the
-// global-memory fallback)
-static void costh_shape(Geom g, bool sky, bool &uni, int &R, size_t &smem) {
+// the staged kernels' form (UNI), rows per block (R = 0: the global-memory
+// fallback) and LDS bytes
+struct CosthShape {
+    bool uni;
+    int R;
+    size_t smem;
+};
+static CosthShape costh_shape(Geom g, bool sky) {
     const size_t rs = (size_t)(g.W + 2 * costh_pad(g.D, g.scale));
-    uni = g.D >= 64 && rs * (16 + (sky ? 1 : 0)) > (size_t)COSTH_MAX_LDS;
+    const bool uni = g.D >= 64 && rs * (16 + (sky ? 1 : 0)) > (size_t)COSTH_MAX_LDS;
     const size_t row_bytes = rs * ((uni ? 8 : 16) + (sky ? 1 : 0));
-    R = (int)(COSTH_MAX_LDS / row_bytes);
+    int R = (int)(COSTH_MAX_LDS / row_bytes);
     if (R > 256 / g.D) R = 256 / g.D;
-    smem = (size_t)(R > 0 ? R : 0) * row_bytes;
+    return {uni, R, (size_t)R * row_bytes};
 }
 
-template <int VIEW, int WIN, bool SKY, bool FILTER>
-static void launch_cost_h_t(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,
-                            int sky_pitch, Geom g, float *out, hipStream_t st) {
-    // stage both census rows when they fit (faster: LDS reads for both
-    // operands); rows too wide for that (4K) stage one and load the uniform
-    // operand as scalars
-    bool uni;
-    int R;
-    size_t smem;
-    costh_shape(g, SKY, uni, R, smem);
-    if (R >= 1) {
-        if (uni)
-            cost_h_kernel<VIEW, WIN, SKY, FILTER, true, 0><<<dim3((g.H + R - 1) / R), R * g.D, smem, st>>>(
-                ctl, ctr, sky, sky_pitch, g.H, g.W, g.D, g.scale, R, out);
-        else if (g.D == 128)
-            cost_h_kernel<VIEW, WIN, SKY, FILTER, false, 128><<<dim3((g.H + R - 1) / R), R * g.D, smem, st>>>(
-                ctl, ctr, sky, sky_pitch, g.H, g.W, g.D, g.scale, R, out);
-        else
-            cost_h_kernel<VIEW, WIN, SKY, FILTER, false, 0><<<dim3((g.H + R - 1) / R), R * g.D, smem, st>>>(
-                ctl, ctr, sky, sky_pitch, g.H, g.W, g.D, g.scale, R, out);
-    } else {
-        const int rpb = 256 / g.D;
-        cost_h_global_kernel<VIEW, WIN, SKY, FILTER><<<dim3((g.H + rpb - 1) / rpb), 256, 0, st>>>(
-            ctl, ctr, sky, sky_pitch, g.H, g.W, g.D, g.scale, out);
-    }
+bool cost_h_staged(const CostSlot *s, int nviews, Geom g) {
+    return costh_shape(g, s->sky != nullptr).R >= 1 &&
+           (nviews == 1 || (s[0].sky == nullptr) == (s[1].sky == nullptr));
 }
 
-template <int VIEW, int WIN>
-static void launch_cost_h_w(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,
-                            int sky_pitch, int filter, Geom g, float *out, hipStream_t st) {
-    if (sky) {
-        if (filter) launch_cost_h_t<VIEW, WIN, true, true>(ctl, ctr, sky, sky_pitch, g, out, st);
-        else launch_cost_h_t<VIEW, WIN, true, false>(ctl, ctr, sky, sky_pitch, g, out, st);
-    } else {
-        if (filter) launch_cost_h_t<VIEW, WIN, false, true>(ctl, ctr, sky, sky_pitch, g, out, st);
-        else launch_cost_h_t<VIEW, WIN, false, false>(ctl, ctr, sky, sky_pitch, g, out, st);
-    }
+// f(tags...): each flag as std::true_type or std::false_type, which a generic
+// lambda names in constant expressions (as for_width's tags, sgm_bodies.h)
+template <class F>
+static void for_flags(F &&f) {
+    f();
+}
+template <class F, class... B>
+static void for_flags(F &&f, bool b, B... rest) {
+    if (b) for_flags([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else for_flags([&](auto... t) { f(std::false_type{}, t...); }, rest...);
 }
 
-template <int WIN, bool SKY, bool FILTER>
-static hipError_t launch_cost_h2_t(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
-                                   const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
-                                   int sky_pitch, Geom g, float *out0, float *out1, hipStream_t st) {
-    bool uni;
-    int R;
-    size_t smem;
-    costh_shape(g, SKY, uni, R, smem);
-    if (R < 1) return hipErrorInvalidValue;  // the caller launches the views one by one
-    const dim3 grid((g.H + R - 1) / R, 1, 2);
-    if (uni)
-        cost_h2_kernel<WIN, SKY, FILTER, true, 0><<<grid, R * g.D, smem, st>>>(
-            ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
-    else if (g.D == 128)
-        cost_h2_kernel<WIN, SKY, FILTER, false, 128><<<grid, R * g.D, smem, st>>>(
-            ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
-    else
-        cost_h2_kernel<WIN, SKY, FILTER, false, 0><<<grid, R * g.D, smem, st>>>(
-            ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, g.scale, R, out0, out1);
+// The staged kernels' form, f(UNI, DC): both census rows staged when they fit
+// (faster: LDS reads for both operands), D = 128 as a constant; rows too wide
+// for that (4K) stage one and load the uniform operand as scalars
+template <class F>
+static void for_staged_form(bool uni, int D, F &&f) {
+    if (uni) f(std::true_type{}, std::integral_constant<int, 0>{});
+    else if (D == 128) f(std::false_type{}, std::integral_constant<int, 128>{});
+    else f(std::false_type{}, std::integral_constant<int, 0>{});
+}
+
+// whether the slots are a launch's: one of either DSI, or (DSI 0, DSI 1)
+static bool slots_ok(const CostSlot *s, int nviews) {
+    return nviews == 1 ? (s->dsi == 0 || s->dsi == 1) : (nviews == 2 && s[0].dsi == 0 && s[1].dsi == 1);
+}
+
+hipError_t launch_cost_h(const CostSlot *s, int nviews, int sky_pitch, int filter, Geom g, hipStream_t st) {
+    if (!slots_ok(s, nviews) || (nviews == 2 && !(filter && cost_h_staged(s, 2, g)))) return hipErrorInvalidValue;
+    const CosthShape sh = costh_shape(g, s->sky != nullptr);
+    const int rpb = sh.R >= 1 ? sh.R : 256 / g.D;  // rows per block (the fallback: of 256 threads)
+    const dim3 grid((g.H + rpb - 1) / rpb, 1, nviews);
+    for_flags(
+        [&](auto SKY, auto FILTER, auto WIN5) {
+            constexpr int WIN = WIN5 ? 5 : 2;
+            if (nviews == 2) {  // both slots: staged and filtered (checked above)
+                if constexpr (FILTER) {
+                    const CensusTables t = census_tables(s, 2);
+                    for_staged_form(sh.uni, g.D, [&](auto UNI, auto DC) {
+                        cost_h2_kernel<WIN, SKY, FILTER, UNI, DC><<<grid, sh.R * g.D, sh.smem, st>>>(
+                            t.ctl, t.ctr, t.ctl_s, t.ctr_s, s[0].sky, s[1].sky, sky_pitch, g.H, g.W, g.D, g.scale,
+                            sh.R, s[0].ch, s[1].ch);
+                    });
+                }
+                return;
+            }
+            for_flags(
+                [&](auto RIGHT) {  // one slot: its DSI
+                    constexpr int VIEW = RIGHT ? 1 : 0;
+                    if (sh.R >= 1) {
+                        for_staged_form(sh.uni, g.D, [&](auto UNI, auto DC) {
+                            cost_h_kernel<VIEW, WIN, SKY, FILTER, UNI, DC><<<grid, sh.R * g.D, sh.smem, st>>>(
+                                s->ctl, s->ctr, s->sky, sky_pitch, g.H, g.W, g.D, g.scale, sh.R, s->ch);
+                        });
+                    } else {
+                        cost_h_global_kernel<VIEW, WIN, SKY, FILTER><<<grid, 256, 0, st>>>(
+                            s->ctl, s->ctr, s->sky, sky_pitch, g.H, g.W, g.D, g.scale, s->ch);
+                    }
+                },
+                s->dsi == 1);
+        },
+        s->sky != nullptr, filter != 0, g.scale == 1);
     return hipGetLastError();
-}
-
-bool cost_h2_supported(Geom g, bool sky) {
-    bool uni;
-    int R;
-    size_t smem;
-    costh_shape(g, sky, uni, R, smem);
-    return R >= 1;
-}
-
-hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
-                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
-                          int sky_pitch, Geom g, float *out0, float *out1, hipStream_t st) {
-    if ((sky0 == nullptr) != (sky1 == nullptr)) return hipErrorInvalidValue;
-    if (sky0) {
-        if (g.scale == 1) return launch_cost_h2_t<5, true, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
-        return launch_cost_h2_t<2, true, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
-    }
-    if (g.scale == 1) return launch_cost_h2_t<5, false, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
-    return launch_cost_h2_t<2, false, true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g, out0, out1, st);
 }
 
 // The checkpoint pass's chain (sgm_vstrip.hip): cost_h_body's horizontal IIR
@@ -544,9 +546,9 @@ hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint64
 // bytes are negligible, so the chains' latency is its time: the steps run in
 // blocks of one strip (U = kVStripNC) that start at an edge, so the
 // checkpoint is the block's first action (no branch), and the next block's
-// census words are loaded one block ahead -- the uniform row (UNI) by vector
-// loads from an opaque per-lane address: SMEM returns out of order, so its
-// waits are lgkmcnt(0), which hipcc placed right before each block.
+// census words are loaded one block ahead -- the uniform row (UNI) by scalar
+// loads: SMEM returns out of order, so its waits are lgkmcnt(0), which hipcc
+// placed right before each block.
 template <int VIEW, bool UNI>
 __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
                                              const uint64_t *__restrict__ ctr, int H, int W, int D,
@@ -554,7 +556,6 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
                                              unsigned char *smem, int ns) {
     constexpr int U = kVStripNC;
     const int P = costh_pad(D, 1), RS = W + 2 * P;
-    constexpr int NS = UNI ? 1 : 2;
     uint64_t *sl = reinterpret_cast<uint64_t *>(smem);
     uint64_t *sr = sl + (UNI ? 0 : (size_t)R * RS);
     const int row0 = blk * R;
@@ -566,7 +567,6 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
             if (!UNI || VIEW == 0) sr[idx] = ctr[(size_t)i * W + j];
         }
     }
-    (void)NS;
     __syncthreads();
     const int r = UNI ? uniform(tid_x() / D) : tid_x() / D, d = tid_x() - r * D;
     const int i = row0 + r;
@@ -574,13 +574,6 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
     const uint64_t *cl = sl + (size_t)r * RS + P + (VIEW == 1 ? d : 0);
     const uint64_t *cr = sr + (size_t)r * RS + P - (VIEW == 0 ? d : 0);
     const uint64_t *cu = (VIEW == 0 ? ctl : ctr) + (size_t)i * W;
-#ifdef COSTCK_VLOAD
-    if constexpr (UNI) {
-        int z;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-        cu += z;
-    }
-#endif
     float *o = out + (size_t)i * ns * 3 * D + d;
     // the shifted operand (LDS) and the other one (UNI: global) of position
     // j <= W-1 (positions past the row are clamped; their costs feed nothing)
@@ -648,7 +641,8 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
 // The strip schedule's checkpoint pass (sgm_vstrip.hip): each view slot's
 // horizontal IIR state at every strip edge, both slots in one launch
 // (workgroup z = slot; dsi0/dsi1: the slot's DSI, 0 left view, 1 right: it
-// reads (ctl, ctr_s) or (ctl_s, ctr), as cost_h2_kernel's views).
+// reads (ctl, ctr_s) or (ctl_s, ctr), as cost_h2_kernel's slots; a one-slot
+// launch of DSI 1 is a right-view handle's).
 template <bool SKY, bool UNI, int DC>
 __global__ __launch_bounds__(256) void cost_ck_kernel(const uint64_t *__restrict__ ctl,
                                                       const uint64_t *__restrict__ ctr,
@@ -672,49 +666,26 @@ __global__ __launch_bounds__(256) void cost_ck_kernel(const uint64_t *__restrict
     }
 }
 
-template <bool SKY>
-static hipError_t launch_cost_ck_t(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
-                                   const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
-                                   int sky_pitch, int dsi0, int dsi1, int nviews, Geom g, float *ck0,
-                                   float *ck1, hipStream_t st) {
-    bool uni;
-    int R;
-    size_t smem;
-    costh_shape(g, SKY, uni, R, smem);
-    if (R < 1 || g.scale != 1) return hipErrorInvalidValue;  // (vstrip_supported)
-    const dim3 grid((g.H + R - 1) / R, 1, nviews);
+hipError_t launch_cost_ck(const CostSlot *s, int nviews, int sky_pitch, Geom g, hipStream_t st) {
+    if (!slots_ok(s, nviews) || !vstrip_supported(s, nviews, g)) return hipErrorInvalidValue;
+    const CosthShape sh = costh_shape(g, s->sky != nullptr);
+    const dim3 grid((g.H + sh.R - 1) / sh.R, 1, nviews);
     const int ns = (int)vstrip_strips(g);
+    const CensusTables t = census_tables(s, nviews);
+    const CostSlot &b = s[nviews - 1];
     // (census operands straight from global memory instead of the staged
     // rows measured slower: HD256 610 vs 317 us, 4K256 2.33 vs 1.82 ms; one
     // row per block, for more waves per CU, changed nothing:
     // profiles/r06_experiments/r06q_vstrip.txt)
-#define CK_ARGS ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, g.H, g.W, g.D, R, ck0, ck1, dsi0, dsi1, ns
-    if (uni) cost_ck_kernel<SKY, true, 0><<<grid, R * g.D, smem, st>>>(CK_ARGS);
-    else if (g.D == 128) cost_ck_kernel<SKY, false, 128><<<grid, R * g.D, smem, st>>>(CK_ARGS);
-    else cost_ck_kernel<SKY, false, 0><<<grid, R * g.D, smem, st>>>(CK_ARGS);
-#undef CK_ARGS
-    return hipGetLastError();
-}
-
-hipError_t launch_cost_ck(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
-                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
-                          int sky_pitch, int dsi0, int dsi1, int nviews, Geom g, float *ck0,
-                          float *ck1, hipStream_t st) {
-    if (nviews == 2 && (sky0 == nullptr) != (sky1 == nullptr)) return hipErrorInvalidValue;
-    if (sky0) return launch_cost_ck_t<true>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, dsi0, dsi1, nviews, g, ck0, ck1, st);
-    return launch_cost_ck_t<false>(ctl, ctr, ctl_s, ctr_s, sky0, sky1, sky_pitch, dsi0, dsi1, nviews, g, ck0, ck1, st);
-}
-
-hipError_t launch_cost_h(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,
-                         int sky_pitch, int view, int filter, Geom g, float *out,
-                         hipStream_t st) {
-    if (view == 0) {
-        if (g.scale == 1) launch_cost_h_w<0, 5>(ctl, ctr, sky, sky_pitch, filter, g, out, st);
-        else launch_cost_h_w<0, 2>(ctl, ctr, sky, sky_pitch, filter, g, out, st);
-    } else {
-        if (g.scale == 1) launch_cost_h_w<1, 5>(ctl, ctr, sky, sky_pitch, filter, g, out, st);
-        else launch_cost_h_w<1, 2>(ctl, ctr, sky, sky_pitch, filter, g, out, st);
-    }
+    for_flags(
+        [&](auto SKY) {
+            for_staged_form(sh.uni, g.D, [&](auto UNI, auto DC) {
+                cost_ck_kernel<SKY, UNI, DC><<<grid, sh.R * g.D, sh.smem, st>>>(
+                    t.ctl, t.ctr, t.ctl_s, t.ctr_s, s->sky, b.sky, sky_pitch, g.H, g.W, g.D, sh.R, s->ch, b.ch, s->dsi,
+                    b.dsi, ns);
+            });
+        },
+        s->sky != nullptr);
     return hipGetLastError();
 }
 

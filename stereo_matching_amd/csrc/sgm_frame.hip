@@ -12,9 +12,31 @@
 
 using sgm::PairArgs;
 
-// The shifted tables after a census (or an upload) wrote d_ct; nothing at min_disp = 0
-int sgm::shift_tables(sgm_handle *h, bool left, bool right, hipStream_t st) {
+// What view slot `slot`'s cost stage takes (sgm_internal.h) when it runs DSI
+// `dsi` (0: left view, 1: right view) under the mask `sky` (null: none).  With
+// cost_slots below, the one place that knows which table of a DSI's pair is
+// the min_disp-shifted one (the other image's: d_cts, the tables themselves at
+// min_disp = 0) and where the sky words of a masked strip frame sit: after the
+// checkpoints in the dead Ch volume, 3/16 + 2/D of its floats at most.
+sgm::CostSlot sgm::cost_slot(sgm_handle *h, int slot, int dsi, const uint8_t *sky) {
+    sgm::CostSlot s{};
+    s.ctl = dsi ? h->d_cts[0] : h->d_ct[0];
+    s.ctr = dsi ? h->d_ct[1] : h->d_cts[1];
+    s.dsi = dsi;
+    s.sky = sky;
+    s.ch = h->d_ch[slot];
+    if (sky) s.skw = reinterpret_cast<uint64_t *>(h->d_ch[slot] + sgm::vstrip_sky_words_offset(h->g));
+    s.c = cost_buf(h, slot);
+    s.l3 = h->d_l3[slot];
+    return s;
+}
+
+// The shifted tables the slots' DSIs read (DSI 0 the right image's, DSI 1 the
+// left image's), after a census (or an upload) wrote d_ct; nothing at min_disp = 0
+int sgm::shift_tables(sgm_handle *h, const sgm::CostSlot *s, int nviews, hipStream_t st) {
     if (h->min_disp == 0) return SGM_OK;
+    bool left = false, right = false;
+    for (int v = 0; v < nviews; ++v) (s[v].dsi ? left : right) = true;
     HIPCHK(h, timed(h, "ct_shift", (double)((left ? 1 : 0) + (right ? 1 : 0)) * h->g.H * h->g.W, st, [&] {
                return sgm::launch_ct_shift(h->d_ct[0], h->d_ct[1], left ? h->d_cts[0] : nullptr,
                                            right ? h->d_cts[1] : nullptr, h->min_disp / h->g.scale,
@@ -85,6 +107,7 @@ int sgm::slant_cus() {
 
 namespace {
 
+using sgm::CostSlot;
 using sgm::ViewRoles;
 
 // The one place that wires the roles (sgm_internal.h) to a view's buffers: C (cost_buf), S12
@@ -236,20 +259,25 @@ int aggregate4(sgm_handle *h, int nv, const ViewRoles *r, hipStream_t st) {
     return SGM_OK;
 }
 
-// build_dsi_from_table[_beta] (dsi 0 / 1) + horizontal IIR (cost_h), then
-// the vertical IIR fused with the L3 forward pass (vfwd), into view slot
-// `view`'s buffers.
-int cost_view(sgm_handle *h, int view, int dsi, const uint8_t *sky, int sky_pitch, hipStream_t st,
-              bool vfwd = true) {
+// The frame's view slots: the left view in slot 0 and, with two views, the
+// right view in slot 1; a right-view handle (SGM_VIEW_RIGHT) runs the right
+// view, DSI 1 under the right mask, in slot 0.
+void cost_slots(sgm_handle *h, const uint8_t *sky_l, const uint8_t *sky_r, CostSlot *s) {
+    const bool right_only = h->p.view == SGM_VIEW_RIGHT;
+    s[0] = sgm::cost_slot(h, 0, right_only ? 1 : 0, right_only ? sky_r : sky_l);
+    if (h->nviews == 2) s[1] = sgm::cost_slot(h, 1, 1, sky_r);
+}
+
+// View slot `view`'s build_dsi_from_table[_beta] + horizontal IIR (cost_h),
+// then the vertical IIR fused with the L3 forward pass (vfwd).
+int cost_view(sgm_handle *h, const CostSlot *s, int view, int sky_pitch, hipStream_t st, bool vfwd = true) {
     const double elems = vol_elems(h->g);
-    HIPCHK(h, timed(h, "cost_h", elems, st, [&] {
-               return sgm::launch_cost_h(ct_left(h, dsi), ct_right(h, dsi), sky, sky_pitch, dsi, 1,
-                                         h->g, h->d_ch[view], st);
-           }));
+    HIPCHK(h, timed(h, "cost_h", elems, st,
+                    [&] { return sgm::launch_cost_h(&s[view], 1, sky_pitch, 1, h->g, st); }));
     if (!vfwd) return SGM_OK;
     const PairArgs pa = vfwd_args(h, view);
-    const float *in = h->d_ch[view];
-    float *out = cost_buf(h, view);
+    const float *in = s[view].ch;
+    float *out = s[view].c;
     HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &out, &pa, 1, nullptr, h->g, st); }));
     return SGM_OK;
 }
@@ -272,8 +300,8 @@ int bm_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
                return sgm::launch_census(f.left, f.pitch, g, h->p.blur, h->d_ct[0], st, true, f.right,
                                          h->d_ct[1]);
            }));
-    int rc;
-    if ((rc = cost_view(h, 0, 0, f.sky_l, f.sky_pitch, st)) != SGM_OK) return rc;
+    const CostSlot s = sgm::cost_slot(h, 0, 0, f.sky_l);
+    if (int rc = cost_view(h, &s, 0, f.sky_pitch, st)) return rc;
     HIPCHK(h, timed(h, "bm_wta", vol_elems(g), st, [&] {
                return sgm::launch_bm_wta(cost_buf(h, 0), h->p.uniqueness, h->d_disp[0], f.out,
                                          f.out_pitch, g, st);
@@ -398,9 +426,9 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
     const uint8_t *d_sky_l = f.sky_l, *d_sky_r = f.sky_r;
     int sky_pitch = f.sky_pitch;
     const double npx = (double)g.H * g.W;
-    // a right-view handle (SGM_VIEW_RIGHT) runs the right view in slot 0
-    const bool right_only = h->p.view == SGM_VIEW_RIGHT;
     if (h->p.sky_detect) {  // node.cpp:80-93: detect on both inputs, then process with the masks
+        // (a right-view handle detects on the right image alone, into d_sky[0])
+        const bool right_only = h->p.view == SGM_VIEW_RIGHT;
         const uint8_t *imgs[2] = {right_only ? f.right : f.left, f.right};
         HIPCHK(h, timed(h, "sky_detect", npx, st, [&] {
                    return sgm::launch_sky_detect(imgs, f.pitch, h->d_sky, g.W, h->d_sky_scratch,
@@ -414,65 +442,33 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
                return sgm::launch_census(f.left, f.pitch, g, h->p.blur, h->d_ct[0], st, false,
                                          f.right, h->d_ct[1]);
            }));
-    // min_disp: the shifted table(s) the views' DSIs read (the left view the
-    // right image's, the right view the left image's)
-    if ((rc = sgm::shift_tables(h, h->nviews == 2 || right_only, !right_only, st)) != SGM_OK) return rc;
+    CostSlot s[2] = {};
+    cost_slots(h, d_sky_l, d_sky_r, s);
+    const int nv = h->nviews;
+    if ((rc = sgm::shift_tables(h, s, nv, st)) != SGM_OK) return rc;
+    const double elems = nv * vol_elems(g);
     // two views: both DSIs + horizontal IIRs in one launch (a view's H*D
     // serial chains alone leave most SIMDs idle at KITTI sizes)
-    const bool both_h = h->nviews == 2 && (d_sky_l == nullptr) == (d_sky_r == nullptr) &&
-                        sgm::cost_h2_supported(g, d_sky_l != nullptr);
+    const bool joint = nv == 2 && sgm::cost_h_staged(s, 2, g);
     // banded frames run vfwd in forward bands (forward_bands); the slanted
     // schedule runs its own vertical pass
     const bool vfwd_here = h->sched != SCHED_BANDS && h->sched != SCHED_SLANT;
     // the slanted schedule's cost stage as checkpoints + strips (sgm_vstrip.hip):
     // C and the L3 volumes in one pass, 9 B per element instead of cost_h's
     // 4 and vfwd_l3's 12
-    const uint8_t *sky0 = right_only ? d_sky_r : d_sky_l;
-    const bool vstrip = h->slant && h->vstrip && sgm::vstrip_supported(g, sky0 != nullptr) &&
-                        (h->nviews == 1 || (sky0 == nullptr) == (d_sky_r == nullptr));
-    // (a masked frame's sky flags go to the strip pass as words, after the
-    // checkpoints in the Ch buffer: 3/16 + 2/D of its floats at most)
+    const bool vstrip = h->slant && h->vstrip && sgm::vstrip_supported(s, nv, g);
     if (vstrip) {
-        const int dsi0 = right_only ? 1 : 0;
-        HIPCHK(h, timed(h, "cost_ck", h->nviews * npx * g.D, st, [&] {
-                   return sgm::launch_cost_ck(h->d_ct[0], h->d_ct[1], h->d_cts[0], h->d_cts[1], sky0,
-                                              d_sky_r, sky_pitch, dsi0, 1, h->nviews, g, h->d_ch[0],
-                                              h->d_ch[1], st);
-               }));
-        sgm::VStripArgs va{};
-        va.ctl = h->d_ct[0];
-        va.ctr = h->d_ct[1];
-        va.ctl_s = h->d_cts[0];
-        va.ctr_s = h->d_cts[1];
-        if (sky0) {
-            const uint8_t *skm[2] = {sky0, d_sky_r};
-            uint64_t *skw[2] = {nullptr, nullptr};
-            for (int v = 0; v < h->nviews; ++v) {
-                skw[v] = reinterpret_cast<uint64_t *>(h->d_ch[v] + sgm::vstrip_sky_words_offset(g));
+        HIPCHK(h, timed(h, "cost_ck", elems, st, [&] { return sgm::launch_cost_ck(s, nv, sky_pitch, g, st); }));
+        // (a masked frame's sky flags go to the strip pass as words)
+        for (int v = 0; v < nv; ++v)
+            if (s[v].sky)
                 HIPCHK(h, timed(h, "sky_words", npx, st,
-                                [&] { return sgm::launch_sky_words(skm[v], sky_pitch, g, skw[v], st); }));
-            }
-            va.skw0 = skw[0];
-            va.skw1 = skw[1];
-        }
-        va.dsi0 = dsi0;
-        va.dsi1 = 1;
-        va.ck0 = h->d_ch[0];  // (the checkpoints sit in the dead Ch volumes)
-        va.ck1 = h->d_ch[1];
-        va.c0 = h->d_c[0];
-        va.c1 = h->d_c[1];
-        va.l30 = h->d_l3[0];
-        va.l31 = h->d_l3[1];
-        va.dummy = h->d_slant_dummy;
-        va.p1 = (float)h->p.p1;
-        va.p2 = (float)h->p.p2;
-        HIPCHK(h, timed(h, "vstrip", h->nviews * npx * g.D, st,
-                        [&] { return sgm::launch_vstrip(va, h->nviews, g, st); }));
-    } else if (both_h) {
-        HIPCHK(h, timed(h, "cost_h", 2.0 * npx * g.D, st, [&] {
-                   return sgm::launch_cost_h2(h->d_ct[0], h->d_ct[1], h->d_cts[0], h->d_cts[1], d_sky_l,
-                                              d_sky_r, sky_pitch, g, h->d_ch[0], h->d_ch[1], st);
+                                [&] { return sgm::launch_sky_words(s[v].sky, sky_pitch, g, s[v].skw, st); }));
+        HIPCHK(h, timed(h, "vstrip", elems, st, [&] {
+                   return sgm::launch_vstrip(s, nv, h->d_slant_dummy, (float)h->p.p1, (float)h->p.p2, g, st);
                }));
+    } else if (joint) {
+        HIPCHK(h, timed(h, "cost_h", elems, st, [&] { return sgm::launch_cost_h(s, 2, sky_pitch, 1, g, st); }));
         if (vfwd_here) {
             // both views' vertical passes in one launch: W chains per view
             // leave the CUs under-filled at KITTI (K64 2 x 69.7 -> 90.7 us,
@@ -480,19 +476,14 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
             // (view 1's columns first, view 0's last, as the per-view passes
             // ran: stage A then finds more of view 0 in the cache, K64 stage
             // A -3 us, profiles/r05_experiments/r05s_ab_vfwd2.txt)
-            const int v0 = 1, v1 = 0;
-            const PairArgs pa[2] = {vfwd_args(h, v0), vfwd_args(h, v1)};
-            const float *in[2] = {h->d_ch[v0], h->d_ch[v1]};
-            float *out[2] = {cost_buf(h, v0), cost_buf(h, v1)};
-            HIPCHK(h, timed(h, "vfwd", 2.0 * npx * g.D, st,
-                            [&] { return sgm::launch_vfwd(in, out, pa, 2, nullptr, g, st); }));
+            const PairArgs pa[2] = {vfwd_args(h, 1), vfwd_args(h, 0)};
+            const float *in[2] = {s[1].ch, s[0].ch};
+            float *out[2] = {s[1].c, s[0].c};
+            HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(in, out, pa, 2, nullptr, g, st); }));
         }
     } else {
-        if (h->nviews == 2 && (rc = cost_view(h, 1, 1, d_sky_r, sky_pitch, st, vfwd_here)) != SGM_OK)
-            return rc;
-        if ((rc = cost_view(h, 0, right_only ? 1 : 0, right_only ? d_sky_r : d_sky_l, sky_pitch,
-                            st, vfwd_here)) != SGM_OK)
-            return rc;
+        for (int v = nv - 1; v >= 0; --v)  // (slot 1 first)
+            if ((rc = cost_view(h, s, v, sky_pitch, st, vfwd_here)) != SGM_OK) return rc;
     }
     *have_c = vstrip;
     return SGM_OK;

@@ -306,11 +306,6 @@ inline sgm::PairArgs vfwd_args(const sgm_handle *h, int view) {
     return a;
 }
 
-// the census table pair of a DSI (0: left view, 1: right view): the other
-// image's table is the min_disp-shifted one
-inline const uint64_t *ct_left(const sgm_handle *h, int dsi) { return dsi ? h->d_cts[0] : h->d_ct[0]; }
-inline const uint64_t *ct_right(const sgm_handle *h, int dsi) { return dsi ? h->d_ct[1] : h->d_cts[1]; }
-
 // the view's final cost volume C and its T chain (T reuses the horizontally
 // filtered volume, dead once vfwd has read it; an in-place vfwd with T in the
 // second volume measured no faster, profiles/r03_experiments/inplace_c.txt)
@@ -334,7 +329,9 @@ int run_frame(sgm_handle *h, FrameIO f, hipStream_t st);
 int post_filter(sgm_handle *h, float *d_map, int pitch, hipStream_t st, bool to_lk = false);
 int lk_refine(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int pitch,
               float *d_map, int map_pitch, hipStream_t st, bool staged = false);
-int shift_tables(sgm_handle *h, bool left, bool right, hipStream_t st);
+// the cost stage's view slots (sgm_internal.h) and the shifted tables they read
+sgm::CostSlot cost_slot(sgm_handle *h, int slot, int dsi, const uint8_t *sky);
+int shift_tables(sgm_handle *h, const sgm::CostSlot *s, int nviews, hipStream_t st);
 // sgm_stage_aggregate: view 0's aggregation from the final cost volume in
 // d_c[0], whole-volume passes on every handle, into d_disp[0] and d_sub[0]
 int stage_aggregate(sgm_handle *h, hipStream_t st);

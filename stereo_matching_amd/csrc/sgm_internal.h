@@ -1,6 +1,7 @@
-// sgm_internal.h -- kernel launchers and their argument structs (one view's
-// roles: ViewRoles) shared by the host side (sgm_capi.hip, sgm_frame.hip) and
-// the kernel files.  Not part of the public interface.
+// sgm_internal.h -- kernel launchers and their argument structs (one view
+// slot's cost stage: CostSlot; one view's aggregation roles: ViewRoles) shared
+// by the host side (sgm_capi.hip, sgm_frame.hip) and the kernel files.  Not
+// part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -224,15 +225,41 @@ hipError_t launch_bm_wta(const float *cost, float uniq, uint16_t *disp, float *o
 // that of (ctl_s, ctr); with min_disp = 0 the shifted tables are the tables.
 hipError_t launch_ct_shift(const uint64_t *ctl, const uint64_t *ctr, uint64_t *ctl_s, uint64_t *ctr_s,
                            int k, Geom g, hipStream_t st);
-// both views' DSI + horizontal IIR in one launch (both sky masks or neither):
-// view 0 from (ctl, ctr_s), view 1 from (ctl_s, ctr);
-// cost_h2_supported: false when rows do not fit the staged kernel
-bool cost_h2_supported(Geom g, bool sky);
-hipError_t launch_cost_h2(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
-                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
-                          int sky_pitch, Geom g, float *out0, float *out1, hipStream_t st);
-hipError_t launch_cost_h(const uint64_t *ctl, const uint64_t *ctr, const uint8_t *sky,
-                         int sky_pitch, int view, int filter, Geom g, float *out,
+// What one view slot's cost stage takes (sgm_frame.hip's cost_slot wires it to
+// the buffers; slot = the view's index in a frame's buffers).
+struct CostSlot {
+    const uint64_t *ctl, *ctr;  // the census table pair its DSI reads, resolved: DSI 0 the left
+                                // table and the shifted right one, DSI 1 the shifted left one
+                                // and the right one (launch_ct_shift; min_disp = 0: the tables)
+    int dsi;                    // 0: build_dsi_from_table (left view), 1: ..._beta (right view)
+    const uint8_t *sky;         // working-grid sky mask (null: no mask)
+    float *ch;                  // the horizontally filtered volume, or the strip schedule's
+                                // checkpoints, which reuse it
+    uint64_t *skw;              // strips: the mask as one word per pixel (launch_sky_words), null as sky
+    float *c, *l3;              // strips: the final cost C and the L3 volume
+};
+// The kernels that take both slots (cost_h2_kernel, cost_ck_kernel,
+// vstrip_kernel) take the four tables and pick a DSI's pair themselves, (ctl,
+// ctr_s) for DSI 0 and (ctl_s, ctr) for DSI 1: the slots' pairs, put back.  One
+// slot fills its own DSI's pair; nothing reads the other.  With one slot ctl ==
+// ctl_s and ctr == ctr_s (as the tables and their shifted ones are at min_disp
+// = 0), and the kernels take all four as __restrict__: they may only ever be
+// read.
+struct CensusTables {
+    const uint64_t *ctl, *ctr, *ctl_s, *ctr_s;
+};
+inline CensusTables census_tables(const CostSlot *s, int nviews) {
+    const CostSlot &b = s[nviews - 1];
+    return {s->ctl, b.ctr, b.ctl, s->ctr};
+}
+// The cost stage's launches, each over the nviews (1 or 2) slots s[0 .. nviews)
+// of a frame, workgroup z (the strip pass: y) = slot.  Two slots are the frames'
+// (DSI 0, DSI 1); they share a launch when cost_h_staged says so: rows that fit
+// the staged kernels and both sky masks or neither.
+bool cost_h_staged(const CostSlot *s, int nviews, Geom g);
+// DSI + horizontal IIR into s[v].ch (filter = 0: the raw DSI; one slot only).
+// One slot whose rows do not fit the staged kernel runs the global-memory one.
+hipError_t launch_cost_h(const CostSlot *s, int nviews, int sky_pitch, int filter, Geom g,
                          hipStream_t st);
 // The strip schedule of the slanted frames' cost stage (sgm_vstrip.hip):
 // a checkpoint pass of the horizontal IIR (launch_cost_ck, sgm_cost.hip),
@@ -242,26 +269,15 @@ hipError_t launch_cost_h(const uint64_t *ctl, const uint64_t *ctr, const uint8_t
 #define VSTRIP_NC 16
 #endif
 constexpr int kVStripNC = VSTRIP_NC;
-struct VStripArgs {
-    const uint64_t *ctl, *ctr;  // census words (left, right image)
-    const uint64_t *ctl_s, *ctr_s;  // the shifted tables (launch_ct_shift; = ctl, ctr at min_disp 0)
-    const uint64_t *skw0, *skw1; // per view slot: sky flags, one word per pixel (null: no mask)
-    int dsi0, dsi1;             // slot's DSI: 0 left view, 1 right view
-    const float *ck0, *ck1;     // checkpoints (launch_cost_ck)
-    float *c0, *c1;             // final cost C
-    float *l30, *l31;           // L3 volume
-    float *dummy;               // >= 256 floats: the target of idle stores
-    float p1, p2;
-};
 size_t vstrip_strips(Geom g);
 size_t vstrip_ck_floats(Geom g);
-bool vstrip_supported(Geom g, bool sky);
-// (a slot with DSI 0 reads (ctl, ctr_s), one with DSI 1 (ctl_s, ctr))
-hipError_t launch_cost_ck(const uint64_t *ctl, const uint64_t *ctr, const uint64_t *ctl_s,
-                          const uint64_t *ctr_s, const uint8_t *sky0, const uint8_t *sky1,
-                          int sky_pitch, int dsi0, int dsi1, int nviews, Geom g, float *ck0,
-                          float *ck1, hipStream_t st);
-hipError_t launch_vstrip(const VStripArgs &a, int nviews, Geom g, hipStream_t st);
+// scale 1 and cost_h_staged
+bool vstrip_supported(const CostSlot *s, int nviews, Geom g);
+// the checkpoints into s[v].ch
+hipError_t launch_cost_ck(const CostSlot *s, int nviews, int sky_pitch, Geom g, hipStream_t st);
+// dummy: >= 256 floats, the target of idle stores
+hipError_t launch_vstrip(const CostSlot *s, int nviews, float *dummy, float p1, float p2, Geom g,
+                         hipStream_t st);
 // the sky mask as 0/1 words (the strip pass stages 8-byte words only), kept
 // in the Ch buffer after the checkpoints (offset in floats)
 size_t vstrip_sky_words_offset(Geom g);

@@ -5,7 +5,8 @@
 //
 // The two filters are serial chains along perpendicular axes, so a single
 // pass needs, at every row, the horizontal chain's state at the first column
-// it owns.  A checkpoint pass (cost_h_body<..., CK = kVStripNC>, sgm_cost.hip)
+// it owns.  A checkpoint pass (launch_cost_ck, sgm_cost.hip: cost_ck_body, or
+// cost_h_body<..., CK = kVStripNC> under a sky mask)
 // runs the horizontal chains alone and keeps only that state -- the running
 // sum and the two values it will subtract -- at every strip edge: 3 floats
 // per (row, strip, d), 0.5 B per element written and read again here,
@@ -25,6 +26,11 @@
 // Every chain keeps the reference's order of operations (cost_h_body and
 // vfwd_body restate them; this pass computes the same values), so C and L3
 // are bit-identical to cost_h + vfwd_l3 (tests/test_gpu_vstrip.py).
+//
+// Both passes launch over the frame's view slots (CostSlot, sgm_internal.h).
+// The kernel here keeps an argument struct of its own, filled from the slots
+// by launch_vstrip: reading the slots themselves moved its register counts
+// (profiles/cost_stage_merge_codegen.txt).
 #include "sgm_bodies.h"
 
 namespace sgm {
@@ -42,6 +48,19 @@ struct VStripLds {
     float ch[4][NC][64 * V];       // Ch of row r in ring slot r & 3
     float raw[2][NC + 3][64 * V];  // raw costs of a row (the strip's columns + 3)
     uint64_t st[2][VStripStage<V, NC>::N];
+};
+
+// The kernel's arguments (launch_vstrip fills them from the view slots)
+struct VStripArgs {
+    const uint64_t *ctl, *ctr;  // census words (left, right image)
+    const uint64_t *ctl_s, *ctr_s;  // the shifted tables (launch_ct_shift; = ctl, ctr at min_disp 0)
+    const uint64_t *skw0, *skw1; // per view slot: sky flags, one word per pixel (null: no mask)
+    int dsi0, dsi1;             // slot's DSI: 0 left view, 1 right view
+    const float *ck0, *ck1;     // checkpoints (launch_cost_ck)
+    float *c0, *c1;             // final cost C
+    float *l30, *l31;           // L3 volume
+    float *dummy;               // >= 256 floats: the target of idle stores
+    float p1, p2;
 };
 
 size_t vstrip_strips(Geom g) { return (size_t)((g.W + kVStripNC - 1) / kVStripNC); }
@@ -321,7 +340,7 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
         if (it0 + u < NIT) iter(it0 + u, u);
 }
 
-bool vstrip_supported(Geom g, bool sky) { return g.scale == 1 && cost_h2_supported(g, sky); }
+bool vstrip_supported(const CostSlot *s, int nviews, Geom g) { return g.scale == 1 && cost_h_staged(s, nviews, g); }
 
 // The sky mask as one word per pixel (0 or 1) for the strip pass's staging.
 __global__ __launch_bounds__(256) void sky_words_kernel(const uint8_t *__restrict__ sky, int pitch, int H,
@@ -342,8 +361,13 @@ hipError_t launch_sky_words(const uint8_t *sky, int pitch, Geom g, uint64_t *out
     return hipGetLastError();
 }
 
-hipError_t launch_vstrip(const VStripArgs &a, int nviews, Geom g, hipStream_t st) {
+hipError_t launch_vstrip(const CostSlot *s, int nviews, float *dummy, float p1, float p2, Geom g,
+                         hipStream_t st) {
     const dim3 grid((unsigned)vstrip_strips(g), nviews);
+    const CensusTables t = census_tables(s, nviews);
+    const CostSlot &b = s[nviews - 1];  // (one slot: the grid never picks the second)
+    const VStripArgs a = {t.ctl, t.ctr, t.ctl_s, t.ctr_s, s->skw, b.skw, s->dsi, b.dsi, s->ch, b.ch,
+                          s->c,  b.c,   s->l3,   b.l3,    dummy,  p1,    p2};
     constexpr int NV = kVStripNC / 2;
 #ifndef VSTRIP_PD
 #define VSTRIP_PD 4
