@@ -4,14 +4,21 @@ TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() (as the
 checker) and bench.py's cpu_baseline leg.  The product package
 ``stereo_matching_amd`` never imports this module.
 
-Parity status: "parity unpinned" (see sgm_oracle.h and DESIGN.md): the
-reference is unbuildable in this image and ships no golden vectors.
+Parity status (see sgm_oracle.h and DESIGN.md "Oracle and its pinning"):
+pinned to the reference's own binaries from the census on.  build_ref()
+compiles the reference's src/{Solver,SGM,cost,BM}.cpp unmodified against
+stand-in headers (oracle/ref/) into oracle/_ref/; run_ref() runs them; the
+recorded outputs are tests/golden/ref_*.npz, and tests/test_reference_parity.py
+compares this oracle with them bit for bit.  Not pinned: cv::GaussianBlur's own
+arithmetic, LKRefine, and everything the reference does not have.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -29,6 +36,84 @@ def build(force: bool = False) -> str:
                                           for f in ("sgm_oracle.c", "sgm_oracle.h", "Makefile"))):
         subprocess.run(["make", "-s", "-C", _HERE, "liboracle_sgm.so"], check=True)
     return _LIB_PATH
+
+
+# ------------------------------------------------------------------ reference
+_REF_OUT = os.path.join(_HERE, "_ref")
+_REF_DRIVER = os.path.join(_REF_OUT, "ref_driver")
+REF_MODES = {"stages": 0, "process": 1, "bm": 2, "post_filter": 3, "subpixel": 4, "colormap": 5}
+
+
+def reference_dir():
+    """The reference checkout (SGM_REFERENCE_DIR, default: `reference` next to
+    the repository), or None when it does not hold the four source files."""
+    d = os.environ.get("SGM_REFERENCE_DIR") or os.path.join(os.path.dirname(os.path.dirname(_HERE)),
+                                                            "reference")
+    ok = all(os.path.isfile(os.path.join(d, "src", f))
+             for f in ("Solver.cpp", "SGM.cpp", "cost.cpp", "BM.cpp"))
+    return os.path.abspath(d) if ok else None
+
+
+def build_ref():
+    """Compile the reference's own sources and oracle/ref/ref_driver.cpp into
+    oracle/_ref/ (Makefile target `ref`).  Returns the driver's path, or None
+    when there is no reference to compile."""
+    d = reference_dir()
+    if d is None:
+        return None
+    subprocess.run(["make", "-s", "-C", _HERE, "ref", "SGM_REFERENCE_DIR=" + d], check=True,
+                   stdout=subprocess.DEVNULL)
+    return _REF_DRIVER
+
+
+def ref_driver():
+    """Path of a built driver whose reference is still there, else None."""
+    return _REF_DRIVER if reference_dir() and os.access(_REF_DRIVER, os.X_OK) else None
+
+
+def run_ref(mode, left, right, D, scale=1, sky_l=None, sky_r=None, fmap=None, blur=True,
+            threads=1, driver=None):
+    """Run the reference through the driver; returns {name: array} in the
+    order the driver wrote them (request and record layout: ref_driver.cpp)."""
+    driver = driver or ref_driver()
+    if driver is None:
+        raise RuntimeError("no reference driver: oracle.build_ref() found no reference")
+    left = _c(left, np.uint8)
+    right = _c(right, np.uint8)
+    h, w = left.shape
+    H, W = h // scale, w // scale
+    has_sky = sky_l is not None
+    head = struct.pack("<10i", 0x51524753, REF_MODES[mode], h, w, scale, D, int(bool(blur)),
+                       int(has_sky), int(fmap is not None), 0)
+    env = dict(os.environ, OMP_NUM_THREADS=str(threads), OMP_DYNAMIC="false")
+    with tempfile.TemporaryDirectory() as tmp:
+        req, res = os.path.join(tmp, "req.bin"), os.path.join(tmp, "out.bin")
+        with open(req, "wb") as fh:
+            fh.write(head)
+            fh.write(left.tobytes())
+            fh.write(right.tobytes())
+            if has_sky:
+                for m in (sky_l, sky_r):
+                    m = _c(m, np.uint8)
+                    assert m.shape == (H, W)
+                    fh.write(m.tobytes())
+            if fmap is not None:
+                fmap = _c(fmap, np.float32)
+                assert fmap.shape == (H, W)
+                fh.write(fmap.tobytes())
+        subprocess.run([driver, req, res], check=True, env=env, stdout=subprocess.DEVNULL, timeout=300)
+        out = {}
+        dtypes = (np.uint8, np.float32, np.uint64)
+        with open(res, "rb") as fh:
+            while True:
+                rec = fh.read(32)
+                if not rec:
+                    break
+                name = rec[:16].rstrip(b"\0").decode()
+                kind, d0, d1, d2 = struct.unpack("<4i", rec[16:])
+                shape = (d0, d1, d2) if d2 else (d0, d1)
+                out[name] = np.fromfile(fh, dtypes[kind], int(np.prod(shape))).reshape(shape)
+    return out
 
 
 class _Result(ctypes.Structure):

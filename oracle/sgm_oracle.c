@@ -5,9 +5,10 @@
  * __graft_entry__.smoke() and the timed CPU baseline of bench.py.  Never
  * linked into, loaded by, or called from the product library.
  *
- * PARITY STATUS: "parity unpinned" -- the reference is unbuildable here
- * (needs OpenCV + ROS headers, inc/global.h:11-20) and ships no golden
- * vectors; see sgm_oracle.h and DESIGN.md section "Oracle".
+ * PARITY STATUS: pinned from the census on to what the reference's own
+ * unmodified sources compute (oracle/ref/, tests/golden/ref_*,
+ * tests/test_reference_parity.py); see sgm_oracle.h and DESIGN.md section
+ * "Oracle and its pinning" for what stays outside that pin.
  *
  * Three schedules of the same arithmetic, bit-identical outputs:
  *  - orc_process: per-stage functions with 10 volumes (cost, S, L1..L8), the

@@ -7,14 +7,17 @@
  * and by bench.py's cpu_baseline leg as the timed CPU baseline ("kind": "port",
  * orc_process_refplace: the reference's OpenMP placement).
  *
- * PARITY STATUS: "parity unpinned".  The reference (C++/OpenCV/ROS catkin
- * package) is unbuildable in this image: src/{Solver,SGM,cost}.cpp include
- * inc/global.h, which pulls OpenCV, ROS, cv_bridge and image_transport headers
- * (inc/global.h:11-20) that the image does not have, and the rules of this
- * build forbid writing stand-ins for them.  The reference ships no tests, no
- * fixtures and no golden vectors.  This restatement is
- * therefore cross-checked only against an independent pure-Python restatement
- * (tests/pyref.py) and hand-derived known-answer cases (tests/test_oracle.py).
+ * PARITY STATUS: pinned to the reference's own binaries from the census on.
+ * The reference's src/{Solver,SGM,cost,BM}.cpp are compiled unmodified against
+ * stand-in headers (oracle/ref/, oracle/Makefile target ref) and run through
+ * oracle/ref/ref_driver.cpp; what they computed is recorded in
+ * tests/golden/ref_*, and tests/test_reference_parity.py compares every stage
+ * of this file with it bit for bit.  Not pinned that way: cv::GaussianBlur's
+ * own arithmetic (orc_blur is a pinned formula), LKRefine, the sky detector
+ * (pinned by the reference's example output), D = 256, non-default
+ * parameters, and what the reference does not have (DESIGN.md "Oracle and its
+ * pinning").  There the cross-checks are tests/pyref.py and the hand-derived
+ * known answers of tests/test_oracle.py.
  *
  * Every function cites the reference lines it restates.  Float arithmetic is
  * written in the reference's exact association order and must be compiled with

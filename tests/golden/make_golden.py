@@ -3,8 +3,9 @@
 Run from the repo root:  python tests/golden/make_golden.py
 Inputs are the portable splitmix64 synthetic pairs of
 stereo_matching_amd/synthetic.py; outputs come from the CPU oracle
-(oracle/sgm_oracle.c), whose parity with the reference is UNPINNED (the
-reference cannot be built in this image and ships no vectors).
+(oracle/sgm_oracle.c).  These are regression vectors of the oracle; what pins
+the oracle to the reference are the ref_* fixtures, which the reference's own
+sources produce (make_ref_golden.py, DESIGN.md "Oracle and its pinning").
 Each fixture stores inputs and every H x W output in full, and sha256 hashes
 of the census words, the left cost volume and the eight left path volumes
 (hashes.json) to keep the fixtures small.

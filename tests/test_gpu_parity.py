@@ -2,8 +2,9 @@
 
 Bar (DESIGN.md "Parity"): bit-exact for every stage -- census words, cost
 volumes, path costs, WTA indices, sub-pixel floats, LR-checked floats --
-compared as raw bits.  Oracle: oracle/sgm_oracle.c ("parity unpinned": the
-reference itself cannot be built here).
+compared as raw bits.  Oracle: oracle/sgm_oracle.c, itself pinned to the
+reference's own binaries from the census on (tests/test_reference_parity.py);
+tests/test_gpu_reference.py compares the library with those directly.
 """
 from __future__ import annotations
 
