@@ -35,6 +35,9 @@
  *                                through stereoRectify's Q on the GPU: xyz() (CV_32FC3, what
  *                                cv::reprojectImageTo3D gives), depth() (CV_32FC1), depth16()
  *                                (CV_16UC1, REP 118's millimetres); reproject(disp, ...) on any map
+ *   aggregate_device(vol, ...)   (not in the reference) a caller's DEVICE cost volume through the
+ *                                path aggregation, the LR check and post_filter (sgm_aggregate_device);
+ *                                import_volume_device(vol, view, dst) is its first launch alone
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -362,6 +365,23 @@ public:
     const Mat &xyz() const { return product(SGM_REPROJECT_XYZ, xyz_, "xyz"); }
     const Mat &depth() const { return product(SGM_REPROJECT_DEPTH, depth_, "depth"); }
     const Mat &depth16() const { return product(SGM_REPROJECT_DEPTH16, depth16_, "depth16"); }
+
+    // A caller's DEVICE cost volume (sgm_volume: learned costs, AD/SAD/MI, ...)
+    // through the frame from the cost volume on (sgm_aggregate_device): the
+    // path aggregation, the LR check, post_filter and the reprojection as the
+    // handle is set up; d_out a DEVICE rows x cols f32 map (out_pitch floats),
+    // d_raw the left raw map or null.  Enqueue only: the caller synchronises.
+    void aggregate_device(const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw = nullptr,
+                          void *stream = nullptr) {
+        if (sgm_aggregate_device(handle_, &vol, d_out, out_pitch, d_raw, stream) != SGM_OK)
+            fail("aggregate_device", sgm_last_error(handle_));
+    }
+    // Its first launch alone (sgm_volume_import_device): the dense fp32 rows x
+    // cols x D volume of `view` (the right view's derived from the left one)
+    void import_volume_device(const sgm_volume &vol, int view, float *d_dst, void *stream = nullptr) {
+        if (sgm_volume_import_device(handle_, &vol, view, d_dst, stream) != SGM_OK)
+            fail("import_volume_device", sgm_last_error(handle_));
+    }
 
     // The pixel format of the images process() takes (sgm_set_input_format):
     // SGM_PIX_BGR8 / SGM_PIX_RGB8 take CV_8UC3 Mats, SGM_PIX_BGRA8 /

@@ -507,6 +507,84 @@ int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_ri
                        const uint8_t *d_sky_l, const uint8_t *d_sky_r, int sky_pitch,
                        float *d_out, int out_pitch, uint16_t *d_raw_disp, void *stream);
 
+/* ---- a caller's cost volume: learned costs in, maps out ----
+ *
+ * For matching costs the library does not build itself (a network's, AD/SAD/MI,
+ * a census of another window): sgm_volume describes the LEFT view's cost volume
+ * on the working grid, in DEVICE memory.  Element (i, j, d), i < rows, j < cols,
+ * d < D, is at d_cost[i * stride_row + j * stride_col + d * stride_disp]
+ * (strides in ELEMENTS); index d stands for disparity min_disp + d.  Exactly
+ * one of stride_disp == 1 ("HWD", the library's own layout) and stride_col == 1
+ * ("DHW", torch's [D, H, W]) must hold; the other two strides may be anything
+ * non-negative that keeps every element at its own address (padded rows and
+ * planes, one item of a [B, D, H, W] batch): sorted by stride, each stride is at
+ * least the previous stride times the previous extent.  d_cost is aligned to
+ * its element type; 16-byte accesses are used wherever an address allows.
+ * Costs are finite and in [0, 999999] (the reference's largest cost,
+ * Solver.cpp:176; sgm_create's uniqueness bound rests on it).  Values outside
+ * that range, NaN and Inf are not checked: the maps are then not pinned, but no
+ * address depends on a cost, so memory safety is unaffected. */
+enum { SGM_VOL_F32 = 0, SGM_VOL_F16 = 1 };
+typedef struct sgm_volume {
+    const void *d_cost;          /* DEVICE memory */
+    int dtype;                   /* SGM_VOL_F32 | SGM_VOL_F16 (IEEE binary16) */
+    long long stride_row, stride_col, stride_disp;   /* in ELEMENTS */
+} sgm_volume;
+
+/* Writes the dense fp32 rows x cols x D HWD volume of `view` into d_dst.
+ * SGM_VIEW_LEFT: the re-layout, bit for bit (f16 to f32 is exact).
+ * SGM_VIEW_RIGHT: the right view's volume derived from the left one,
+ *   C_R[i, j, d] = C_L[i, min(j + (d + min_disp) / scale, cols - 1), d]
+ * (integer division): build_dsi_from_table_beta's own column index
+ * (Solver.cpp:239, with sgm_set_min_disp's shift).  Where that index is not
+ * clamped this is an identity of the reference's raw DSIs (ham(ctL[j + k],
+ * ctR[j]) is the left DSI at column j + k).  In the clamped columns (j + (d +
+ * min_disp) / scale > cols - 1) it DIFFERS from the reference, which compares
+ * ctL[cols - 1] with ctR[j] there: a caller's volume holds no such cost, and
+ * the left volume's last column is the only choice it allows.
+ * One launch on `stream` (NULL = the handle's stream), no host wait, no
+ * allocation: capturable into a HIP graph.  Any handle of the working size
+ * serves, aux_only included (its min_disp is the one used).  d_dst must not
+ * overlap the source (not checked).  SGM_ERR_INVALID_ARG, with a message, for a
+ * NULL pointer, a bad dtype or view, strides outside the rule above, or
+ * hipStreamLegacy as the stream.
+ * The legacy default stream is NOT accepted by this call and by
+ * sgm_aggregate_device (unlike the entry points above): a call on a caller's
+ * stream records its end there, and the next call on another stream waits on
+ * that event; with the event recorded on hipStreamLegacy that wait crashed the
+ * host process under PyTorch's HIP runtime (seen once, after a call on the
+ * legacy stream followed by sgm_stage_confidence; the runtime-side reason is
+ * not established).  Work on the legacy stream is ordered with these calls by
+ * an event of the caller's: record it there, make a created stream (or the
+ * handle's own, sgm_get_stream) wait for it, and pass that stream. */
+int sgm_volume_import_device(sgm_handle *h, const sgm_volume *vol, int view, float *d_dst, void *stream);
+
+/* The frame from the cost volume on: imports vol into the handle's own cost
+ * buffer(s) (one launch writes both views' volumes on a views == 2 handle),
+ * runs the aggregation sgm_stage_aggregate runs (the L3 checkpoints from the
+ * final volume, then the whole-volume 8-path passes, or the 4-path passes on a
+ * paths == 4 handle; with two views, view after view), then exactly what a
+ * frame does after its aggregation: the LR check (views == 2) into d_out,
+ * post_filter with params.post_filter (adaptive, or with a launch budget), the
+ * reprojection launch with sgm_set_reproject, the confidence maps with
+ * sgm_set_confidence.  Maps leave in true disparity (+ min_disp); d_raw is the
+ * left raw WTA map or NULL.  The cost filters, the sky override and the census
+ * are the caller's business: masks, sky_detect and blur play no part.
+ * Works on handles of every schedule (the aggregation itself always takes the
+ * whole-volume passes, whose buffers every frame handle holds: no call
+ * allocates).  It waits for nothing on the host given a fill budget or no post
+ * filter, and can then be captured into and replayed from a HIP graph; call it
+ * once eagerly before capturing, as for frames.  Stream ordering, the event
+ * record and sgm_check behave as for sgm_process_device.  The import is timed
+ * under the profile class "vol_import".
+ * SGM_ERR_INVALID_ARG, with a message and nothing enqueued, for NULL pointers,
+ * a bad dtype, strides outside the rule above, hipStreamLegacy as the stream
+ * (see sgm_volume_import_device), out_pitch < cols, BM handles,
+ * aux_only handles, SGM_VIEW_RIGHT handles, and handles with params.lk_refine
+ * (LKRefine needs images: run sgm_lk_refine_device afterwards). */
+int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int out_pitch,
+                         uint16_t *d_raw, void *stream);
+
 /* Post-sync validity check of the frames enqueued so far (the reference has
  * no asynchronous work to check: SGM::process is synchronous, SGM.cpp:32-826).
  * Waits for the handle's last call's work (its stream, or the event the call

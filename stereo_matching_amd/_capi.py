@@ -48,7 +48,11 @@ EXPORTS = (
     "sgm_get_input_gray", "sgm_stage_input_gray",
     "sgm_set_reproject", "sgm_get_reproject", "sgm_reproject_device", "sgm_stage_reproject",
     "sgm_get_reprojected", "sgm_stage_reprojected", "sgm_camera_q",
+    "sgm_volume_import_device", "sgm_aggregate_device",
 )
+# sgm_volume's element types (SGM_VOL_*)
+SGM_VOL_F32 = 0
+SGM_VOL_F16 = 1
 # sgm_set_input_format's pixel formats (SGM_PIX_*), by their ROS encoding names
 PIX_FORMATS = {"gray8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4}
 PIX_BYTES = {0: 1, 1: 3, 2: 3, 3: 4, 4: 4}
@@ -88,6 +92,13 @@ class Reproject(ctypes.Structure):
     and depth16's scale."""
     _fields_ = [("q", ctypes.c_double * 16), ("outputs", ctypes.c_int),
                 ("max_range", ctypes.c_float), ("depth_scale", ctypes.c_float)]
+
+
+class Volume(ctypes.Structure):
+    """sgm_volume: a caller's device cost volume, strides in elements."""
+    _fields_ = [("d_cost", ctypes.c_void_p), ("dtype", ctypes.c_int),
+                ("stride_row", ctypes.c_longlong), ("stride_col", ctypes.c_longlong),
+                ("stride_disp", ctypes.c_longlong)]
 
 
 class KernelStat(ctypes.Structure):
@@ -200,6 +211,9 @@ def lib():
     L.sgm_get_reprojected.argtypes = [P, I, ctypes.POINTER(P), ctypes.POINTER(I)]
     L.sgm_stage_reprojected.argtypes = [P, I, P]
     L.sgm_camera_q.argtypes = [ctypes.POINTER(Camera), ctypes.POINTER(ctypes.c_double)]
+    VP = ctypes.POINTER(Volume)
+    L.sgm_volume_import_device.argtypes = [P, VP, I, P, P]
+    L.sgm_aggregate_device.argtypes = [P, VP, P, I, P, P]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

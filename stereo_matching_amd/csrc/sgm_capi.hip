@@ -9,6 +9,7 @@
 // scratch in the constructors, Solver.cpp:18-27 and SGM.cpp:7-24), apart from
 // the maps the setters switch on and off.
 #include "sgm_handle.h"
+#include "sgm_volume_args.h"
 
 #include <float.h>
 #include <stdlib.h>
@@ -652,6 +653,64 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
         memcpy(out + (size_t)i * out_pitch, pout + (size_t)i * h->g.W, h->g.W * sizeof(float));
     if (raw_disp) memcpy(raw_disp, praw, npx * sizeof(uint16_t));
     return SGM_OK;
+}
+
+// The checks a caller's volume passes before anything is enqueued (sgm_volume_args.h); `fn`: the
+// entry point's name, for the message.
+static int check_volume(sgm_handle *h, const char *fn, const sgm_volume *vol, void *stream) {
+    if (!vol || !vol->d_cost) return set_err(h, SGM_ERR_INVALID_ARG, "%s: NULL volume", fn);
+    // (a call's end recorded on the legacy stream is an event the next call on another stream
+    // would wait on; that wait crashed the host in torch's HIP runtime: sgm_hip.h)
+    if (stream == (void *)hipStreamLegacy)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "%s: hipStreamLegacy is not accepted; pass a created stream, or NULL for the handle's own", fn);
+    char why[256];
+    if (!sgm::volume_layout(vol->dtype, vol->stride_row, vol->stride_col, vol->stride_disp, h->g.H, h->g.W,
+                            h->g.D, why, sizeof(why)))
+        return set_err(h, SGM_ERR_INVALID_ARG, "%s: %s", fn, why);
+    if ((uintptr_t)vol->d_cost % (uintptr_t)sgm::volume_elem_bytes(vol->dtype))
+        return set_err(h, SGM_ERR_INVALID_ARG, "%s: d_cost is not aligned to its element type", fn);
+    return SGM_OK;
+}
+
+int sgm_volume_import_device(sgm_handle *h, const sgm_volume *vol, int view, float *d_dst, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (int rc = check_volume(h, "sgm_volume_import_device", vol, stream)) return rc;
+    if (!d_dst || (uintptr_t)d_dst % sizeof(float))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_volume_import_device: d_dst is NULL or not a float pointer");
+    if (view != SGM_VIEW_LEFT && view != SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_volume_import_device: view must be SGM_VIEW_LEFT or SGM_VIEW_RIGHT");
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "vol_import", vol_elems(h->g), st, [&] {
+               return sgm::launch_volume_import(vol->d_cost, vol->dtype, vol->stride_row, vol->stride_col,
+                                                vol->stride_disp, view == SGM_VIEW_LEFT ? d_dst : nullptr,
+                                                view == SGM_VIEW_RIGHT ? d_dst : nullptr, h->min_disp, h->g, st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int out_pitch, uint16_t *d_raw,
+                         void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (int rc = check_frame_err(h)) return rc;
+    if (h->p.aux_only)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_aggregate_device: handle created with aux_only (no cost volumes)");
+    if (h->p.solver != SGM_SOLVER_SGM)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_aggregate_device: a BM handle aggregates nothing");
+    if (h->p.view == SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_aggregate_device: a SGM_VIEW_RIGHT handle (the volume is the left view's)");
+    if (h->p.lk_refine)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_aggregate_device: params.lk_refine needs images; run sgm_lk_refine_device afterwards");
+    if (int rc = check_volume(h, "sgm_aggregate_device", vol, stream)) return rc;
+    if (!d_out || out_pitch < h->g.W)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_aggregate_device: d_out is NULL or out_pitch below cols");
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    return aggregate_volume(h, *vol, d_out, out_pitch, d_raw, scope.st);
 }
 
 #ifdef SGM_SLANT_DEBUG

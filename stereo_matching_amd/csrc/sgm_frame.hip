@@ -613,6 +613,50 @@ int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
     return h->paths4 ? aggregate4(h, 1, &r, st) : aggregate(h, &r, 1, st, true);
 }
 
+int sgm::aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,
+                          hipStream_t st) {
+    const Geom g = h->g;
+    const int nv = h->nviews;
+    const double elems = vol_elems(g);
+    // one launch reads the caller's volume and writes every view's C
+    HIPCHK(h, timed(h, "vol_import", nv * elems, st, [&] {
+               return sgm::launch_volume_import(vol.d_cost, vol.dtype, vol.stride_row, vol.stride_col,
+                                                vol.stride_disp, cost_buf(h, 0), nv == 2 ? cost_buf(h, 1) : nullptr,
+                                                h->min_disp, g, st);
+           }));
+    // the maps' wiring is frame_maps': a dense one-view map straight from the final pass, the
+    // handle's sub-pixel layout for the LR check
+    const bool direct_out = nv == 1 && out_pitch == g.W;
+    ViewRoles r[2] = {};
+    r[0] = view_roles(h, 0, d_raw, direct_out ? d_out : h->d_sub[0], h->sub_cm);
+    if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    // stage_aggregate's passes: the L3 checkpoints from the final volume, then the whole-volume
+    // aggregation, whatever schedule the handle's frames run
+    int rc = SGM_OK;
+    for (int v = 0; v < nv; ++v)
+        HIPCHK(h, timed(h, "pair_fwd_L3", elems, st,
+                        [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r[v].fin, g, st); }));
+    if (h->paths4) rc = aggregate4(h, nv, r, st);
+    else
+        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
+    if (rc != SGM_OK) return rc;
+    if (nv == 2) {
+        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
+                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], d_out, out_pitch,
+                                                        h->p.lr_max_diff, h->gt, st)
+                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, d_out, out_pitch,
+                                                     h->p.lr_max_diff, h->gt, st);
+               }));
+    } else if (!direct_out) {
+        HIPCHK(h, hipMemcpy2DAsync(d_out, (size_t)out_pitch * sizeof(float), h->d_sub[0],
+                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
+                                   hipMemcpyDeviceToDevice, st));
+    }
+    if (h->p.post_filter && (rc = sgm::post_filter(h, d_out, out_pitch, st)) != SGM_OK) return rc;
+    if (h->rp_on && h->rp.outputs) return sgm::reproject_frame(h, d_out, out_pitch, st);
+    return SGM_OK;
+}
+
 int sgm::run_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
     if (int rc = frame_maps(h, f, st)) return rc;
     // The output slot: with reprojection set, one launch more reads the frame's

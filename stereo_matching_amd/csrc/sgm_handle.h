@@ -335,6 +335,11 @@ int shift_tables(sgm_handle *h, const sgm::CostSlot *s, int nviews, hipStream_t 
 // sgm_stage_aggregate: view 0's aggregation from the final cost volume in
 // d_c[0], whole-volume passes on every handle, into d_disp[0] and d_sub[0]
 int stage_aggregate(sgm_handle *h, hipStream_t st);
+// sgm_aggregate_device: the frame from the cost volume on: the caller's volume
+// imported into every view's C, stage_aggregate's whole-volume passes view after view (both at
+// once on a 4-path handle), then the LR check, post_filter and the output slot as run_frame's
+int aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,
+                     hipStream_t st);
 bool slant_default(Geom g, int nviews);
 int band_rows_for(Geom g);
 int slant_cus();

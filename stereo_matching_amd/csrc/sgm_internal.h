@@ -336,6 +336,14 @@ hipError_t launch_reproject(const double *q, const float *disp, int pitch, float
                             float *depth, int depth_pitch, uint16_t *depth16, int depth16_pitch,
                             float invalid, float max_range, float depth_scale, int form, Geom g,
                             hipStream_t st);
+// A caller's cost volume (sgm_volume.hip) into dense fp32 HWD volumes in one launch:
+// src of dtype SGM_VOL_* with element (i, j, d) at src[i * stride_row + j * stride_col + d * stride_disp]
+// (strides in elements, one of stride_col and stride_disp is 1: sgm_volume_args.h) -> dst_l, the
+// re-layout, and dst_r, C_R[i, j, d] = C_L[i, min(j + (d + min_disp) / scale, W - 1), d]; a null
+// destination is skipped.  The destinations must not overlap the source.
+hipError_t launch_volume_import(const void *src, int dtype, long long stride_row, long long stride_col,
+                                long long stride_disp, float *dst_l, float *dst_r, int min_disp, Geom g,
+                                hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

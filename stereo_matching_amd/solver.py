@@ -502,6 +502,112 @@ class SGM:
         check(lib().sgm_camera_q(ctypes.byref(cam), q))
         return np.array(list(q), np.float64).reshape(4, 4)
 
+    # ------------------------------------------------ a caller's cost volume
+    def _volume(self, cost, layout):
+        """(torch, sgm_volume) of a torch device cost volume: shape
+        (rows, cols, D), or (D, rows, cols) with layout="dhw"; strides as the
+        tensor has them (nothing is made contiguous)."""
+        if isinstance(cost, np.ndarray) or not (hasattr(cost, "data_ptr") and hasattr(cost, "stride")):
+            raise TypeError("cost must be a torch device tensor; for a host numpy H x W x D float32 "
+                            "volume use stage_aggregate()")
+        import torch
+        if not cost.is_cuda or cost.device.index != self.device:
+            raise ValueError(f"cost must live on the handle's device cuda:{self.device}, got {cost.device}")
+        if cost.dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"cost must be float32 or float16, got {cost.dtype}")
+        hwd, dhw = (self.rows, self.cols, self.max_disp), (self.max_disp, self.rows, self.cols)
+        shape = tuple(cost.shape)
+        if layout is None:
+            if shape == hwd and shape == dhw:
+                raise ValueError(f"cost of shape {shape} reads as (rows, cols, D) and as (D, rows, cols): "
+                                 "pass layout='hwd' or layout='dhw'")
+            layout = "hwd" if shape == hwd else "dhw" if shape == dhw else None
+            if layout is None:
+                raise ValueError(f"cost: expected shape {hwd} or {dhw}, got {shape}")
+        elif layout not in ("hwd", "dhw"):
+            raise ValueError(f"layout must be 'hwd', 'dhw' or None, got {layout!r}")
+        elif shape != (hwd if layout == "hwd" else dhw):
+            raise ValueError(f"cost: expected shape {hwd if layout == 'hwd' else dhw} for layout "
+                             f"{layout!r}, got {shape}")
+        st = cost.stride()
+        sr, sc, sd = st if layout == "hwd" else (st[1], st[2], st[0])
+        vol = _capi.Volume(cost.data_ptr(), _capi.SGM_VOL_F16 if cost.dtype == torch.float16 else _capi.SGM_VOL_F32,
+                           sr, sc, sd)
+        return torch, vol
+
+    def _on_torch_stream(self, torch, tensor, stream, call) -> None:
+        """call(stream argument) ordered on torch's work.  stream: a
+        hipStream_t handle (e.g. a torch stream's cuda_stream), or None for the
+        tensor's device's current torch stream, so that the call is ordered
+        after the tensor's producer and before what torch enqueues next.
+        torch's default stream has no handle of its own: its cuda_stream is 0,
+        the legacy stream, which the two volume entry points refuse
+        (sgm_hip.h: a later call on another stream would wait on an event
+        recorded on it, and that wait crashed the process).  For it -- current
+        or passed as stream=0 -- the call runs on the handle's own stream
+        between two stream waits, with the same ordering."""
+        if stream is None:
+            stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        if stream:
+            call(_stream(stream))
+            return
+        cur = torch.cuda.default_stream(tensor.device)
+        own = torch.cuda.ExternalStream(self.stream, device=tensor.device)
+        own.wait_stream(cur)
+        call(_stream(None))
+        cur.wait_stream(own)
+
+    def aggregate(self, cost, *, layout=None, out=None, raw=None, stream=None):
+        """sgm_aggregate_device: a caller's cost volume (a torch device tensor,
+        float32 or float16, of shape (rows, cols, D), or (D, rows, cols) with
+        layout="dhw"; any strides with a unit column or disparity stride, e.g.
+        one item of a [B, D, H, W] batch) through the frame from the cost
+        volume on: path aggregation, WTA, sub-pixel, the LR check (views = 2,
+        against the right view's volume derived from this one), post_filter,
+        reprojection and confidence as the handle is set up.  Returns `out`, a
+        torch float32 (rows, cols) tensor on the same device (allocated when
+        None); raw: an optional (rows, cols) int16/uint16 tensor for the left
+        raw WTA map.  Enqueued on `stream` (default: the device's current torch
+        stream; 0: torch's default stream); get_confidence(), get_xyz(),
+        get_depth() and check() work after it as after a frame.  With an
+        explicit `stream` other than the one the tensors were allocated on,
+        the caller keeps `cost`, `out` and `raw` alive and ordered until the
+        call's work is done (tensor.record_stream), as for any torch tensor
+        used on a side stream.  Costs: finite, in [0, 999999]."""
+        torch, vol = self._volume(cost, layout)
+        if out is None:
+            out = torch.empty((self.rows, self.cols), dtype=torch.float32, device=cost.device)
+        if (out.dtype != torch.float32 or tuple(out.shape) != (self.rows, self.cols) or out.device != cost.device
+                or out.stride(1) != 1):
+            raise ValueError(f"out must be a float32 {(self.rows, self.cols)} tensor on {cost.device} with unit "
+                             "column stride")
+        if raw is not None and (raw.element_size() != 2 or tuple(raw.shape) != (self.rows, self.cols)
+                                or raw.device != cost.device or not raw.is_contiguous()):
+            raise ValueError(f"raw must be a contiguous 16-bit {(self.rows, self.cols)} tensor on {cost.device}")
+        self._on_torch_stream(torch, cost, stream, lambda st: check(self._lib.sgm_aggregate_device(
+            self._h, ctypes.byref(vol), ctypes.c_void_p(out.data_ptr()), out.stride(0),
+            ctypes.c_void_p(raw.data_ptr() if raw is not None else None), st), self._h))
+        return out
+
+    def import_volume(self, cost, view: int = 0, *, layout=None, out=None, stream=None):
+        """sgm_volume_import_device: the dense float32 (rows, cols, D) volume of
+        `view` (0 = left: the re-layout; 1 = right: C_L[i, min(j + (d +
+        min_disp) // scale, cols - 1), d]) of a torch device cost volume, as a
+        torch tensor on the same device (`out`, allocated when None).  One
+        launch on `stream` (default: the device's current torch stream; the
+        tensors' lifetime on another stream is the caller's, as for
+        aggregate)."""
+        torch, vol = self._volume(cost, layout)
+        shape = (self.rows, self.cols, self.max_disp)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=cost.device)
+        if (out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != cost.device
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {cost.device}")
+        self._on_torch_stream(torch, cost, stream, lambda st: check(self._lib.sgm_volume_import_device(
+            self._h, ctypes.byref(vol), int(view), ctypes.c_void_p(out.data_ptr()), st), self._h))
+        return out
+
     def check(self) -> None:
         """sgm_check: wait for the frames enqueued so far and raise SGMError
         (SGM_ERR_HIP) if a slanted-pass hand-off gave up, or a fixed-budget

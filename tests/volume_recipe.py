@@ -1,0 +1,152 @@
+"""Expected maps of a caller's cost volume (sgm_aggregate_device),
+composed from the oracle's stage functions.
+
+From any (H, W, D) float32 volume of the LEFT view: the derived right volume
+C_R[i, j, d] = C_L[i, min(j + (d + m) // s, W - 1), d] (numpy), each view's
+aggregation (oracle.path x 8 + oracle.aggregate, or paths4_recipe's 4-path sum),
+oracle.wta, oracle.subpixel, the confidence quotient, oracle.lr_check and
+oracle.post_filter -- the frame from C on.  tests/test_volume_cpu.py ties it to
+oracle.process.  Also the volumes the GPU tests use and the strided sources
+they are handed in.
+
+TEST INFRASTRUCTURE ONLY.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+import oracle
+from confidence_recipe import ratio_of
+from paths4_recipe import aggregate as aggregate4, census
+from stereo_matching_amd import synthetic
+
+
+def derive_right(C, m=0, s=1):
+    """The right view's volume of a left volume C (H, W, D), minimum disparity m, scale s."""
+    H, W, D = C.shape
+    j = np.arange(W)[:, None] + (np.arange(D)[None, :] + m) // s
+    j = np.minimum(j, W - 1)
+    return np.ascontiguousarray(C[:, j, np.arange(D)[None, :]])
+
+
+def unclamped(W, D, m=0, s=1):
+    """(W, D) mask of the elements whose column index j + (d + m) // s is not clamped."""
+    return np.arange(W)[:, None] + (np.arange(D)[None, :] + m) // s <= W - 1
+
+
+def view_maps(C, m, paths):
+    C = np.ascontiguousarray(C, np.float32)
+    if paths == 8:
+        S = oracle.aggregate([oracle.path(C, k)[0] for k in range(8)])
+    else:
+        S = aggregate4(C, 4)
+    d = oracle.wta(S)
+    f = oracle.subpixel(d, S)
+    return d + m, (f + np.float32(m)).astype(np.float32), ratio_of(S)
+
+
+def recipe(C, m=0, s=1, paths=8):
+    """Every map of the frame from C on, in true disparity: "disp", "sub", "ratio" (left view),
+    "sub_beta", "ratio_beta" (the derived right view), "lr" and "final" (post-filtered)."""
+    H, W, D = C.shape
+    out = {}
+    out["disp"], out["sub"], out["ratio"] = view_maps(C, m, paths)
+    _, out["sub_beta"], out["ratio_beta"] = view_maps(derive_right(C, m, s), m, paths)
+    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
+    out["final"] = oracle.post_filter(out["lr"], D + m, s)
+    return out
+
+
+def road_pair(h, w, D, s=1):
+    return synthetic.stereo_pair(h * s, w * s, D, pair_index=2, kind="road")
+
+
+def road_tables(h, w, D, s=1):
+    left, right = road_pair(h, w, D, s)
+    return census(left, s), census(right, s)
+
+
+def road_volume(h, w, D, s=1):
+    """The oracle's filtered left DSI of a synthetic road pair on an h x w working grid."""
+    ctl, ctr = road_tables(h, w, D, s)
+    return oracle.vfilter(oracle.hfilter(oracle.dsi(ctl, ctr, D, s, 0, None), 5 // s), 3 // s)
+
+
+def noise_volume(h, w, D, seed=7):
+    """Noise over a planted surface (a slanted plane with a step, disparities the width allows),
+    rounded to binary16 so that its fp16 and fp32 sources hold the same values."""
+    rng = np.random.default_rng(seed)
+    i, j = np.mgrid[0:h, 0:w]
+    top = min(D, w) * 0.45
+    truth = 2.0 + top * (0.3 + 0.5 * i / h) * np.where(j > w // 2, 1.0, 0.55)
+    d = np.arange(D)[None, None, :]
+    c = np.minimum(np.abs(d - truth[..., None]) * 9.0, 70.0) + rng.uniform(0.0, 24.0, (h, w, D))
+    return np.ascontiguousarray(c.astype(np.float16).astype(np.float32))
+
+
+# the volumes of tests/test_gpu_volume.py's aggregate cases: name -> (kind, h, w, D, scale)
+GPU_VOLUMES = {
+    "road_24x80_D32": ("road", 24, 80, 32, 1),
+    "noise_24x80_D32": ("noise", 24, 80, 32, 1),
+    "road_20x40_D128": ("road", 20, 40, 128, 1),
+    "noise_20x40_D128": ("noise", 20, 40, 128, 1),
+    "road_12x72_D256": ("road", 12, 72, 256, 1),
+    "noise_12x72_D256": ("noise", 12, 72, 256, 1),
+    "road_24x80_D32_s2": ("road", 24, 80, 32, 2),
+    "noise_80x240_D256": ("noise", 80, 240, 256, 1),  # the schedules' handles
+}
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_volume(name, f16=False):
+    """The (H, W, D) float32 volume of a GPU_VOLUMES entry; f16: rounded to binary16, what an fp16
+    source of it holds (the noise volumes are binary16-exact either way); read-only."""
+    kind, h, w, D, s = GPU_VOLUMES[name]
+    c = road_volume(h, w, D, s) if kind == "road" else noise_volume(h, w, D)
+    if f16:
+        c = np.ascontiguousarray(c.astype(np.float16).astype(np.float32))
+    c.setflags(write=False)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name, m=0, paths=8, f16=False):
+    """recipe() of a GPU_VOLUMES entry, computed once per session; read-only."""
+    out = recipe(gpu_volume(name, f16), m, GPU_VOLUMES[name][4], paths)
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+VARIANTS = ("dense", "padded", "batch", "offset")
+
+
+def source(C, layout, dtype, variant):
+    """A strided source holding C: (storage, element offset of (0, 0, 0), (stride_row, stride_col,
+    stride_disp)).  storage is a 1-D array of `dtype` filled with a canary (7.0) around the
+    volume; layout "hwd" | "dhw"; variant: dense, padded (row / plane pitch), batch (item 1 of a
+    [3, ...] batch), offset (the base one element into the allocation)."""
+    H, W, D = C.shape
+    off = 0
+    if layout == "hwd":
+        sc, sd = D + (3 if variant == "padded" else 0), 1
+        sr = sc * W + (5 if variant == "padded" else 0)
+        n = sr * H
+    else:
+        sc, sr = 1, W + (3 if variant == "padded" else 0)
+        sd = sr * H + (5 if variant == "padded" else 0)
+        n = sd * D
+    if variant == "batch":
+        off, n = n, 3 * n
+    if variant == "offset":
+        off, n = 1, n + 1
+    store = np.full(n, 7.0, dtype)
+    i, j, d = np.meshgrid(np.arange(H), np.arange(W), np.arange(D), indexing="ij")
+    store[off + i * sr + j * sc + d * sd] = C.astype(dtype)
+    return store, off, (sr, sc, sd)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
