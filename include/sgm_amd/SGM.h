@@ -38,6 +38,9 @@
  *   aggregate_device(vol, ...)   (not in the reference) a caller's DEVICE cost volume through the
  *                                path aggregation, the LR check and post_filter (sgm_aggregate_device);
  *                                import_volume_device(vol, view, dst) is its first launch alone
+ *   set_cost(kind), cost()       Solver.cpp:96-117 over cost.cpp:4-59: frames match on the SAD or
+ *                                SSD window cost instead of the census (sgm_set_cost);
+ *                                window_cost_device(kind, l, r, pitch, dst) is that volume alone
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -381,6 +384,26 @@ public:
     void import_volume_device(const sgm_volume &vol, int view, float *d_dst, void *stream = nullptr) {
         if (sgm_volume_import_device(handle_, &vol, view, d_dst, stream) != SGM_OK)
             fail("import_volume_device", sgm_last_error(handle_));
+    }
+
+    // The matching cost of every later frame (sgm_set_cost): SGM_COST_CENSUS
+    // (the default), or the reference's SAD / SSD window cost (Solver::build_dsi
+    // over cost.cpp:4-59: no blur, no cost filters; sky masks are then refused).
+    void set_cost(int kind) {
+        if (sgm_set_cost(handle_, kind) != SGM_OK) fail("set_cost", sgm_last_error(handle_));
+    }
+    int cost() const {
+        int kind = SGM_COST_CENSUS;
+        if (sgm_get_cost(handle_, &kind) != SGM_OK) fail("cost", sgm_last_error(handle_));
+        return kind;
+    }
+    // The SAD / SSD volume alone (sgm_window_cost_device): DEVICE grey images of
+    // the constructed size, `pitch` bytes per row, into the dense fp32 rows x
+    // cols x D volume d_dst, which aggregate_device takes.  Enqueue only.
+    void window_cost_device(int kind, const uint8_t *d_left, const uint8_t *d_right, int pitch, float *d_dst,
+                            void *stream = nullptr) {
+        if (sgm_window_cost_device(handle_, kind, d_left, d_right, pitch, d_dst, stream) != SGM_OK)
+            fail("window_cost_device", sgm_last_error(handle_));
     }
 
     // The pixel format of the images process() takes (sgm_set_input_format):

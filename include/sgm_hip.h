@@ -585,6 +585,68 @@ int sgm_volume_import_device(sgm_handle *h, const sgm_volume *vol, int view, flo
 int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int out_pitch,
                          uint16_t *d_raw, void *stream);
 
+/* ---- the matching cost of a frame: census, or a SAD / SSD window ----
+ *
+ * The reference's second way to build the disparity space image,
+ * Solver::build_dsi (Solver.cpp:96-117) over the window costs SAD and SSD
+ * (cost.cpp:4-59), on the GPU.  On the working grid (rows = h / scale, cols =
+ * w / scale), with L and R the frame's grey images after its input slot,
+ * decimated by scale as the census reads them and NOT blurred (build_dsi reads
+ * img_l and img_r; params.blur plays no part), win_h = 7 / scale and win_w =
+ * 9 / scale (integer division):
+ *   AD(y, x, d)   = |L[y][x] - R[y][max(x - (d + min_disp) / scale, 0)]|   (SSD: its square)
+ *   C_L[i][j][d]  = (sum over a = -win_h/2 .. win_h/2, b = -win_w/2 .. win_w/2 of
+ *                    AD(clamp(i + a, 0, rows - 1), clamp(j + b, 0, cols - 1), d)) / win_h / win_w
+ * The sum is an integer (at most 63 * 255^2); two correctly rounded fp32
+ * divisions follow, in that order.  At scale 2 the loops run over 3 x 5 taps and
+ * divide by 3 and 4, as the reference's do.  The largest cost is 65025.
+ * WEIGHTED_COST (0 in the reference, inc/Solver.h:15) and an ensemble with the
+ * census (no formula in the reference) are not built. */
+enum { SGM_COST_CENSUS = 0, SGM_COST_SAD = 1, SGM_COST_SSD = 2 };
+
+/* The cost every later frame of the handle matches on.  SGM_COST_CENSUS is
+ * every handle's default and runs exactly as before.  A property of the handle
+ * (like sgm_set_min_disp; sgm_params and SGM_HIP_VERSION are unchanged); it
+ * allocates nothing and waits for nothing; re-capture graphs afterwards.
+ * A frame on a SAD or SSD handle runs its input slot as before, then one launch
+ * writes C_L into the handle's left cost buffer; with views == 2 the right
+ * view's volume is derived from it by sgm_volume_import_device's rule,
+ *   C_R[i, j, d] = C_L[i, min(j + (d + min_disp) / scale, cols - 1), d];
+ * then comes what sgm_aggregate_device does after its import: the L3
+ * checkpoints from the final volume, the whole-volume 8-path (or 4-path) passes
+ * on every handle whatever its schedule, the LR check, post_filter, confidence
+ * and reprojection; and LKRefine with params.lk_refine (the frame has images).
+ * What such a frame leaves out: the 5 x 3 cost filters are NOT applied (the
+ * window sum is a box aggregation already, build_dsi pins nothing about them,
+ * and the library has no horizontal filter that runs on a finished volume);
+ * sky masks have no meaning in build_dsi, so a frame call with a non-NULL mask
+ * on such a handle returns SGM_ERR_INVALID_ARG.
+ * SGM_ERR_INVALID_ARG, with a message, for a kind that is none of the three,
+ * and for BM, aux_only, SGM_VIEW_RIGHT and sky_detect handles. */
+int sgm_set_cost(sgm_handle *h, int kind);
+int sgm_get_cost(const sgm_handle *h, int *kind);
+
+/* The producer alone: the dense fp32 rows x cols x D (HWD) left volume C_L of
+ * two grey images, into d_dst, DEVICE memory.  d_left and d_right are the
+ * images sgm_process_device takes on a handle with no input stage set: height x
+ * width bytes, `pitch` bytes per row, read decimated by scale; the handle's
+ * min_disp is the one used.  kind is SGM_COST_SAD or SGM_COST_SSD, whatever
+ * sgm_set_cost says.  One launch on `stream` (NULL = the handle's stream), no
+ * host wait, no allocation: capturable into a HIP graph.  Any handle of the
+ * working size serves, aux_only included.  The volume goes straight into
+ * sgm_aggregate_device (SGM_VOL_F32, strides cols * D, D, 1).  Timed under the
+ * profile class "window_cost".  SGM_ERR_INVALID_ARG, with a message, for a bad
+ * kind, a NULL or misaligned pointer, pitch < width, and hipStreamLegacy as the
+ * stream (see sgm_volume_import_device). */
+int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const uint8_t *d_right, int pitch,
+                           float *d_dst, void *stream);
+/* Its HOST-memory twin (tests): images in, rows * cols * D floats out; synchronous. */
+int sgm_stage_window_cost(sgm_handle *h, int kind, const uint8_t *left, const uint8_t *right, int pitch,
+                          float *cost);
+/* The columns one workgroup of the producer writes (tests and tools derive
+ * their edge-case widths from it). */
+int sgm_window_cost_tile_cols(void);
+
 /* Post-sync validity check of the frames enqueued so far (the reference has
  * no asynchronous work to check: SGM::process is synchronous, SGM.cpp:32-826).
  * Waits for the handle's last call's work (its stream, or the event the call

@@ -49,7 +49,11 @@ EXPORTS = (
     "sgm_set_reproject", "sgm_get_reproject", "sgm_reproject_device", "sgm_stage_reproject",
     "sgm_get_reprojected", "sgm_stage_reprojected", "sgm_camera_q",
     "sgm_volume_import_device", "sgm_aggregate_device",
+    "sgm_set_cost", "sgm_get_cost", "sgm_window_cost_device", "sgm_stage_window_cost",
+    "sgm_window_cost_tile_cols",
 )
+# sgm_set_cost's kinds (SGM_COST_*), by name
+COST_KINDS = {"census": 0, "sad": 1, "ssd": 2}
 # sgm_volume's element types (SGM_VOL_*)
 SGM_VOL_F32 = 0
 SGM_VOL_F16 = 1
@@ -214,6 +218,11 @@ def lib():
     VP = ctypes.POINTER(Volume)
     L.sgm_volume_import_device.argtypes = [P, VP, I, P, P]
     L.sgm_aggregate_device.argtypes = [P, VP, P, I, P, P]
+    L.sgm_set_cost.argtypes = [P, I]
+    L.sgm_get_cost.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_window_cost_device.argtypes = [P, I, P, P, I, P, P]
+    L.sgm_stage_window_cost.argtypes = [P, I, P, P, I, P]
+    L.sgm_window_cost_tile_cols.argtypes = []
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

@@ -10,6 +10,7 @@
 // the maps the setters switch on and off.
 #include "sgm_handle.h"
 #include "sgm_volume_args.h"
+#include "sgm_window_cost_args.h"
 
 #include <float.h>
 #include <stdlib.h>
@@ -599,6 +600,9 @@ int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_ri
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: bad pointer or pitch");
     if (h->p.aux_only)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: handle created with aux_only");
+    if (h->cost_kind != SGM_COST_CENSUS && (d_sky_l || d_sky_r))
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_process_device: sky masks have no meaning with a SAD or SSD cost (sgm_set_cost)");
     DeviceGuard guard(h->device);
     StreamScope scope(h, stream);
     return run_frame(h, {d_left, d_right, pitch, d_sky_l, d_sky_r, sky_pitch, d_out, out_pitch, d_raw_disp},
@@ -614,6 +618,9 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: bad pointer or pitch");
     if (h->p.aux_only)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: handle created with aux_only");
+    if (h->cost_kind != SGM_COST_CENSUS && (sky_l || sky_r))
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_process: sky masks have no meaning with a SAD or SSD cost (sgm_set_cost)");
     int rc;
     if ((rc = check_frame_err(h))) return rc;
     DeviceGuard guard(h->device);
@@ -711,6 +718,74 @@ int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int
     DeviceGuard guard(h->device);
     StreamScope scope(h, stream);
     return aggregate_volume(h, *vol, d_out, out_pitch, d_raw, scope.st);
+}
+
+int sgm_set_cost(sgm_handle *h, int kind) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (kind != SGM_COST_CENSUS && kind != SGM_COST_SAD && kind != SGM_COST_SSD)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_cost: kind must be SGM_COST_CENSUS, SGM_COST_SAD or SGM_COST_SSD, got %d", kind);
+    if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_cost: BM and aux_only handles run no SGM frames");
+    if (h->p.view == SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_cost: a SGM_VIEW_RIGHT handle (the window costs build the left view's volume)");
+    if (h->p.sky_detect)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_cost: a sky_detect handle (sky masks have no meaning in build_dsi)");
+    // (a host-side switch the next frame reads: every frame handle already holds the buffers of
+    // the whole-volume passes, and frames enqueued so far keep the launches they were given)
+    h->cost_kind = kind;
+    return SGM_OK;
+}
+
+int sgm_get_cost(const sgm_handle *h, int *kind) {
+    if (!h || !kind) return SGM_ERR_INVALID_ARG;
+    *kind = h->cost_kind;
+    return SGM_OK;
+}
+
+int sgm_window_cost_tile_cols(void) { return sgm::kWinCostTileCols; }
+
+int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const uint8_t *d_right, int pitch,
+                           float *d_dst, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (const char *why = sgm::window_cost_refusal(kind, d_left, d_right, pitch, h->p.width, d_dst))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_window_cost_device: %s", why);
+    // (as check_volume: an end event recorded on the legacy stream is one the next call waits on)
+    if (stream == (void *)hipStreamLegacy)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_window_cost_device: hipStreamLegacy is not accepted; pass a created stream, or NULL "
+                       "for the handle's own");
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    hipStream_t st = scope.st;
+    HIPCHK(h, timed(h, "window_cost", vol_elems(h->g), st, [&] {
+               return sgm::launch_window_cost(kind, d_left, d_right, pitch, d_dst, h->min_disp, h->g, st);
+           }));
+    return SGM_OK;
+}
+
+int sgm_stage_window_cost(sgm_handle *h, int kind, const uint8_t *left, const uint8_t *right, int pitch,
+                          float *cost) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (const char *why = sgm::window_cost_refusal(kind, left, right, pitch, h->p.width, cost))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_window_cost: %s", why);
+    DeviceGuard guard(h->device);
+    int rc;
+    const size_t nvol = (size_t)h->g.H * h->g.W * h->g.D;
+    {
+        StreamScope scope(h, nullptr);
+        if ((rc = copy_in_image(h, h->d_in[0], left, pitch))) return rc;
+        if ((rc = copy_in_image(h, h->d_in[1], right, pitch))) return rc;
+    }
+    // (an aux_only handle has no cost buffer: a temporary of the call's own)
+    StreamTemp<float> d_cost(h->st);
+    HIPCHK(h, hipMallocAsync((void **)&d_cost.p, nvol * sizeof(float), h->st));
+    if ((rc = sgm_window_cost_device(h, kind, h->d_in[0], h->d_in[1], h->p.width, d_cost.p, nullptr))) return rc;
+    HIPCHK(h, hipMemcpyAsync(cost, d_cost.p, nvol * sizeof(float), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return SGM_OK;
 }
 
 #ifdef SGM_SLANT_DEBUG

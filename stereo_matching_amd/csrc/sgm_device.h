@@ -207,13 +207,17 @@ __device__ __forceinline__ float readlane_f(float x, int lane) {
 // FMA residual step equals IEEE division bit-for-bit for EVERY non-negative
 // finite float (exhaustive GPU check, tools/verify_div.hip; negative x follows
 // by symmetry, and -0 cannot occur in the filters); 3 VALU ops instead of the
-// ~10-op div_scale/div_fmas/div_fixup sequence.
+// ~10-op div_scale/div_fmas/div_fixup sequence.  For WIN = 7 and 9 (the window
+// costs' divisors, sgm_window_cost.hip) the same form is proven over the inputs
+// a window sum can reach, not over every float (sgm_window_cost_args.h).
 template <int WIN>
 __device__ __forceinline__ float div_win(float x) {
     if constexpr (WIN == 1) {
         return x;
     } else if constexpr (WIN == 2) {
         return x * 0.5f;
+    } else if constexpr (WIN == 4) {
+        return x * 0.25f;
     } else {
         constexpr float r = 1.0f / WIN;
         const float q0 = x * r;

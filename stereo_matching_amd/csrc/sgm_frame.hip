@@ -7,6 +7,7 @@
 // queue): a frame runs on one stream, at 73.5 B of HBM traffic per
 // pixel-disparity in the per-view schedule (aggregate).
 #include "sgm_handle.h"
+#include "sgm_volume_args.h"
 
 #include <stdlib.h>
 
@@ -534,6 +535,63 @@ int input_slot(sgm_handle *h, FrameIO *f, hipStream_t st) {
     return SGM_OK;
 }
 
+// The frame from the cost volume on, given every view's final volume in its C
+// (aggregate_volume's import, or window_cost_stage): the maps' wiring is
+// frame_maps'; stage_aggregate's passes -- the L3 checkpoints from the final
+// volume, then the whole-volume aggregation, whatever schedule the handle's
+// frames run --, the LR check or the one-view copy, post_filter and LKRefine.
+int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
+    const Geom g = h->g;
+    const int nv = h->nviews;
+    const double elems = vol_elems(g);
+    // a dense one-view map straight from the final pass, the handle's sub-pixel layout for the
+    // LR check
+    const bool direct_out = nv == 1 && f.out_pitch == g.W;
+    ViewRoles r[2] = {};
+    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
+    if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    int rc = SGM_OK;
+    for (int v = 0; v < nv; ++v)
+        HIPCHK(h, timed(h, "pair_fwd_L3", elems, st,
+                        [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r[v].fin, g, st); }));
+    if (h->paths4) rc = aggregate4(h, nv, r, st);
+    else
+        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
+    if (rc != SGM_OK) return rc;
+    if (nv == 2) {
+        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
+                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
+                                                        h->p.lr_max_diff, h->gt, st)
+                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, f.out, f.out_pitch,
+                                                     h->p.lr_max_diff, h->gt, st);
+               }));
+    } else if (!direct_out) {
+        HIPCHK(h, hipMemcpy2DAsync(f.out, (size_t)f.out_pitch * sizeof(float), h->d_sub[0],
+                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
+                                   hipMemcpyDeviceToDevice, st));
+    }
+    return finish_frame(h, f, st);
+}
+
+// The cost stage of a frame on a SAD or SSD handle (sgm_set_cost, DESIGN.md
+// 5o): one launch writes the left view's window cost volume into its C; with
+// two views the import kernel's right-view role derives the right view's from
+// it (the handle's own left buffer as a dense fp32 HWD source).  No census, no
+// cost filters, no masks.
+int window_cost_stage(sgm_handle *h, const FrameIO &f, hipStream_t st) {
+    const Geom g = h->g;
+    HIPCHK(h, timed(h, "window_cost", vol_elems(g), st, [&] {
+               return sgm::launch_window_cost(h->cost_kind, f.left, f.right, f.pitch, cost_buf(h, 0),
+                                              h->min_disp, g, st);
+           }));
+    if (h->nviews == 2)
+        HIPCHK(h, timed(h, "vol_import", vol_elems(g), st, [&] {
+                   return sgm::launch_volume_import(cost_buf(h, 0), sgm::kVolF32, (long long)g.W * g.D, g.D, 1,
+                                                    nullptr, cost_buf(h, 1), h->min_disp, g, st);
+               }));
+    return SGM_OK;
+}
+
 // The frame up to its last map stage: the input slot, the solver, the LR check, post_filter and
 // LKRefine (run_frame, below, follows it with the output slot).
 int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
@@ -549,6 +607,10 @@ int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
     // volumes fit together (K64: joint launches) or neither fits (HD/4K:
     // bands, or the slanted schedule).
     if (h->p.solver == SGM_SOLVER_BM) return bm_frame(h, f, st);
+    if (h->cost_kind != SGM_COST_CENSUS) {  // a window cost instead of the census cost stage
+        if ((rc = window_cost_stage(h, f, st)) != SGM_OK) return rc;
+        return volume_frame(h, f, st);
+    }
     bool have_c = false;
     if ((rc = cost_stage(h, f, st, &have_c)) != SGM_OK) return rc;
     // one view with a dense output map: the final pass writes the sub-pixel
@@ -615,44 +677,15 @@ int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
 
 int sgm::aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,
                           hipStream_t st) {
-    const Geom g = h->g;
     const int nv = h->nviews;
-    const double elems = vol_elems(g);
     // one launch reads the caller's volume and writes every view's C
-    HIPCHK(h, timed(h, "vol_import", nv * elems, st, [&] {
+    HIPCHK(h, timed(h, "vol_import", nv * vol_elems(h->g), st, [&] {
                return sgm::launch_volume_import(vol.d_cost, vol.dtype, vol.stride_row, vol.stride_col,
                                                 vol.stride_disp, cost_buf(h, 0), nv == 2 ? cost_buf(h, 1) : nullptr,
-                                                h->min_disp, g, st);
+                                                h->min_disp, h->g, st);
            }));
-    // the maps' wiring is frame_maps': a dense one-view map straight from the final pass, the
-    // handle's sub-pixel layout for the LR check
-    const bool direct_out = nv == 1 && out_pitch == g.W;
-    ViewRoles r[2] = {};
-    r[0] = view_roles(h, 0, d_raw, direct_out ? d_out : h->d_sub[0], h->sub_cm);
-    if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
-    // stage_aggregate's passes: the L3 checkpoints from the final volume, then the whole-volume
-    // aggregation, whatever schedule the handle's frames run
-    int rc = SGM_OK;
-    for (int v = 0; v < nv; ++v)
-        HIPCHK(h, timed(h, "pair_fwd_L3", elems, st,
-                        [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r[v].fin, g, st); }));
-    if (h->paths4) rc = aggregate4(h, nv, r, st);
-    else
-        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
-    if (rc != SGM_OK) return rc;
-    if (nv == 2) {
-        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
-                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], d_out, out_pitch,
-                                                        h->p.lr_max_diff, h->gt, st)
-                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, d_out, out_pitch,
-                                                     h->p.lr_max_diff, h->gt, st);
-               }));
-    } else if (!direct_out) {
-        HIPCHK(h, hipMemcpy2DAsync(d_out, (size_t)out_pitch * sizeof(float), h->d_sub[0],
-                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
-                                   hipMemcpyDeviceToDevice, st));
-    }
-    if (h->p.post_filter && (rc = sgm::post_filter(h, d_out, out_pitch, st)) != SGM_OK) return rc;
+    // (no images: sgm_aggregate_device refuses handles with lk_refine)
+    if (int rc = volume_frame(h, {nullptr, nullptr, 0, nullptr, nullptr, 0, d_out, out_pitch, d_raw}, st)) return rc;
     if (h->rp_on && h->rp.outputs) return sgm::reproject_frame(h, d_out, out_pitch, st);
     return SGM_OK;
 }

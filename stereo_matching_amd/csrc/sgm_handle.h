@@ -57,6 +57,8 @@ struct sgm_handle {
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
+    int cost_kind;        // sgm_set_cost: SGM_COST_CENSUS (frames as ever), or the SAD / SSD window cost
+                          //   (frames: window_cost_stage + volume_frame, sgm_frame.hip)
     uint64_t *d_cts[2];   // the tables shifted by min_disp / scale columns (launch_ct_shift):
                           // [0] the left image's (the right view's DSI reads it), [1] the right
                           // image's (the left view's); min_disp = 0: d_ct[0], d_ct[1] themselves
@@ -338,6 +340,7 @@ int stage_aggregate(sgm_handle *h, hipStream_t st);
 // sgm_aggregate_device: the frame from the cost volume on: the caller's volume
 // imported into every view's C, stage_aggregate's whole-volume passes view after view (both at
 // once on a 4-path handle), then the LR check, post_filter and the output slot as run_frame's
+// (the tail a SAD / SSD frame shares: volume_frame, sgm_frame.hip)
 int aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,
                      hipStream_t st);
 bool slant_default(Geom g, int nviews);

@@ -344,6 +344,11 @@ hipError_t launch_reproject(const double *q, const float *disp, int pitch, float
 hipError_t launch_volume_import(const void *src, int dtype, long long stride_row, long long stride_col,
                                 long long stride_disp, float *dst_l, float *dst_r, int min_disp, Geom g,
                                 hipStream_t st);
+// The SAD (kind 1) or SSD (kind 2) window cost of two grey images (sgm_window_cost.hip, DESIGN.md
+// 5o) as the dense fp32 HWD left volume, one launch: left, right of g.H * g.scale rows and g.W *
+// g.scale columns, pitch bytes per row, read decimated by g.scale and not blurred.
+hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
+                              int min_disp, Geom g, hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

@@ -1,0 +1,132 @@
+// sgm_window_cost.hip -- the reference's SAD / SSD window costs as a cost
+// volume: Solver::build_dsi (Solver.cpp:96-117) over SAD and SSD
+// (cost.cpp:4-59), one launch.
+//
+//   AD(y, x, d)  = |L[y][x] - R[y][max(x - (d + min_disp) / scale, 0)]|   (SSD: its square)
+//   C[i][j][d]   = (sum over the (2 hh + 1) x (2 hw + 1) taps of
+//                   AD(clamp(i + a, 0, H - 1), clamp(j + b, 0, W - 1), d)) / win_h / win_w
+//
+// The output is the library's dense fp32 HWD volume.  A workgroup of 256 lanes
+// takes kWinCostBandRows rows, kWinCostTileCols columns and DC disparities (64;
+// 32 at D = 32): lane = disparity, so a store is a whole 256-byte line (128 at
+// D = 32, two columns per wave), and each group of DC lanes owns NC columns.
+// The band's rows of L and R are staged in LDS as bytes at clamped coordinates
+// (sgm_window_cost_args.h: R's span is the tile's columns plus the chunk's shift
+// range), so no tap tests an edge.  Each lane keeps its NC + 2 hw column sums
+// over the window's rows in registers while it walks down the band -- one AD
+// added, one dropped per column and row -- and slides the window sum along its
+// columns.  The sums are integers (at most 63 * 255^2: exact in any order);
+// two correctly rounded divisions follow (div_win: proven against IEEE
+// division over every reachable sum by tests/cpp/window_cost_args_main.cpp).
+#include "sgm_device.h"
+
+#include "sgm_window_cost_args.h"
+
+namespace sgm {
+namespace {
+
+struct WinArgs {
+    const uint8_t *left, *right;
+    size_t rpitch;  // bytes between working-grid rows
+    float *dst;
+    int H, W, D;
+    int min_disp;
+};
+
+template <int SCALE, int DC, bool SSD>
+__global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
+    constexpr int HH = win_cost_hh(SCALE), HW = win_cost_hw(SCALE);
+    constexpr int WH = win_cost_h(SCALE), WW = win_cost_w(SCALE);
+    constexpr int TJ = kWinCostTileCols, RB = kWinCostBandRows;
+    constexpr int NC = TJ / (256 / DC);  // columns per group of DC lanes
+    constexpr int NCA = NC + 2 * HW;     // column sums a group keeps
+    constexpr int LC = win_cost_l_cols(SCALE), RC = win_cost_r_cols(SCALE, DC), NR = win_cost_rows(SCALE);
+    __shared__ uint8_t sl[NR][LC];
+    __shared__ uint8_t sr[NR][RC];
+    const int ntj = (a.W + TJ - 1) / TJ;
+    const int i0 = (bid_x() / ntj) * RB, j0 = (bid_x() % ntj) * TJ, d0 = bid_y() * DC;
+    const int t = tid_x();
+    const int s_hi = (d0 + DC - 1 + a.min_disp) / SCALE;
+    for (int idx = t; idx < NR * LC; idx += 256) {
+        const int r = idx / LC, c = idx - r * LC;
+        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = clampi(j0 - HW + c, 0, a.W - 1);
+        sl[r][c] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
+    }
+    for (int idx = t; idx < NR * RC; idx += 256) {
+        const int r = idx / RC, c = idx - r * RC;
+        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = win_cost_r_col(j0, c, a.W, SCALE, s_hi);
+        sr[r][c] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
+    }
+    __syncthreads();
+    // tile column c0 + c is image column j0 - HW + c0 + c: output column k of the group sums
+    // its column sums k .. k + 2 HW
+    const int c0 = (t / DC) * NC, d = d0 + t % DC;
+    const int s = (d + a.min_disp) / SCALE;
+    int ru[NCA];
+#pragma unroll
+    for (int c = 0; c < NCA; ++c) ru[c] = win_cost_r_index(j0, c0 + c, a.W, SCALE, s_hi, s);
+    auto ad = [&](int r, int c) -> int {
+        const int v = (int)sl[r][c0 + c] - (int)sr[r][ru[c]];
+        return SSD ? v * v : (v < 0 ? -v : v);
+    };
+    int cs[NCA];
+#pragma unroll
+    for (int c = 0; c < NCA; ++c) {
+        cs[c] = 0;
+#pragma unroll
+        for (int r = 0; r <= 2 * HH; ++r) cs[c] += ad(r, c);
+    }
+    const int rows = a.H - i0 < RB ? a.H - i0 : RB;
+    for (int rr = 0; rr < rows; ++rr) {
+        int sum = 0;
+#pragma unroll
+        for (int c = 0; c <= 2 * HW; ++c) sum += cs[c];
+        float *o = a.dst + ((size_t)(i0 + rr) * a.W + j0 + c0) * a.D + d;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            if (j0 + c0 + k < a.W) o[(size_t)k * a.D] = div_win<WW>(div_win<WH>((float)sum));
+            if (k + 1 < NC) sum += cs[k + 2 * HW + 1] - cs[k];
+        }
+        // the window moves down a row: staged row rr + 2 HH + 1 enters, rr leaves
+        if (rr + 1 < rows) {
+#pragma unroll
+            for (int c = 0; c < NCA; ++c) cs[c] += ad(rr + 2 * HH + 1, c) - ad(rr, c);
+        }
+    }
+}
+
+template <int SCALE, int DC>
+hipError_t launch_t(bool ssd, const WinArgs &a, hipStream_t st) {
+    const long long ntj = (a.W + kWinCostTileCols - 1) / kWinCostTileCols;
+    const long long nb = (a.H + kWinCostBandRows - 1) / kWinCostBandRows;
+    if (ntj * nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(ntj * nb), (unsigned)(a.D / DC));
+    if (ssd)
+        hipLaunchKernelGGL((window_cost_kernel<SCALE, DC, true>), grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((window_cost_kernel<SCALE, DC, false>), grid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
+                              int min_disp, Geom g, hipStream_t st) {
+    if (!left || !right || !dst || (kind != kCostSad && kind != kCostSsd) || min_disp < 0 ||
+        (g.scale != 1 && g.scale != 2) || g.D % 32 != 0)
+        return hipErrorInvalidValue;
+    WinArgs a{};
+    a.left = left;
+    a.right = right;
+    a.rpitch = (size_t)pitch * g.scale;  // SGM.cpp:47-48's decimation, as the census reads
+    a.dst = dst;
+    a.H = g.H;
+    a.W = g.W;
+    a.D = g.D;
+    a.min_disp = min_disp;
+    const bool ssd = kind == kCostSsd;
+    if (g.scale == 1) return g.D == 32 ? launch_t<1, 32>(ssd, a, st) : launch_t<1, 64>(ssd, a, st);
+    return g.D == 32 ? launch_t<2, 32>(ssd, a, st) : launch_t<2, 64>(ssd, a, st);
+}
+
+}  // namespace sgm

@@ -70,8 +70,13 @@ class SGM:
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
                  input_size=None, rectify=None, input_format: str = "gray8", reproject=None,
-                 _solver: int = _capi.SGM_SOLVER_SGM):
+                 cost: str = "census", _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
+        # cost ("census" | "sad" | "ssd"): the matching cost of every frame
+        # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost
+        # (Solver::build_dsi over cost.cpp:4-59) with no cost filters after it
+        if cost not in _capi.COST_KINDS:
+            raise ValueError(f"cost must be one of {sorted(_capi.COST_KINDS)}, got {cost!r}")
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
         # S = ((L1+L2)+L3)+L4 per view, no diagonal paths (SGM.cpp:387-390)
         # (0 means 8, as in a zero-initialised sgm_params)
@@ -153,6 +158,8 @@ class SGM:
                 self.set_rectify(*rectify)
             if reproject is not None:
                 self.set_reproject(reproject)
+            if cost != "census":
+                self.set_cost(cost)
         except Exception:
             self.close()
             raise
@@ -607,6 +614,67 @@ class SGM:
         self._on_torch_stream(torch, cost, stream, lambda st: check(self._lib.sgm_volume_import_device(
             self._h, ctypes.byref(vol), int(view), ctypes.c_void_p(out.data_ptr()), st), self._h))
         return out
+
+    # ------------------------------------------------------ the matching cost
+    def set_cost(self, kind: str) -> None:
+        """sgm_set_cost: "census" (the default), "sad" or "ssd".  With a window
+        cost every later frame builds the reference's build_dsi volume (one
+        launch), derives the right view's from it and runs what aggregate()
+        runs; the cost filters are not applied and sky masks are refused.
+        Re-capture graphs afterwards."""
+        if kind not in _capi.COST_KINDS:
+            raise ValueError(f"cost must be one of {sorted(_capi.COST_KINDS)}, got {kind!r}")
+        check(self._lib.sgm_set_cost(self._h, _capi.COST_KINDS[kind]), self._h)
+
+    @property
+    def cost(self) -> str:
+        """sgm_get_cost, by name."""
+        k = ctypes.c_int()
+        check(self._lib.sgm_get_cost(self._h, ctypes.byref(k)), self._h)
+        return {v: n for n, v in _capi.COST_KINDS.items()}[k.value]
+
+    def window_cost(self, left, right, kind: str = "sad", out=None, stream=None):
+        """sgm_window_cost_device: the float32 (rows, cols, D) SAD or SSD cost
+        volume of two torch uint8 device images of shape (h, w) (unit column
+        stride; read decimated by the scale, not blurred), as a torch tensor on
+        the same device (`out`, allocated when None).  One launch on `stream`
+        (default: the device's current torch stream; the tensors' lifetime on
+        another stream is the caller's, as for aggregate).  The result goes
+        straight into aggregate()."""
+        if kind not in ("sad", "ssd"):
+            raise ValueError(f"kind must be 'sad' or 'ssd', got {kind!r}")
+        import torch
+        for name, img in (("left", left), ("right", right)):
+            if isinstance(img, np.ndarray) or not hasattr(img, "data_ptr"):
+                raise TypeError(f"{name} must be a torch device tensor; for host numpy images use "
+                                "stage_window_cost()")
+            if not img.is_cuda or img.device.index != self.device:
+                raise ValueError(f"{name} must live on the handle's device cuda:{self.device}, got {img.device}")
+            if img.dtype != torch.uint8 or tuple(img.shape) != (self.h, self.w) or img.stride(1) != 1:
+                raise ValueError(f"{name} must be a uint8 {(self.h, self.w)} tensor with unit column stride")
+        if left.stride(0) != right.stride(0):
+            raise ValueError("left and right must have the same row stride")
+        shape = (self.rows, self.cols, self.max_disp)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=left.device)
+        if (out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != left.device
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {left.device}")
+        self._on_torch_stream(torch, left, stream, lambda st: check(self._lib.sgm_window_cost_device(
+            self._h, _capi.COST_KINDS[kind], ctypes.c_void_p(left.data_ptr()), ctypes.c_void_p(right.data_ptr()),
+            left.stride(0), ctypes.c_void_p(out.data_ptr()), st), self._h))
+        return out
+
+    def stage_window_cost(self, left, right, kind: str = "sad") -> np.ndarray:
+        """sgm_stage_window_cost: the same volume from host numpy (h, w) uint8
+        images, as a numpy (rows, cols, D) float32 array (tests)."""
+        if kind not in ("sad", "ssd"):
+            raise ValueError(f"kind must be 'sad' or 'ssd', got {kind!r}")
+        l, r = _u8(left, (self.h, self.w), "left"), _u8(right, (self.h, self.w), "right")
+        cost = np.empty((self.rows, self.cols, self.max_disp), np.float32)
+        check(self._lib.sgm_stage_window_cost(self._h, _capi.COST_KINDS[kind], _ptr(l), _ptr(r), self.w,
+                                              _ptr(cost)), self._h)
+        return cost
 
     def check(self) -> None:
         """sgm_check: wait for the frames enqueued so far and raise SGMError
