@@ -41,6 +41,8 @@
  *   set_cost(kind), cost()       Solver.cpp:96-117 over cost.cpp:4-59: frames match on the SAD or
  *                                SSD window cost instead of the census (sgm_set_cost);
  *                                window_cost_device(kind, l, r, pitch, dst) is that volume alone
+ *   set_window(win_h, win_w)     inc/Solver.h:10-11  WIN_H, WIN_W as a setting of SGM and BM: the
+ *                                census's and the window costs' window (sgm_set_window)
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -396,6 +398,17 @@ public:
         int kind = SGM_COST_CENSUS;
         if (sgm_get_cost(handle_, &kind) != SGM_OK) fail("cost", sgm_last_error(handle_));
         return kind;
+    }
+    // The matching window of the census and of the SAD / SSD costs (sgm_set_window): the
+    // reference's WIN_H, WIN_W (inc/Solver.h:10-11: 7, 9) before the division by s.  Every later
+    // frame of an SGM or a BM, and window_cost_device, use it.  Accepted: 1 <= win_h / s,
+    // win_w / s <= 9, not 1 x 1 taps, not 9 x 9 (80 census bits); anything else fails and
+    // changes nothing.
+    void set_window(int win_h, int win_w) {
+        if (sgm_set_window(handle_, win_h, win_w) != SGM_OK) fail("set_window", sgm_last_error(handle_));
+    }
+    void get_window(int *win_h, int *win_w) const {
+        if (sgm_get_window(handle_, win_h, win_w) != SGM_OK) fail("get_window", sgm_last_error(handle_));
     }
     // The SAD / SSD volume alone (sgm_window_cost_device): DEVICE grey images of
     // the constructed size, `pitch` bytes per row, into the dense fp32 rows x

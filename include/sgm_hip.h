@@ -647,6 +647,40 @@ int sgm_stage_window_cost(sgm_handle *h, int kind, const uint8_t *left, const ui
  * their edge-case widths from it). */
 int sgm_window_cost_tile_cols(void);
 
+/* ---- the matching window: WIN_H, WIN_W of inc/Solver.h as a setting ----
+ *
+ * The reference writes WIN_H = 7, WIN_W = 9 as constants, but its cost functions
+ * take the window at run time: Solver::build_cost_table and build_dsi pass
+ * WIN_H / scale, WIN_W / scale (Solver.cpp:98-99, :127-128) to CT_pts, SAD and
+ * SSD (cost.cpp).  sgm_set_window(h, win_h, win_w) sets those two constants for
+ * one handle, BEFORE the division by scale; every handle starts at (7, 9).
+ * With e_h = win_h / scale, e_w = win_w / scale (integer division), HH = e_h /
+ * 2 and HW = e_w / 2, the loops run -HH .. HH and -HW .. HW (cost.cpp:8,14,107,
+ * 111), so an even e_w = 4 still has 5 taps, as the default has at scale 2.
+ *   census    CT_pts over (2 HH + 1) x (2 HW + 1) taps, the centre skipped, bits
+ *             MSB first in row-major order, coordinates clamped to the
+ *             working-grid edge, on the blurred image when params.blur = 1
+ *   SAD, SSD  the integer sum over the same taps, then / e_h and / e_w: two
+ *             correctly rounded fp32 divisions in that order (the divisors
+ *             are e_h and e_w, not the tap counts)
+ * Accepted: 1 <= e_h, e_w <= 9, not HH = HW = 0, and at most 64 census bits,
+ * which excludes only HH = HW = 4 (80 bits: the reference's own word would
+ * shift bits out).  Anything else returns SGM_ERR_INVALID_ARG with a message
+ * and changes nothing.  The largest sum stays 63 taps * 255^2.
+ * The window is read by every consumer of the census tables and of the window
+ * costs on the handle: SGM frames of every schedule, one and two views,
+ * SGM_SOLVER_BM, sgm_stage_census, frames after sgm_set_cost(SAD | SSD),
+ * sgm_window_cost_device and sgm_stage_window_cost; any handle takes it,
+ * aux_only included (it serves sgm_window_cost_device).  LKRefine's window, the
+ * 5 x 3 cost filters, the median and the speckle constants are not part of it.
+ * A property of the handle, like sgm_set_min_disp (sgm_params and
+ * SGM_HIP_VERSION are unchanged): it synchronises the handle's last work,
+ * allocates nothing, is to be called outside stream capture, and graphs are to
+ * be re-captured afterwards.  (7, 9) launches exactly what an untouched handle
+ * launches. */
+int sgm_set_window(sgm_handle *h, int win_h, int win_w);
+int sgm_get_window(const sgm_handle *h, int *win_h, int *win_w);
+
 /* Post-sync validity check of the frames enqueued so far (the reference has
  * no asynchronous work to check: SGM::process is synchronous, SGM.cpp:32-826).
  * Waits for the handle's last call's work (its stream, or the event the call

@@ -50,7 +50,7 @@ EXPORTS = (
     "sgm_get_reprojected", "sgm_stage_reprojected", "sgm_camera_q",
     "sgm_volume_import_device", "sgm_aggregate_device",
     "sgm_set_cost", "sgm_get_cost", "sgm_window_cost_device", "sgm_stage_window_cost",
-    "sgm_window_cost_tile_cols",
+    "sgm_window_cost_tile_cols", "sgm_set_window", "sgm_get_window",
 )
 # sgm_set_cost's kinds (SGM_COST_*), by name
 COST_KINDS = {"census": 0, "sad": 1, "ssd": 2}
@@ -223,6 +223,8 @@ def lib():
     L.sgm_window_cost_device.argtypes = [P, I, P, P, I, P, P]
     L.sgm_stage_window_cost.argtypes = [P, I, P, P, I, P]
     L.sgm_window_cost_tile_cols.argtypes = []
+    L.sgm_set_window.argtypes = [P, I, I]
+    L.sgm_get_window.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

@@ -220,6 +220,9 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
     h->g.W = p->width / p->scale;
     h->g.D = p->max_disp;
     h->gt = h->g;  // (min_disp = 0 until sgm_set_min_disp)
+    h->win_h = sgm::kWinH;  // (the reference's window until sgm_set_window)
+    h->win_w = sgm::kWinW;
+    h->win = sgm::default_window(h->g.scale);
     h->nviews = p->views;
     const size_t npx = (size_t)h->g.H * h->g.W;
     const size_t nvol = npx * h->g.D;
@@ -484,6 +487,29 @@ int sgm_set_min_disp(sgm_handle *h, int m) {
         h->gt.D = h->g.D + m;
         return SGM_OK;
     });
+}
+
+int sgm_set_window(sgm_handle *h, int win_h, int win_w) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (const char *why = sgm::window_refusal(win_h, win_w, h->g.scale))
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_window: %s, got (%d, %d) at scale %d", why, win_h, win_w,
+                       h->g.scale);
+    // (frames enqueued so far keep the launches they were given; the wait keeps the setter's
+    // contract that of sgm_set_min_disp.  Nothing is allocated: the tables are words whatever
+    // the window, and the window costs stage in LDS)
+    return change_setting(h, "sgm_set_window", win_h == h->win_h && win_w == h->win_w, [&]() -> int {
+        h->win_h = win_h;
+        h->win_w = win_w;
+        h->win = sgm::window_of(win_h, win_w, h->g.scale);
+        return SGM_OK;
+    });
+}
+
+int sgm_get_window(const sgm_handle *h, int *win_h, int *win_w) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (win_h) *win_h = h->win_h;
+    if (win_w) *win_w = h->win_w;
+    return SGM_OK;
 }
 
 int sgm_set_confidence(sgm_handle *h, int enable) {
@@ -761,7 +787,7 @@ int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const
     StreamScope scope(h, stream);
     hipStream_t st = scope.st;
     HIPCHK(h, timed(h, "window_cost", vol_elems(h->g), st, [&] {
-               return sgm::launch_window_cost(kind, d_left, d_right, pitch, d_dst, h->min_disp, h->g, st);
+               return sgm::launch_window_cost(kind, d_left, d_right, pitch, d_dst, h->min_disp, h->g, h->win, st);
            }));
     return SGM_OK;
 }
@@ -845,7 +871,7 @@ int sgm_stage_census(sgm_handle *h, const uint8_t *img, int pitch, uint64_t *ct)
     StreamScope scope(h, nullptr);
     int rc;
     if ((rc = copy_in_image(h, h->d_in[0], img, pitch))) return rc;
-    HIPCHK(h, sgm::launch_census(h->d_in[0], h->p.width, h->g, h->p.blur, h->d_ct[0], h->st));
+    HIPCHK(h, sgm::launch_census(h->d_in[0], h->p.width, h->g, h->win, h->p.blur, h->d_ct[0], h->st));
     HIPCHK(h, hipMemcpyAsync(ct, h->d_ct[0], (size_t)h->g.H * h->g.W * sizeof(uint64_t),
                              hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));

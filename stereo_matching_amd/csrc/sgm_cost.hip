@@ -22,6 +22,8 @@
 // the reference's association order.
 #include "sgm_device.h"
 
+#include "sgm_window_cost_args.h"
+
 #include <type_traits>
 
 namespace sgm {
@@ -151,10 +153,37 @@ __global__ __launch_bounds__(256) void census_kernel(const uint8_t *__restrict__
     }
 }
 
-hipError_t launch_census(const uint8_t *src, int pitch, Geom g, int blur, uint64_t *ct,
+// The census of a window other than the default (sgm_set_window):
+// census_kernel<HH, HWW> itself, instantiated for every accepted pair of half
+// sizes 0 .. 4 (not 0 x 0: no tap; not 4 x 4: 80 bits) and picked from a table.
+// The bit order, the hi / lo split and the clamping are the template's, so a
+// window of at most 32 bits fills lo only and 5 x 7's 34 bits put 2 in hi.
+using CensusFn = void (*)(const uint8_t *, const uint8_t *, int, int, int, int, int, uint64_t *, uint64_t *);
+template <int HH, int HWW>
+constexpr CensusFn census_fn() {
+    if constexpr ((HH == 0 && HWW == 0) || (2 * HH + 1) * (2 * HWW + 1) - 1 > 64)
+        return nullptr;
+    else
+        return census_kernel<HH, HWW>;
+}
+#define SGM_CENSUS_ROW(HH) \
+    { census_fn<HH, 0>(), census_fn<HH, 1>(), census_fn<HH, 2>(), census_fn<HH, 3>(), census_fn<HH, 4>() }
+static const CensusFn kCensusTable[5][5] = {SGM_CENSUS_ROW(0), SGM_CENSUS_ROW(1), SGM_CENSUS_ROW(2),
+                                            SGM_CENSUS_ROW(3), SGM_CENSUS_ROW(4)};
+#undef SGM_CENSUS_ROW
+
+hipError_t launch_census(const uint8_t *src, int pitch, Geom g, Window win, int blur, uint64_t *ct,
                          hipStream_t st, bool bm_rows, const uint8_t *src2, uint64_t *ct2) {
     dim3 grid((g.W + CT_TW - 1) / CT_TW, (g.H + CT_TH - 1) / CT_TH, src2 ? 2 : 1);
     const int rpitch = bm_rows ? pitch : pitch * g.scale;
+    const Window def = default_window(g.scale);
+    if (win.hh() != def.hh() || win.hw() != def.hw()) {
+        if (win.eh < 1 || win.ew < 1 || win.hh() > 4 || win.hw() > 4 || !kCensusTable[win.hh()][win.hw()])
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kCensusTable[win.hh()][win.hw()], grid, dim3(256), 0, st, src, src2, rpitch, g.scale,
+                           g.H, g.W, blur, ct, ct2);
+        return hipGetLastError();
+    }
     if (g.scale == 1)
         census_kernel<3, 4><<<grid, 256, 0, st>>>(src, src2, rpitch, 1, g.H, g.W, blur, ct, ct2);
     else

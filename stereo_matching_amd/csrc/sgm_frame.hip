@@ -298,7 +298,7 @@ int bm_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
         f.sky_pitch = g.W;
     }
     HIPCHK(h, timed(h, "census", 2 * npx, st, [&] {
-               return sgm::launch_census(f.left, f.pitch, g, h->p.blur, h->d_ct[0], st, true, f.right,
+               return sgm::launch_census(f.left, f.pitch, g, h->win, h->p.blur, h->d_ct[0], st, true, f.right,
                                          h->d_ct[1]);
            }));
     const CostSlot s = sgm::cost_slot(h, 0, 0, f.sky_l);
@@ -440,7 +440,7 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
         sky_pitch = g.W;
     }
     HIPCHK(h, timed(h, "census", 2 * npx, st, [&] {  // both images, one launch
-               return sgm::launch_census(f.left, f.pitch, g, h->p.blur, h->d_ct[0], st, false,
+               return sgm::launch_census(f.left, f.pitch, g, h->win, h->p.blur, h->d_ct[0], st, false,
                                          f.right, h->d_ct[1]);
            }));
     CostSlot s[2] = {};
@@ -582,7 +582,7 @@ int window_cost_stage(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     const Geom g = h->g;
     HIPCHK(h, timed(h, "window_cost", vol_elems(g), st, [&] {
                return sgm::launch_window_cost(h->cost_kind, f.left, f.right, f.pitch, cost_buf(h, 0),
-                                              h->min_disp, g, st);
+                                              h->min_disp, g, h->win, st);
            }));
     if (h->nviews == 2)
         HIPCHK(h, timed(h, "vol_import", vol_elems(g), st, [&] {

@@ -57,6 +57,8 @@ struct sgm_handle {
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
+    sgm::Window win;      // sgm_set_window over the scale: the census's and the window costs' window
+    int win_h, win_w;     //   as set (the reference's WIN_H, WIN_W: 7, 9)
     int cost_kind;        // sgm_set_cost: SGM_COST_CENSUS (frames as ever), or the SAD / SSD window cost
                           //   (frames: window_cost_stage + volume_frame, sgm_frame.hip)
     uint64_t *d_cts[2];   // the tables shifted by min_disp / scale columns (launch_ct_shift):

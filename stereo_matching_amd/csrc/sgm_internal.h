@@ -11,6 +11,7 @@
 #include "sgm_gray_args.h"
 #include "sgm_rectify_maps.h"
 #include "sgm_resize_args.h"
+#include "sgm_window_cost_args.h"
 
 namespace sgm {
 
@@ -211,8 +212,9 @@ hipError_t launch_slant_up(const SlantArgs &a, Geom g, hipStream_t st);
 hipError_t launch_slant_down(const SlantArgs &a, Geom g, hipStream_t st);
 
 // bm_rows: BM.cpp:24-25 decimation (rows not strided by the scale); src2/ct2:
-// a second image censused in the same launch
-hipError_t launch_census(const uint8_t *src, int pitch, Geom g, int blur, uint64_t *ct,
+// a second image censused in the same launch; win: the handle's matching window
+// (sgm_set_window; the default launches census_kernel<3, 4> / <1, 2> as ever)
+hipError_t launch_census(const uint8_t *src, int pitch, Geom g, Window win, int blur, uint64_t *ct,
                          hipStream_t st, bool bm_rows = false, const uint8_t *src2 = nullptr,
                          uint64_t *ct2 = nullptr);
 // BM's WTA (BM.cpp:53-85) over the filtered cost: raw disparity + its float copy
@@ -348,7 +350,7 @@ hipError_t launch_volume_import(const void *src, int dtype, long long stride_row
 // 5o) as the dense fp32 HWD left volume, one launch: left, right of g.H * g.scale rows and g.W *
 // g.scale columns, pitch bytes per row, read decimated by g.scale and not blurred.
 hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
-                              int min_disp, Geom g, hipStream_t st);
+                              int min_disp, Geom g, Window win, hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

@@ -18,6 +18,9 @@
 // columns.  The sums are integers (at most 63 * 255^2: exact in any order);
 // two correctly rounded divisions follow (div_win: proven against IEEE
 // division over every reachable sum by tests/cpp/window_cost_args_main.cpp).
+// The window is the handle's (sgm_set_window): the default 7 x 9
+// with every constant at compile time, any other through the instantiation of
+// its half width (window_cost_kernel's comment).
 #include "sgm_device.h"
 
 #include "sgm_window_cost_args.h"
@@ -31,18 +34,39 @@ struct WinArgs {
     float *dst;
     int H, W, D;
     int min_disp;
+    // a window other than the default (sgm_set_window): read only by the
+    // instantiations that leave these to run time
+    int scale, hh;
+    float fh, rh, fw, rw;  // e_h, RN(1 / e_h), e_w, RN(1 / e_w)
 };
 
-template <int SCALE, int DC, bool SSD>
+// x / f with r = RN(1 / f): div_win's form (sgm_device.h) with the divisor at run time.
+// sgm_window_cost_args.h's win_div is its host mirror, proven for every divisor 1 .. 9.
+__device__ __forceinline__ float div_rt(float x, float f, float r) {
+    const float q0 = x * r;
+    const float e = __builtin_fmaf(-q0, f, x);
+    return __builtin_fmaf(e, r, q0);
+}
+
+// HW, the window's half width, sizes the register arrays and is always a template
+// argument.  SCALE_T, HH_T, WH_T, WW_T are the default window's constants (the
+// code of before sgm_set_window); 0, -1, 0, 0 leave the scale, the half height
+// and the two divisors to WinArgs, so that one instantiation per half width
+// serves every other accepted window (the staged rows are then sized for the
+// largest half height and for scale 1, and indexed by the run-time strides).
+template <int HW, int DC, bool SSD, int SCALE_T, int HH_T, int WH_T, int WW_T>
 __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
-    constexpr int HH = win_cost_hh(SCALE), HW = win_cost_hw(SCALE);
-    constexpr int WH = win_cost_h(SCALE), WW = win_cost_w(SCALE);
+    constexpr bool FIXED = SCALE_T != 0;
+    static_assert(FIXED == (HH_T >= 0) && FIXED == (WH_T != 0) && FIXED == (WW_T != 0), "all or none");
+    const int SCALE = FIXED ? SCALE_T : a.scale, HH = FIXED ? HH_T : a.hh;
     constexpr int TJ = kWinCostTileCols, RB = kWinCostBandRows;
     constexpr int NC = TJ / (256 / DC);  // columns per group of DC lanes
     constexpr int NCA = NC + 2 * HW;     // column sums a group keeps
-    constexpr int LC = win_cost_l_cols(SCALE), RC = win_cost_r_cols(SCALE, DC), NR = win_cost_rows(SCALE);
-    __shared__ uint8_t sl[NR][LC];
-    __shared__ uint8_t sr[NR][RC];
+    constexpr int LC = win_l_cols(HW);
+    constexpr int RC_MAX = win_r_cols(HW, FIXED ? SCALE_T : 1, DC), NR_MAX = win_rows(FIXED ? HH_T : kWinMax / 2);
+    const int RC = win_r_cols(HW, SCALE, DC), NR = win_rows(HH);
+    __shared__ uint8_t sl[NR_MAX * LC];
+    __shared__ uint8_t sr[NR_MAX * RC_MAX];
     const int ntj = (a.W + TJ - 1) / TJ;
     const int i0 = (bid_x() / ntj) * RB, j0 = (bid_x() % ntj) * TJ, d0 = bid_y() * DC;
     const int t = tid_x();
@@ -50,12 +74,12 @@ __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
     for (int idx = t; idx < NR * LC; idx += 256) {
         const int r = idx / LC, c = idx - r * LC;
         const int y = clampi(i0 - HH + r, 0, a.H - 1), x = clampi(j0 - HW + c, 0, a.W - 1);
-        sl[r][c] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
+        sl[idx] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
     }
     for (int idx = t; idx < NR * RC; idx += 256) {
         const int r = idx / RC, c = idx - r * RC;
-        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = win_cost_r_col(j0, c, a.W, SCALE, s_hi);
-        sr[r][c] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
+        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = win_r_col(j0, c, a.W, HW, s_hi);
+        sr[idx] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
     }
     __syncthreads();
     // tile column c0 + c is image column j0 - HW + c0 + c: output column k of the group sums
@@ -64,9 +88,9 @@ __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
     const int s = (d + a.min_disp) / SCALE;
     int ru[NCA];
 #pragma unroll
-    for (int c = 0; c < NCA; ++c) ru[c] = win_cost_r_index(j0, c0 + c, a.W, SCALE, s_hi, s);
+    for (int c = 0; c < NCA; ++c) ru[c] = win_r_index(j0, c0 + c, a.W, HW, s_hi, s);
     auto ad = [&](int r, int c) -> int {
-        const int v = (int)sl[r][c0 + c] - (int)sr[r][ru[c]];
+        const int v = (int)sl[r * LC + c0 + c] - (int)sr[r * RC + ru[c]];
         return SSD ? v * v : (v < 0 ? -v : v);
     };
     int cs[NCA];
@@ -84,7 +108,12 @@ __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
         float *o = a.dst + ((size_t)(i0 + rr) * a.W + j0 + c0) * a.D + d;
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
-            if (j0 + c0 + k < a.W) o[(size_t)k * a.D] = div_win<WW>(div_win<WH>((float)sum));
+            if (j0 + c0 + k < a.W) {
+                if constexpr (FIXED)
+                    o[(size_t)k * a.D] = div_win<WW_T>(div_win<WH_T>((float)sum));
+                else
+                    o[(size_t)k * a.D] = div_rt(div_rt((float)sum, a.fh, a.rh), a.fw, a.rw);
+            }
             if (k + 1 < NC) sum += cs[k + 2 * HW + 1] - cs[k];
         }
         // the window moves down a row: staged row rr + 2 HH + 1 enters, rr leaves
@@ -95,25 +124,46 @@ __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
     }
 }
 
-template <int SCALE, int DC>
+template <int HW, int DC, int SCALE_T, int HH_T, int WH_T, int WW_T>
 hipError_t launch_t(bool ssd, const WinArgs &a, hipStream_t st) {
     const long long ntj = (a.W + kWinCostTileCols - 1) / kWinCostTileCols;
     const long long nb = (a.H + kWinCostBandRows - 1) / kWinCostBandRows;
     if (ntj * nb > 0x7fffffffLL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(ntj * nb), (unsigned)(a.D / DC));
     if (ssd)
-        hipLaunchKernelGGL((window_cost_kernel<SCALE, DC, true>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((window_cost_kernel<HW, DC, true, SCALE_T, HH_T, WH_T, WW_T>), grid, dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((window_cost_kernel<SCALE, DC, false>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((window_cost_kernel<HW, DC, false, SCALE_T, HH_T, WH_T, WW_T>), grid, dim3(256), 0, st, a);
     return hipGetLastError();
+}
+
+// the default window at SCALE: every constant at compile time
+template <int SCALE, int DC>
+hipError_t launch_default(bool ssd, const WinArgs &a, hipStream_t st) {
+    constexpr Window w = default_window(SCALE);
+    return launch_t<w.hw(), DC, SCALE, w.hh(), w.eh, w.ew>(ssd, a, st);
+}
+
+// any other accepted window: one instantiation per half width
+template <int DC>
+hipError_t launch_window(int hw, bool ssd, const WinArgs &a, hipStream_t st) {
+    switch (hw) {
+    case 0: return launch_t<0, DC, 0, -1, 0, 0>(ssd, a, st);
+    case 1: return launch_t<1, DC, 0, -1, 0, 0>(ssd, a, st);
+    case 2: return launch_t<2, DC, 0, -1, 0, 0>(ssd, a, st);
+    case 3: return launch_t<3, DC, 0, -1, 0, 0>(ssd, a, st);
+    case 4: return launch_t<4, DC, 0, -1, 0, 0>(ssd, a, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
 hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
-                              int min_disp, Geom g, hipStream_t st) {
+                              int min_disp, Geom g, Window win, hipStream_t st) {
     if (!left || !right || !dst || (kind != kCostSad && kind != kCostSsd) || min_disp < 0 ||
-        (g.scale != 1 && g.scale != 2) || g.D % 32 != 0)
+        (g.scale != 1 && g.scale != 2) || g.D % 32 != 0 || win.eh < 1 || win.eh > kWinMax || win.ew < 1 ||
+        win.ew > kWinMax || win.bits() > 64)
         return hipErrorInvalidValue;
     WinArgs a{};
     a.left = left;
@@ -124,9 +174,18 @@ hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *righ
     a.W = g.W;
     a.D = g.D;
     a.min_disp = min_disp;
+    a.scale = g.scale;
+    a.hh = win.hh();
+    a.fh = (float)win.eh;
+    a.rh = 1.0f / a.fh;
+    a.fw = (float)win.ew;
+    a.rw = 1.0f / a.fw;
     const bool ssd = kind == kCostSsd;
-    if (g.scale == 1) return g.D == 32 ? launch_t<1, 32>(ssd, a, st) : launch_t<1, 64>(ssd, a, st);
-    return g.D == 32 ? launch_t<2, 32>(ssd, a, st) : launch_t<2, 64>(ssd, a, st);
+    const Window def = default_window(g.scale);
+    if (win.eh != def.eh || win.ew != def.ew)
+        return g.D == 32 ? launch_window<32>(win.hw(), ssd, a, st) : launch_window<64>(win.hw(), ssd, a, st);
+    if (g.scale == 1) return g.D == 32 ? launch_default<1, 32>(ssd, a, st) : launch_default<1, 64>(ssd, a, st);
+    return g.D == 32 ? launch_default<2, 32>(ssd, a, st) : launch_default<2, 64>(ssd, a, st);
 }
 
 }  // namespace sgm

@@ -16,21 +16,51 @@ namespace sgm {
 // The cost kinds of include/sgm_hip.h (SGM_COST_*), by value.
 constexpr int kCostCensus = 0, kCostSad = 1, kCostSsd = 2;
 
-// Solver::build_dsi's window (Solver.cpp:98-99): WIN_H / scale x WIN_W / scale.
+// The matching window: sgm_set_window's (win_h, win_w) are the
+// reference's WIN_H, WIN_W; Solver::build_dsi and build_cost_table divide them by
+// the scale (Solver.cpp:98-99, :127-128), and CT_pts, SAD and SSD loop over
+// -e / 2 .. e / 2 on either side (cost.cpp:8,14,107,111): an even e_w = 4 still
+// has 5 taps, and SAD / SSD divide by e_h and e_w, not by the tap counts.
+struct Window {
+    int eh, ew;  // win_h / scale, win_w / scale
+    constexpr int hh() const { return eh / 2; }  // taps above and below
+    constexpr int hw() const { return ew / 2; }  // taps left and right
+    constexpr int bits() const { return (2 * hh() + 1) * (2 * hw() + 1) - 1; }  // census bits
+};
+constexpr int kWinH = 7, kWinW = 9;  // inc/Solver.h
+constexpr int kWinMax = 9;           // the largest e_h, e_w served (half sizes <= 4)
+constexpr Window window_of(int win_h, int win_w, int scale) { return Window{win_h / scale, win_w / scale}; }
+constexpr Window default_window(int scale) { return window_of(kWinH, kWinW, scale); }
+
+// Why sgm_set_window refuses (win_h, win_w) at this scale, or null.  The census
+// word holds 64 bits: 9 x 9 taps (80 bits) would shift bits out in the
+// reference's own word, so it is refused, not served wrong.
+constexpr const char *window_refusal(int win_h, int win_w, int scale) {
+    if (scale != 1 && scale != 2) return "scale must be 1 or 2";
+    const Window w = window_of(win_h, win_w, scale);
+    if (w.eh < 1 || w.eh > kWinMax || w.ew < 1 || w.ew > kWinMax)
+        return "win_h / scale and win_w / scale must lie in 1..9";
+    if (w.hh() == 0 && w.hw() == 0) return "the window has no tap beside its centre";
+    if (w.bits() > 64) return "the census word holds 64 bits (a 9 x 9 window has 80)";
+    return nullptr;
+}
+
+// Solver::build_dsi's default window (Solver.cpp:98-99): WIN_H / scale x WIN_W / scale.
 // SAD and SSD (cost.cpp:8,14) loop over -win/2 .. win/2 on either side, so at
 // scale 2 (3 x 4) they sum 3 x 5 taps and divide by 3 and 4.
-constexpr int win_cost_h(int scale) { return 7 / scale; }
-constexpr int win_cost_w(int scale) { return 9 / scale; }
-constexpr int win_cost_hh(int scale) { return win_cost_h(scale) / 2; }  // taps above and below
-constexpr int win_cost_hw(int scale) { return win_cost_w(scale) / 2; }  // taps left and right
+constexpr int win_cost_h(int scale) { return default_window(scale).eh; }
+constexpr int win_cost_w(int scale) { return default_window(scale).ew; }
+constexpr int win_cost_hh(int scale) { return default_window(scale).hh(); }
+constexpr int win_cost_hw(int scale) { return default_window(scale).hw(); }
 
 // The largest window sum: 63 taps of 255 (SAD) or 255^2 (SSD); exact in int32 and in fp32.
 constexpr int kWinCostMaxSum = 63 * 255 * 255;
 
-// x / win, correctly rounded, for win = 3, 7, 9 (div_win<WIN>, sgm_device.h: the
-// rounded reciprocal's product corrected by one FMA residual step) and win = 4
-// (exact).  tests/cpp/window_cost_args_main.cpp compares it with IEEE division
-// on every input a window sum can reach.
+// x / win, correctly rounded, for win = 1 .. 9 (div_win<WIN>, sgm_device.h: the
+// rounded reciprocal's product corrected by one FMA residual step; with win a
+// power of two the reciprocal and the product are exact and the residual is 0).
+// tests/cpp/window_cost_args_main.cpp and window_args_main.cpp compare it with
+// IEEE division on every input a window sum can reach.
 inline float win_div(float x, int win) {
     if (win == 4) return x * 0.25f;
     const float r = 1.0f / (float)win;
@@ -40,33 +70,48 @@ inline float win_div(float x, int win) {
 }
 
 // cost.cpp:29,58: cost / win_h / win_w, two divisions in that order.
-inline float win_cost_value(int sum, int scale) {
-    return win_div(win_div((float)sum, win_cost_h(scale)), win_cost_w(scale));
-}
+inline float win_cost_value(int sum, Window w) { return win_div(win_div((float)sum, w.eh), w.ew); }
+inline float win_cost_value(int sum, int scale) { return win_cost_value(sum, default_window(scale)); }
 
 // The kernel's tile: a workgroup writes kWinCostTileCols columns of
 // kWinCostBandRows rows for a chunk of DC disparities (64; 32 at D = 32).
 constexpr int kWinCostTileCols = 64;
 constexpr int kWinCostBandRows = 16;
 
-// Staged columns.  The left rows hold L[clamp(j0 - hw + t, 0, W - 1)] at t, the
-// right rows R[clamp(j0 - hw - s_hi + u, 0, W - 1)] at u, where s_lo .. s_hi
-// are the chunk's column shifts (d + min_disp) / scale.  A tap at tile column t
-// under shift s reads u = min(j0 - hw + t, W - 1) - (j0 - hw) + (s_hi - s):
-// the right edge's clamp comes before the shift (cost.cpp:17-18), the left
-// edge's after it, where the staged clamp gives the same column.
-constexpr int win_cost_l_cols(int scale) { return kWinCostTileCols + 2 * win_cost_hw(scale); }
-constexpr int win_cost_r_cols(int scale, int DC) { return win_cost_l_cols(scale) + DC / scale; }
-constexpr int win_cost_rows(int scale) { return kWinCostBandRows + 2 * win_cost_hh(scale); }
-constexpr int win_cost_r_index(int j0, int t, int W, int scale, int s_hi, int s) {
-    const int hw = win_cost_hw(scale);
+// Staged columns, with hw the window's half width.  The left rows hold
+// L[clamp(j0 - hw + t, 0, W - 1)] at t, the right rows
+// R[clamp(j0 - hw - s_hi + u, 0, W - 1)] at u, where s_lo .. s_hi are the chunk's
+// column shifts (d + min_disp) / scale.  A tap at tile column t under shift s
+// reads u = min(j0 - hw + t, W - 1) - (j0 - hw) + (s_hi - s): the right edge's
+// clamp comes before the shift (cost.cpp:17-18), the left edge's after it,
+// where the staged clamp gives the same column.
+constexpr int win_l_cols(int hw) { return kWinCostTileCols + 2 * hw; }
+constexpr int win_r_cols(int hw, int scale, int DC) { return win_l_cols(hw) + DC / scale; }
+constexpr int win_rows(int hh) { return kWinCostBandRows + 2 * hh; }
+constexpr int win_r_index(int j0, int t, int W, int hw, int s_hi, int s) {
     const int x = j0 - hw + t;
     return (x < W - 1 ? x : W - 1) - (j0 - hw) + (s_hi - s);
 }
 // the image column that index stands for
-constexpr int win_cost_r_col(int j0, int u, int W, int scale, int s_hi) {
-    const int c = j0 - win_cost_hw(scale) - s_hi + u;
+constexpr int win_r_col(int j0, int u, int W, int hw, int s_hi) {
+    const int c = j0 - hw - s_hi + u;
     return c < 0 ? 0 : c > W - 1 ? W - 1 : c;
+}
+// LDS bytes of a workgroup's staged rows.  The largest over the accepted windows, at scale 1
+// and DC = 64, is 9 x 7's 24 rows of 70 + 134 bytes = 4896 (the default 7 x 9: 22 x (72 + 136)
+// = 4576), of the 64 KiB a workgroup may take.
+constexpr int win_lds_bytes(Window w, int scale, int DC) {
+    return win_rows(w.hh()) * (win_l_cols(w.hw()) + win_r_cols(w.hw(), scale, DC));
+}
+// the default window's, by scale
+constexpr int win_cost_l_cols(int scale) { return win_l_cols(win_cost_hw(scale)); }
+constexpr int win_cost_r_cols(int scale, int DC) { return win_r_cols(win_cost_hw(scale), scale, DC); }
+constexpr int win_cost_rows(int scale) { return win_rows(win_cost_hh(scale)); }
+constexpr int win_cost_r_index(int j0, int t, int W, int scale, int s_hi, int s) {
+    return win_r_index(j0, t, W, win_cost_hw(scale), s_hi, s);
+}
+constexpr int win_cost_r_col(int j0, int u, int W, int scale, int s_hi) {
+    return win_r_col(j0, u, W, win_cost_hw(scale), s_hi);
 }
 
 // The checks sgm_window_cost_device makes before it enqueues anything: the

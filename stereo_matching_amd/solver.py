@@ -70,7 +70,7 @@ class SGM:
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
                  input_size=None, rectify=None, input_format: str = "gray8", reproject=None,
-                 cost: str = "census", _solver: int = _capi.SGM_SOLVER_SGM):
+                 cost: str = "census", window=None, _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # cost ("census" | "sad" | "ssd"): the matching cost of every frame
         # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost
@@ -160,6 +160,10 @@ class SGM:
                 self.set_reproject(reproject)
             if cost != "census":
                 self.set_cost(cost)
+            # window = (win_h, win_w): the census's and the SAD / SSD costs' window, the
+            # reference's WIN_H, WIN_W before the division by s (set_window); None: (7, 9)
+            if window is not None:
+                self.set_window(*window)
         except Exception:
             self.close()
             raise
@@ -633,6 +637,22 @@ class SGM:
         check(self._lib.sgm_get_cost(self._h, ctypes.byref(k)), self._h)
         return {v: n for n, v in _capi.COST_KINDS.items()}[k.value]
 
+    def set_window(self, win_h: int, win_w: int) -> None:
+        """sgm_set_window: the matching window of the census and of the SAD /
+        SSD costs, the reference's WIN_H, WIN_W (7, 9) before the division by
+        the scale.  Frames, stage_census() and window_cost() of this handle use
+        it from the next call on.  Accepted: 1 <= win_h // s, win_w // s <= 9, not
+        1 x 1 taps and not 9 x 9 (80 census bits); anything else raises SGMError and
+        changes nothing.  Waits for the handle's work; re-capture graphs afterwards."""
+        check(self._lib.sgm_set_window(self._h, int(win_h), int(win_w)), self._h)
+
+    @property
+    def window(self):
+        """sgm_get_window: (win_h, win_w) as set."""
+        wh, ww = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.sgm_get_window(self._h, ctypes.byref(wh), ctypes.byref(ww)), self._h)
+        return wh.value, ww.value
+
     def window_cost(self, left, right, kind: str = "sad", out=None, stream=None):
         """sgm_window_cost_device: the float32 (rows, cols, D) SAD or SSD cost
         volume of two torch uint8 device images of shape (h, w) (unit column
@@ -911,12 +931,12 @@ class BM(SGM):
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
                  post_filter_launches: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8", reproject=None):
+                 input_format: str = "gray8", reproject=None, window=None):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
                          post_filter_launches=post_filter_launches, input_size=input_size,
                          rectify=rectify, input_format=input_format, reproject=reproject,
-                         _solver=_capi.SGM_SOLVER_BM)
+                         window=window, _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -930,11 +950,11 @@ class GPU_SGM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8", reproject=None):
+                 input_format: str = "gray8", reproject=None, window=None):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
                          post_filter_launches=post_filter_launches, min_disp=min_disp,
                          input_size=input_size, rectify=rectify, input_format=input_format,
-                         reproject=reproject)
+                         reproject=reproject, window=window)
 
 
 # sgm_camera_q without a handle: the pinhole Q of a camera, 4 x 4 float64
