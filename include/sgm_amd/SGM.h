@@ -41,6 +41,9 @@
  *   set_cost(kind), cost()       Solver.cpp:96-117 over cost.cpp:4-59: frames match on the SAD or
  *                                SSD window cost instead of the census (sgm_set_cost);
  *                                window_cost_device(kind, l, r, pitch, dst) is that volume alone
+ *   set_volume_filter(bits)      Solver.cpp:296-368 on each view's volume of every volume frame
+ *                                (sgm_set_volume_filter); filter_volume_device(d_cost, bits) is
+ *                                the two filters alone, in place
  *   set_window(win_h, win_w)     inc/Solver.h:10-11  WIN_H, WIN_W as a setting of SGM and BM: the
  *                                census's and the window costs' window (sgm_set_window)
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
@@ -386,6 +389,24 @@ public:
     void import_volume_device(const sgm_volume &vol, int view, float *d_dst, void *stream = nullptr) {
         if (sgm_volume_import_device(handle_, &vol, view, d_dst, stream) != SGM_OK)
             fail("import_volume_device", sgm_last_error(handle_));
+    }
+
+    // The reference's two cost filters (Solver.cpp:296-368) on a finished volume.
+    // set_volume_filter(bits): SGM_FILTER_H | SGM_FILTER_V on each view's volume in every later
+    // volume frame (aggregate_device, frames after set_cost(SAD | SSD)); 0, the default: none.
+    void set_volume_filter(int filters) {
+        if (sgm_set_volume_filter(handle_, filters) != SGM_OK) fail("set_volume_filter", sgm_last_error(handle_));
+    }
+    int volume_filter() const {
+        int filters = 0;
+        if (sgm_get_volume_filter(handle_, &filters) != SGM_OK) fail("volume_filter", sgm_last_error(handle_));
+        return filters;
+    }
+    // The filters `filters` names, in place on a dense fp32 rows x cols x D DEVICE volume
+    // (sgm_filter_volume_device).  Enqueue only.
+    void filter_volume_device(float *d_cost, int filters = SGM_FILTER_H | SGM_FILTER_V, void *stream = nullptr) {
+        if (sgm_filter_volume_device(handle_, d_cost, filters, stream) != SGM_OK)
+            fail("filter_volume_device", sgm_last_error(handle_));
     }
 
     // The matching cost of every later frame (sgm_set_cost): SGM_COST_CENSUS

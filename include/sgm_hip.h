@@ -568,8 +568,11 @@ int sgm_volume_import_device(sgm_handle *h, const sgm_volume *vol, int view, flo
  * post_filter with params.post_filter (adaptive, or with a launch budget), the
  * reprojection launch with sgm_set_reproject, the confidence maps with
  * sgm_set_confidence.  Maps leave in true disparity (+ min_disp); d_raw is the
- * left raw WTA map or NULL.  The cost filters, the sky override and the census
- * are the caller's business: masks, sky_detect and blur play no part.
+ * left raw WTA map or NULL.  The sky override and the census are the caller's
+ * business: masks, sky_detect and blur play no part.  The reference's two cost
+ * filters run on each view's volume after the import when the handle is set to
+ * (sgm_set_volume_filter, below; off by default: the volume is then aggregated
+ * as it comes).
  * Works on handles of every schedule (the aggregation itself always takes the
  * whole-volume passes, whose buffers every frame handle holds: no call
  * allocates).  It waits for nothing on the host given a fill budget or no post
@@ -616,10 +619,11 @@ enum { SGM_COST_CENSUS = 0, SGM_COST_SAD = 1, SGM_COST_SSD = 2 };
  * checkpoints from the final volume, the whole-volume 8-path (or 4-path) passes
  * on every handle whatever its schedule, the LR check, post_filter, confidence
  * and reprojection; and LKRefine with params.lk_refine (the frame has images).
- * What such a frame leaves out: the 5 x 3 cost filters are NOT applied (the
- * window sum is a box aggregation already, build_dsi pins nothing about them,
- * and the library has no horizontal filter that runs on a finished volume);
- * sky masks have no meaning in build_dsi, so a frame call with a non-NULL mask
+ * The 5 x 3 cost filters are not applied by default (the window sum is a box
+ * aggregation already); with sgm_set_volume_filter (below) they run on each
+ * view's volume after the right view's derivation, which makes the frame
+ * SGM::process with build_dsi() in the place of the census DSI (SGM.cpp:66-72).
+ * Sky masks have no meaning in build_dsi, so a frame call with a non-NULL mask
  * on such a handle returns SGM_ERR_INVALID_ARG.
  * SGM_ERR_INVALID_ARG, with a message, for a kind that is none of the three,
  * and for BM, aux_only, SGM_VIEW_RIGHT and sky_detect handles. */
@@ -646,6 +650,71 @@ int sgm_stage_window_cost(sgm_handle *h, int kind, const uint8_t *left, const ui
 /* The columns one workgroup of the producer writes (tests and tools derive
  * their edge-case widths from it). */
 int sgm_window_cost_tile_cols(void);
+
+/* ---- the cost filters on a finished volume ----
+ *
+ * SGM::process runs cost_horizontal_filter(COST_WIN_W / scale) and
+ * cost_vertical_filter(COST_WIN_H / scale) over the disparity space image it
+ * built (SGM.cpp:66-72, Solver.cpp:296-368) before the path passes.  Census
+ * frames have always done so, fused into their cost kernels; these entry points
+ * run the same two filters, bit for bit, over a finished dense fp32 rows x cols
+ * x D (HWD) volume: win_w = 5 / scale, win_h = 3 / scale (integer division: 5
+ * and 3, or 2 and 1).  Horizontal, one serial chain per (row, d):
+ *   sum = c[0] + .. + c[win - 1]                  (left to right, from 0)
+ *   step t = 0 .. cols - 2 (win / 2) - 1:
+ *     c[win - win / 2 - 1 + t] = sum / win        (correctly rounded)
+ *     sum += c[win + t];  sum -= c[t]             (two roundings; not after the last step)
+ * in place, so c[t] is an already FILTERED value once t >= win - win / 2 - 1: an
+ * IIR, not a box filter.  The columns the steps do not write keep their raw
+ * values (two on either side at win 5; the last two at win 2).  Vertical: the
+ * same recursion down each (col, d) chain; win 1 is not the identity ((c0 + c1)
+ * - c0 is rounded twice) and is reproduced.  Order: horizontal, then vertical.
+ * Filtered values may leave [0, 999999]: after a steep drop the recursion
+ * undershoots below zero (census frames beside sky pixels do the same).  The
+ * maps stay pinned all the same: the path passes that follow are the ones
+ * census frames run on such volumes.  Other windows are not offered. */
+enum { SGM_FILTER_H = 1, SGM_FILTER_V = 2 };   /* sgm_stage_cost's `filters` bits */
+
+/* The filters every later VOLUME frame of the handle runs: sgm_aggregate_device
+ * and the frames of SAD / SSD handles (sgm_set_cost).  0 = off, every handle's
+ * default: such a handle enqueues exactly the launches it always did.  A
+ * property of the handle like sgm_set_cost (sgm_params and SGM_HIP_VERSION are
+ * unchanged); it allocates nothing (every frame handle holds the Ch volume the
+ * census frames filter through) and waits for nothing; call it outside stream
+ * capture and re-capture graphs afterwards.  The filters run after the import or
+ * producer launch; with views == 2 the right view's volume is first derived
+ * from the RAW left volume, then each view is filtered on its own, as the
+ * reference builds each view's DSI and then filters it.  The horizontal filter
+ * is one launch over both views (profile class "vol_hfilter"); the vertical one
+ * runs fused with the L3 forward pass, per view ("vfwd", in the place of
+ * "pair_fwd_L3").  Census frames ignore the setting: they filter as ever.
+ * SGM_ERR_INVALID_ARG, with a message and nothing changed, for bits other than
+ * SGM_FILTER_H | SGM_FILTER_V and for BM, aux_only and SGM_VIEW_RIGHT handles. */
+int sgm_set_volume_filter(sgm_handle *h, int filters);
+int sgm_get_volume_filter(const sgm_handle *h, int *filters);
+
+/* The filters `filters` names (whatever the setter says), in place on d_cost: a
+ * dense fp32 HWD volume of the handle's working size and D in DEVICE memory,
+ * 16-byte aligned.  Only enqueues on `stream` (NULL = the handle's stream): no
+ * host wait, no allocation, capturable into a HIP graph.  The horizontal filter
+ * alone runs inside d_cost; with the vertical one the call goes through the
+ * left view's Ch volume and L3 checkpoints, scratch every frame rewrites, so
+ * it is refused on aux_only handles, which hold none (every other handle
+ * serves, BM and SGM_VIEW_RIGHT ones included).  The vertical filter alone
+ * costs one device copy more (profile class "vol_copy").  A volume filtered
+ * this way and handed to sgm_aggregate_device on a handle whose setting is 0
+ * gives the maps the setting gives on a views == 1 handle; with views == 2 the
+ * setting filters the derived right volume itself, which a caller-side filter
+ * of the left volume cannot reproduce.  SGM_ERR_INVALID_ARG, with a message and
+ * nothing enqueued, for a NULL or misaligned pointer, filters outside 1 .. 3,
+ * hipStreamLegacy as the stream (see sgm_volume_import_device) and aux_only
+ * handles. */
+int sgm_filter_volume_device(sgm_handle *h, float *d_cost, int filters, void *stream);
+/* Its HOST-memory twin (tests): rows * cols * D floats, filtered in place; synchronous. */
+int sgm_stage_filter_volume(sgm_handle *h, float *cost, int filters);
+/* The steps of one prefetched block of the horizontal filter's main loop (tests
+ * and tools derive their edge-case widths from it). */
+int sgm_volume_filter_block(void);
 
 /* ---- the matching window: WIN_H, WIN_W of inc/Solver.h as a setting ----
  *

@@ -51,7 +51,12 @@ EXPORTS = (
     "sgm_volume_import_device", "sgm_aggregate_device",
     "sgm_set_cost", "sgm_get_cost", "sgm_window_cost_device", "sgm_stage_window_cost",
     "sgm_window_cost_tile_cols", "sgm_set_window", "sgm_get_window",
+    "sgm_set_volume_filter", "sgm_get_volume_filter", "sgm_filter_volume_device",
+    "sgm_stage_filter_volume", "sgm_volume_filter_block",
 )
+# sgm_set_volume_filter's bits (SGM_FILTER_*)
+SGM_FILTER_H = 1
+SGM_FILTER_V = 2
 # sgm_set_cost's kinds (SGM_COST_*), by name
 COST_KINDS = {"census": 0, "sad": 1, "ssd": 2}
 # sgm_volume's element types (SGM_VOL_*)
@@ -225,6 +230,11 @@ def lib():
     L.sgm_window_cost_tile_cols.argtypes = []
     L.sgm_set_window.argtypes = [P, I, I]
     L.sgm_get_window.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
+    L.sgm_set_volume_filter.argtypes = [P, I]
+    L.sgm_get_volume_filter.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_filter_volume_device.argtypes = [P, P, I, P]
+    L.sgm_stage_filter_volume.argtypes = [P, P, I]
+    L.sgm_volume_filter_block.argtypes = []
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

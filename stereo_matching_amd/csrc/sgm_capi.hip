@@ -814,6 +814,67 @@ int sgm_stage_window_cost(sgm_handle *h, int kind, const uint8_t *left, const ui
     return SGM_OK;
 }
 
+int sgm_set_volume_filter(sgm_handle *h, int filters) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (filters & ~(SGM_FILTER_H | SGM_FILTER_V))
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_volume_filter: filters must be 0 or SGM_FILTER_H | SGM_FILTER_V bits, got %d", filters);
+    if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_volume_filter: BM and aux_only handles run no volume frames");
+    if (h->p.view == SGM_VIEW_RIGHT)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_set_volume_filter: a SGM_VIEW_RIGHT handle (volume frames start from the left view's)");
+    // (a host-side switch the next volume frame reads, as sgm_set_cost: the filters work in the
+    // C and Ch volumes every frame handle holds)
+    h->vol_filter = filters;
+    return SGM_OK;
+}
+
+int sgm_get_volume_filter(const sgm_handle *h, int *filters) {
+    if (!h || !filters) return SGM_ERR_INVALID_ARG;
+    *filters = h->vol_filter;
+    return SGM_OK;
+}
+
+int sgm_volume_filter_block(void) { return sgm::volume_filter_block(); }
+
+int sgm_filter_volume_device(sgm_handle *h, float *d_cost, int filters, void *stream) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!d_cost || (uintptr_t)d_cost % 16)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_filter_volume_device: d_cost is NULL or not 16-byte aligned");
+    if (filters < 1 || filters > (SGM_FILTER_H | SGM_FILTER_V))
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_filter_volume_device: filters must be SGM_FILTER_H, SGM_FILTER_V or both, got %d", filters);
+    // (as check_volume: an end event recorded on the legacy stream is one the next call waits on)
+    if (stream == (void *)hipStreamLegacy)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_filter_volume_device: hipStreamLegacy is not accepted; pass a created stream, or NULL "
+                       "for the handle's own");
+    if (h->p.aux_only)
+        return set_err(h, SGM_ERR_INVALID_ARG,
+                       "sgm_filter_volume_device: handle created with aux_only (no Ch volume to filter through)");
+    DeviceGuard guard(h->device);
+    StreamScope scope(h, stream);
+    return sgm::filter_volume(h, d_cost, filters, scope.st);
+}
+
+int sgm_stage_filter_volume(sgm_handle *h, float *cost, int filters) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!cost) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_filter_volume: NULL volume");
+    if (h->p.aux_only)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_filter_volume: handle created with aux_only (no cost volumes)");
+    DeviceGuard guard(h->device);
+    const size_t nvol = (size_t)h->g.H * h->g.W * h->g.D;
+    {  // staged in view 0's C
+        StreamScope scope(h, nullptr);
+        HIPCHK(h, hipMemcpyAsync(h->d_c[0], cost, nvol * sizeof(float), hipMemcpyHostToDevice, h->st));
+    }
+    if (int rc = sgm_filter_volume_device(h, h->d_c[0], filters, nullptr)) return rc;
+    HIPCHK(h, hipMemcpyAsync(cost, h->d_c[0], nvol * sizeof(float), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    return SGM_OK;
+}
+
 #ifdef SGM_SLANT_DEBUG
 // hang-guard give-ups of the slanted passes (SlantCtl::err), read and cleared
 int sgm_debug_slant_err(sgm_handle *h, unsigned *down, unsigned *up) {

@@ -535,7 +535,14 @@ int input_slot(sgm_handle *h, FrameIO *f, hipStream_t st) {
     return SGM_OK;
 }
 
-// The frame from the cost volume on, given every view's final volume in its C
+// Where a volume frame's producers (aggregate_volume's import, window_cost_stage) leave view v's raw
+// volume: its C, which the horizontal filter reads and the unfiltered passes aggregate; with the
+// vertical filter alone its Ch, vfwd's input.
+float *volume_raw_buf(sgm_handle *h, int v) {
+    return h->vol_filter == SGM_FILTER_V ? h->d_ch[v] : cost_buf(h, v);
+}
+
+// The frame from the cost volume on, given every view's raw volume in volume_raw_buf
 // (aggregate_volume's import, or window_cost_stage): the maps' wiring is
 // frame_maps'; stage_aggregate's passes -- the L3 checkpoints from the final
 // volume, then the whole-volume aggregation, whatever schedule the handle's
@@ -551,9 +558,30 @@ int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
     if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
     int rc = SGM_OK;
-    for (int v = 0; v < nv; ++v)
-        HIPCHK(h, timed(h, "pair_fwd_L3", elems, st,
-                        [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r[v].fin, g, st); }));
+    // the handle's cost filters (sgm_set_volume_filter), each view's volume on its
+    // own as SGM::process filters each DSI it built: the horizontal one over both views in one
+    // launch -- in place in C, or with the vertical one to follow into Ch, which vfwd reads --,
+    // the vertical one as the census frames run it, fused with the L3 forward pass (vfwd in the
+    // place of pair_fwd_L3; alone it finds the raw volumes in Ch: volume_raw_buf)
+    const int fl = h->vol_filter;
+    if (fl & SGM_FILTER_H) {
+        const bool to_ch = (fl & SGM_FILTER_V) != 0;
+        const float *in[2] = {cost_buf(h, 0), nv == 2 ? cost_buf(h, 1) : nullptr};
+        float *out[2] = {to_ch ? h->d_ch[0] : cost_buf(h, 0), nv == 2 ? (to_ch ? h->d_ch[1] : cost_buf(h, 1)) : nullptr};
+        HIPCHK(h, timed(h, "vol_hfilter", nv * elems, st,
+                        [&] { return sgm::launch_volume_hfilter(in, out, nv, to_ch, g, st); }));
+    }
+    for (int v = 0; v < nv; ++v) {
+        if (fl & SGM_FILTER_V) {
+            const PairArgs pa = vfwd_args(h, v);
+            const float *in = h->d_ch[v];
+            float *out = cost_buf(h, v);
+            HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &out, &pa, 1, nullptr, g, st); }));
+        } else {
+            HIPCHK(h, timed(h, "pair_fwd_L3", elems, st,
+                            [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r[v].fin, g, st); }));
+        }
+    }
     if (h->paths4) rc = aggregate4(h, nv, r, st);
     else
         for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
@@ -576,18 +604,19 @@ int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
 // The cost stage of a frame on a SAD or SSD handle (sgm_set_cost, DESIGN.md
 // 5o): one launch writes the left view's window cost volume into its C; with
 // two views the import kernel's right-view role derives the right view's from
-// it (the handle's own left buffer as a dense fp32 HWD source).  No census, no
-// cost filters, no masks.
+// it (the handle's own left buffer as a dense fp32 HWD source), from the raw
+// volume: the handle's cost filters (sgm_set_volume_filter) run after it, in
+// volume_frame.  No census, no masks.
 int window_cost_stage(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     const Geom g = h->g;
     HIPCHK(h, timed(h, "window_cost", vol_elems(g), st, [&] {
-               return sgm::launch_window_cost(h->cost_kind, f.left, f.right, f.pitch, cost_buf(h, 0),
+               return sgm::launch_window_cost(h->cost_kind, f.left, f.right, f.pitch, volume_raw_buf(h, 0),
                                               h->min_disp, g, h->win, st);
            }));
     if (h->nviews == 2)
         HIPCHK(h, timed(h, "vol_import", vol_elems(g), st, [&] {
-                   return sgm::launch_volume_import(cost_buf(h, 0), sgm::kVolF32, (long long)g.W * g.D, g.D, 1,
-                                                    nullptr, cost_buf(h, 1), h->min_disp, g, st);
+                   return sgm::launch_volume_import(volume_raw_buf(h, 0), sgm::kVolF32, (long long)g.W * g.D, g.D, 1,
+                                                    nullptr, volume_raw_buf(h, 1), h->min_disp, g, st);
                }));
     return SGM_OK;
 }
@@ -675,14 +704,36 @@ int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
     return h->paths4 ? aggregate4(h, 1, &r, st) : aggregate(h, &r, 1, st, true);
 }
 
+int sgm::filter_volume(sgm_handle *h, float *d_cost, int filters, hipStream_t st) {
+    const Geom g = h->g;
+    const double elems = vol_elems(g);
+    const float *in = d_cost;
+    if (filters & SGM_FILTER_H) {
+        // alone in place; with the vertical filter to follow into view 0's Ch, as in the frames
+        float *out = filters & SGM_FILTER_V ? h->d_ch[0] : d_cost;
+        HIPCHK(h, timed(h, "vol_hfilter", elems, st,
+                        [&] { return sgm::launch_volume_hfilter(&in, &out, 1, out != d_cost, g, st); }));
+        in = out;
+    } else if (filters & SGM_FILTER_V) {  // (vfwd's volumes are __restrict__: it reads a copy)
+        HIPCHK(h, timed(h, "vol_copy", elems, st, [&] { return sgm::launch_copy(d_cost, h->d_ch[0], g, st); }));
+        in = h->d_ch[0];
+    }
+    if (filters & SGM_FILTER_V) {
+        // (its L3 checkpoints land in view 0's, which every frame rewrites)
+        const PairArgs pa = vfwd_args(h, 0);
+        HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &d_cost, &pa, 1, nullptr, g, st); }));
+    }
+    return SGM_OK;
+}
+
 int sgm::aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,
                           hipStream_t st) {
     const int nv = h->nviews;
-    // one launch reads the caller's volume and writes every view's C
+    // one launch reads the caller's volume and writes every view's raw volume
     HIPCHK(h, timed(h, "vol_import", nv * vol_elems(h->g), st, [&] {
                return sgm::launch_volume_import(vol.d_cost, vol.dtype, vol.stride_row, vol.stride_col,
-                                                vol.stride_disp, cost_buf(h, 0), nv == 2 ? cost_buf(h, 1) : nullptr,
-                                                h->min_disp, h->g, st);
+                                                vol.stride_disp, volume_raw_buf(h, 0),
+                                                nv == 2 ? volume_raw_buf(h, 1) : nullptr, h->min_disp, h->g, st);
            }));
     // (no images: sgm_aggregate_device refuses handles with lk_refine)
     if (int rc = volume_frame(h, {nullptr, nullptr, 0, nullptr, nullptr, 0, d_out, out_pitch, d_raw}, st)) return rc;

@@ -61,6 +61,9 @@ struct sgm_handle {
     int win_h, win_w;     //   as set (the reference's WIN_H, WIN_W: 7, 9)
     int cost_kind;        // sgm_set_cost: SGM_COST_CENSUS (frames as ever), or the SAD / SSD window cost
                           //   (frames: window_cost_stage + volume_frame, sgm_frame.hip)
+    int vol_filter;       // sgm_set_volume_filter: the cost filters (SGM_FILTER_H | SGM_FILTER_V) every
+                          //   volume frame runs on each view's volume (aggregate_volume, SAD / SSD
+                          //   frames: volume_frame, sgm_frame.hip); 0: none
     uint64_t *d_cts[2];   // the tables shifted by min_disp / scale columns (launch_ct_shift):
                           // [0] the left image's (the right view's DSI reads it), [1] the right
                           // image's (the left view's); min_disp = 0: d_ct[0], d_ct[1] themselves
@@ -345,6 +348,9 @@ int stage_aggregate(sgm_handle *h, hipStream_t st);
 // (the tail a SAD / SSD frame shares: volume_frame, sgm_frame.hip)
 int aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,
                      hipStream_t st);
+// sgm_filter_volume_device: the cost filters `filters` in place on a caller's dense fp32 HWD volume
+// (the horizontal filter alone runs in it; with the vertical one, view 0's Ch is the scratch)
+int filter_volume(sgm_handle *h, float *d_cost, int filters, hipStream_t st);
 bool slant_default(Geom g, int nviews);
 int band_rows_for(Geom g);
 int slant_cus();

@@ -346,6 +346,14 @@ hipError_t launch_reproject(const double *q, const float *disp, int pitch, float
 hipError_t launch_volume_import(const void *src, int dtype, long long stride_row, long long stride_col,
                                 long long stride_disp, float *dst_l, float *dst_r, int min_disp, Geom g,
                                 hipStream_t st);
+// cost_horizontal_filter(COST_WIN_W / scale) (Solver.cpp:296-330) over nviews (1 or 2) dense fp32 HWD
+// volumes in one launch (sgm_volume_filter.hip): in[v] -> out[v], in place where
+// out[v] == in[v] (else the volumes must not overlap); nt: the output by non-temporal stores (a
+// volume read once, as Ch by vfwd).  g.W >= 5 / g.scale.
+hipError_t launch_volume_hfilter(const float *const *in, float *const *out, int nviews, bool nt, Geom g,
+                                 hipStream_t st);
+// the steps of one prefetched block of its main loop (the widths around it: tests)
+int volume_filter_block();
 // The SAD (kind 1) or SSD (kind 2) window cost of two grey images (sgm_window_cost.hip, DESIGN.md
 // 5o) as the dense fp32 HWD left volume, one launch: left, right of g.H * g.scale rows and g.W *
 // g.scale columns, pitch bytes per row, read decimated by g.scale and not blurred.

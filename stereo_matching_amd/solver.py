@@ -70,7 +70,7 @@ class SGM:
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
                  input_size=None, rectify=None, input_format: str = "gray8", reproject=None,
-                 cost: str = "census", window=None, _solver: int = _capi.SGM_SOLVER_SGM):
+                 cost: str = "census", window=None, volume_filter=None, _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # cost ("census" | "sad" | "ssd"): the matching cost of every frame
         # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost
@@ -164,6 +164,10 @@ class SGM:
             # reference's WIN_H, WIN_W before the division by s (set_window); None: (7, 9)
             if window is not None:
                 self.set_window(*window)
+            # volume_filter = (horizontal, vertical): the reference's cost filters on every
+            # volume frame (aggregate(), SAD / SSD frames; set_volume_filter); None: off
+            if volume_filter is not None:
+                self.set_volume_filter(*volume_filter)
         except Exception:
             self.close()
             raise
@@ -624,8 +628,8 @@ class SGM:
         """sgm_set_cost: "census" (the default), "sad" or "ssd".  With a window
         cost every later frame builds the reference's build_dsi volume (one
         launch), derives the right view's from it and runs what aggregate()
-        runs; the cost filters are not applied and sky masks are refused.
-        Re-capture graphs afterwards."""
+        runs; the cost filters run only when set_volume_filter says so, and sky
+        masks are refused.  Re-capture graphs afterwards."""
         if kind not in _capi.COST_KINDS:
             raise ValueError(f"cost must be one of {sorted(_capi.COST_KINDS)}, got {kind!r}")
         check(self._lib.sgm_set_cost(self._h, _capi.COST_KINDS[kind]), self._h)
@@ -636,6 +640,60 @@ class SGM:
         k = ctypes.c_int()
         check(self._lib.sgm_get_cost(self._h, ctypes.byref(k)), self._h)
         return {v: n for n, v in _capi.COST_KINDS.items()}[k.value]
+
+    # --------------------------------- the cost filters on a finished volume
+    @staticmethod
+    def _filter_bits(horizontal, vertical) -> int:
+        return (_capi.SGM_FILTER_H if horizontal else 0) | (_capi.SGM_FILTER_V if vertical else 0)
+
+    def set_volume_filter(self, horizontal: bool = True, vertical: bool = True) -> None:
+        """sgm_set_volume_filter: the reference's cost_horizontal_filter(5 // s)
+        and cost_vertical_filter(3 // s) (Solver.cpp:296-368) on each view's
+        volume in every later volume frame: aggregate() and the frames of
+        "sad" / "ssd" handles, after the import or producer launch and after
+        the right view's derivation from the raw left volume.  Both False:
+        off, the default.  Census frames ignore it (they filter as ever).
+        Allocates nothing; call it outside stream capture and re-capture
+        graphs afterwards.  BM, aux_only and view="right" handles raise
+        SGMError."""
+        check(self._lib.sgm_set_volume_filter(self._h, self._filter_bits(horizontal, vertical)), self._h)
+
+    @property
+    def volume_filter(self):
+        """sgm_get_volume_filter: (horizontal, vertical)."""
+        f = ctypes.c_int()
+        check(self._lib.sgm_get_volume_filter(self._h, ctypes.byref(f)), self._h)
+        return bool(f.value & _capi.SGM_FILTER_H), bool(f.value & _capi.SGM_FILTER_V)
+
+    def filter_volume(self, cost, horizontal: bool = True, vertical: bool = True, stream=None):
+        """sgm_filter_volume_device: the cost filters, in place, on a contiguous
+        float32 torch device tensor of shape (rows, cols, D), whatever
+        set_volume_filter says.  Enqueued on `stream` (default: the device's
+        current torch stream; torch's default stream goes through the handle's
+        own, as for aggregate).  Returns `cost`.  Filtered this way a volume
+        goes into aggregate() of a views=1 handle whose setting is off and
+        gives the maps the setting gives."""
+        if isinstance(cost, np.ndarray) or not hasattr(cost, "data_ptr"):
+            raise TypeError("cost must be a torch device tensor; for a host numpy volume use stage_filter_volume()")
+        import torch
+        shape = (self.rows, self.cols, self.max_disp)
+        if not cost.is_cuda or cost.device.index != self.device:
+            raise ValueError(f"cost must live on the handle's device cuda:{self.device}, got {cost.device}")
+        if cost.dtype != torch.float32 or tuple(cost.shape) != shape or not cost.is_contiguous():
+            raise ValueError(f"cost must be a contiguous float32 {shape} tensor")
+        bits = self._filter_bits(horizontal, vertical)
+        self._on_torch_stream(torch, cost, stream, lambda st: check(self._lib.sgm_filter_volume_device(
+            self._h, ctypes.c_void_p(cost.data_ptr()), bits, st), self._h))
+        return cost
+
+    def stage_filter_volume(self, cost, horizontal: bool = True, vertical: bool = True) -> np.ndarray:
+        """sgm_stage_filter_volume: the same filters on a host numpy (rows,
+        cols, D) float32 volume; returns the filtered copy (tests)."""
+        c = np.array(cost, np.float32, order="C", copy=True)
+        if c.shape != (self.rows, self.cols, self.max_disp):
+            raise ValueError(f"cost: expected shape {(self.rows, self.cols, self.max_disp)}, got {c.shape}")
+        check(self._lib.sgm_stage_filter_volume(self._h, _ptr(c), self._filter_bits(horizontal, vertical)), self._h)
+        return c
 
     def set_window(self, win_h: int, win_w: int) -> None:
         """sgm_set_window: the matching window of the census and of the SAD /
