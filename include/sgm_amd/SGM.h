@@ -46,6 +46,9 @@
  *                                the two filters alone, in place
  *   set_window(win_h, win_w)     inc/Solver.h:10-11  WIN_H, WIN_W as a setting of SGM and BM: the
  *                                census's and the window costs' window (sgm_set_window)
+ *   set_weighted(on), weighted() inc/Solver.h:15     WEIGHTED_COST as a setting: Gaussian SAD / SSD
+ *                                taps, the census masked to a disc (sgm_set_weighted);
+ *                                window_weights() is Solver.cpp:29-45's table
  *   show_disp(view)              Solver.cpp:55-93   (2h x w BGR, colormap :652-707)
  *
  * Mat is cv::Mat when OpenCV's core header is included first (or
@@ -62,6 +65,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../sgm_hip.h"
 
@@ -430,6 +434,26 @@ public:
     }
     void get_window(int *win_h, int *win_w) const {
         if (sgm_get_window(handle_, win_h, win_w) != SGM_OK) fail("get_window", sgm_last_error(handle_));
+    }
+    // The reference's WEIGHTED_COST (inc/Solver.h:15) as a setting (sgm_set_weighted): Gaussian
+    // taps in SAD and SSD, and the census's window masked to the disc of weights >= 0.5.  Every
+    // consumer of the window follows it.  Only with win_h / s and win_w / s odd: enabling it on
+    // another window, or setting such a window on a weighted solver, fails and changes nothing.
+    void set_weighted(bool enable) {
+        if (sgm_set_weighted(handle_, enable ? 1 : 0) != SGM_OK) fail("set_weighted", sgm_last_error(handle_));
+    }
+    bool weighted() const {
+        int on = 0;
+        if (sgm_get_weighted(handle_, &on) != SGM_OK) fail("weighted", sgm_last_error(handle_));
+        return on != 0;
+    }
+    // The (win_h / s) x (win_w / s) weight table in use, row-major (sgm_get_window_weights).
+    std::vector<float> window_weights() const {
+        int n = 0;
+        if (sgm_get_window_weights(handle_, nullptr, 0, &n) != SGM_OK) fail("window_weights", sgm_last_error(handle_));
+        std::vector<float> w((size_t)n);
+        if (sgm_get_window_weights(handle_, w.data(), n, &n) != SGM_OK) fail("window_weights", sgm_last_error(handle_));
+        return w;
     }
     // The SAD / SSD volume alone (sgm_window_cost_device): DEVICE grey images of
     // the constructed size, `pitch` bytes per row, into the dense fp32 rows x

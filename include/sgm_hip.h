@@ -603,8 +603,9 @@ int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int
  * The sum is an integer (at most 63 * 255^2); two correctly rounded fp32
  * divisions follow, in that order.  At scale 2 the loops run over 3 x 5 taps and
  * divide by 3 and 4, as the reference's do.  The largest cost is 65025.
- * WEIGHTED_COST (0 in the reference, inc/Solver.h:15) and an ensemble with the
- * census (no formula in the reference) are not built. */
+ * WEIGHTED_COST (0 in the reference, inc/Solver.h:15) is the handle setting
+ * sgm_set_weighted below; an ensemble with the census (no formula in the
+ * reference) is not built. */
 enum { SGM_COST_CENSUS = 0, SGM_COST_SAD = 1, SGM_COST_SSD = 2 };
 
 /* The cost every later frame of the handle matches on.  SGM_COST_CENSUS is
@@ -749,6 +750,47 @@ int sgm_volume_filter_block(void);
  * launches. */
 int sgm_set_window(sgm_handle *h, int win_h, int win_w);
 int sgm_get_window(const sgm_handle *h, int *win_h, int *win_w);
+
+/* ---- weighted windows: WEIGHTED_COST of inc/Solver.h as a setting ----
+ *
+ * With WEIGHTED_COST on, Solver::Solver builds a Gaussian table over the window
+ * (Solver.cpp:29-45), with e_h, e_w, HH, HW as above:
+ *   w[a][b] = (float)exp(((a - HH)^2 + (b - HW)^2) / -25.0),  a < e_h, b < e_w
+ * computed in double on the host whenever this setting or the window changes.
+ *   SAD, SSD  cost = 0.0f; over the taps in row-major order (a outer, b inner):
+ *             cost = cost + (float)AD * w[a][b], one fp32 multiply and one fp32
+ *             add, never fused, AD the integer |L - R| or (L - R)^2 at the
+ *             clamped coordinates of SGM_COST_*; then cost / e_h / e_w, two
+ *             correctly rounded divisions (cost.cpp:19-22, :48-51)
+ *   census    CT_pts skips every tap with w[a][b] < 0.5 (cost.cpp:115-116), that
+ *             is every tap outside the disc (a - HH)^2 + (b - HW)^2 <= 17; the
+ *             kept bits are appended in the same order, so the word narrows:
+ *             7 x 9 keeps 50 of 62 bits, 7 x 7 44 of 48, 5 x 9 40 of 44; 5 x 5,
+ *             3 x 3, 1 x 9 keep every bit.  Everything after the census sees
+ *             only the words.
+ * Odd effective windows only: with e_h or e_w even the reference indexes its
+ * table one past a row's end (at the default window and scale 2, 3 x 4 with
+ * 3 x 5 taps, past the table), which defines nothing.  sgm_set_weighted(h, 1)
+ * returns SGM_ERR_INVALID_ARG with a message when e_h or e_w is even, and
+ * sgm_set_window returns the same on a weighted handle for a window that would
+ * make either even -- (7, 9) at scale 2 is such a window; set (14, 18), or
+ * another odd pair, first.  Every other rule of sgm_set_window holds.
+ * Every consumer of the handle's window follows the setting: the census of SGM
+ * and BM frames of every schedule, sgm_stage_census, SAD / SSD frames,
+ * sgm_window_cost_device and sgm_stage_window_cost; any handle takes it,
+ * aux_only, BM and SGM_VIEW_RIGHT ones included.  A property of the handle like
+ * sgm_set_window (sgm_params and SGM_HIP_VERSION are unchanged): it
+ * synchronises the handle's last work, allocates nothing, is to be called
+ * outside stream capture, and graphs are to be re-captured afterwards.  Off, the
+ * default, launches exactly what an untouched handle launches; on, the census
+ * launch (profile class "census_masked" where the disc drops a tap) and the
+ * producer launch ("window_cost_weighted") are other kernels. */
+int sgm_set_weighted(sgm_handle *h, int enable);
+int sgm_get_weighted(const sgm_handle *h, int *enabled);
+/* The e_h x e_w table in use, row-major, into w[0 .. max - 1]; *count = e_h * e_w
+ * (w NULL: the count alone).  SGM_ERR_INVALID_ARG on a handle that is not
+ * weighted, or with max below the count. */
+int sgm_get_window_weights(sgm_handle *h, float *w, int max, int *count);
 
 /* Post-sync validity check of the frames enqueued so far (the reference has
  * no asynchronous work to check: SGM::process is synchronous, SGM.cpp:32-826).

@@ -53,6 +53,7 @@ EXPORTS = (
     "sgm_window_cost_tile_cols", "sgm_set_window", "sgm_get_window",
     "sgm_set_volume_filter", "sgm_get_volume_filter", "sgm_filter_volume_device",
     "sgm_stage_filter_volume", "sgm_volume_filter_block",
+    "sgm_set_weighted", "sgm_get_weighted", "sgm_get_window_weights",
 )
 # sgm_set_volume_filter's bits (SGM_FILTER_*)
 SGM_FILTER_H = 1
@@ -230,6 +231,9 @@ def lib():
     L.sgm_window_cost_tile_cols.argtypes = []
     L.sgm_set_window.argtypes = [P, I, I]
     L.sgm_get_window.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
+    L.sgm_set_weighted.argtypes = [P, I]
+    L.sgm_get_weighted.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_get_window_weights.argtypes = [P, P, I, ctypes.POINTER(I)]
     L.sgm_set_volume_filter.argtypes = [P, I]
     L.sgm_get_volume_filter.argtypes = [P, ctypes.POINTER(I)]
     L.sgm_filter_volume_device.argtypes = [P, P, I, P]

@@ -491,7 +491,9 @@ int sgm_set_min_disp(sgm_handle *h, int m) {
 
 int sgm_set_window(sgm_handle *h, int win_h, int win_w) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (const char *why = sgm::window_refusal(win_h, win_w, h->g.scale))
+    // (a weighted handle takes odd effective windows only: weighted_refusal)
+    if (const char *why = h->win.weighted ? sgm::weighted_refusal(win_h, win_w, h->g.scale)
+                                          : sgm::window_refusal(win_h, win_w, h->g.scale))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_window: %s, got (%d, %d) at scale %d", why, win_h, win_w,
                        h->g.scale);
     // (frames enqueued so far keep the launches they were given; the wait keeps the setter's
@@ -500,7 +502,10 @@ int sgm_set_window(sgm_handle *h, int win_h, int win_w) {
     return change_setting(h, "sgm_set_window", win_h == h->win_h && win_w == h->win_w, [&]() -> int {
         h->win_h = win_h;
         h->win_w = win_w;
+        const bool weighted = h->win.weighted;
         h->win = sgm::window_of(win_h, win_w, h->g.scale);
+        h->win.weighted = weighted;
+        if (weighted) sgm::window_weights(h->win, h->weights);
         return SGM_OK;
     });
 }
@@ -509,6 +514,39 @@ int sgm_get_window(const sgm_handle *h, int *win_h, int *win_w) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (win_h) *win_h = h->win_h;
     if (win_w) *win_w = h->win_w;
+    return SGM_OK;
+}
+
+int sgm_set_weighted(sgm_handle *h, int enable) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (enable)
+        if (const char *why = sgm::weighted_refusal(h->win_h, h->win_w, h->g.scale))
+            return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_weighted: %s, the window is (%d, %d) at scale %d", why,
+                           h->win_h, h->win_w, h->g.scale);
+    // (as sgm_set_window: frames enqueued so far keep their launches; nothing is allocated, the
+    // table travels in the producer's arguments and the census's mask is compiled in)
+    return change_setting(h, "sgm_set_weighted", (enable != 0) == h->win.weighted, [&]() -> int {
+        h->win.weighted = enable != 0;
+        if (enable) sgm::window_weights(h->win, h->weights);
+        return SGM_OK;
+    });
+}
+
+int sgm_get_weighted(const sgm_handle *h, int *enabled) {
+    if (!h || !enabled) return SGM_ERR_INVALID_ARG;
+    *enabled = h->win.weighted ? 1 : 0;
+    return SGM_OK;
+}
+
+int sgm_get_window_weights(sgm_handle *h, float *w, int max, int *count) {
+    if (!h) return SGM_ERR_INVALID_ARG;
+    if (!h->win.weighted)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_window_weights: the handle is not weighted (sgm_set_weighted)");
+    const int n = h->win.eh * h->win.ew;
+    if (w && max < n)
+        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_get_window_weights: the table has %d entries, max is %d", n, max);
+    if (w) memcpy(w, h->weights, (size_t)n * sizeof(float));
+    if (count) *count = n;
     return SGM_OK;
 }
 
@@ -786,8 +824,9 @@ int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const
     DeviceGuard guard(h->device);
     StreamScope scope(h, stream);
     hipStream_t st = scope.st;
-    HIPCHK(h, timed(h, "window_cost", vol_elems(h->g), st, [&] {
-               return sgm::launch_window_cost(kind, d_left, d_right, pitch, d_dst, h->min_disp, h->g, h->win, st);
+    HIPCHK(h, timed(h, window_cost_name(h), vol_elems(h->g), st, [&] {
+               return sgm::launch_window_cost(kind, d_left, d_right, pitch, d_dst, h->min_disp, h->g, h->win,
+                                              h->weights, st);
            }));
     return SGM_OK;
 }

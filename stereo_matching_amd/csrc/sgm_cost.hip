@@ -55,7 +55,23 @@ constexpr int CT_TW = 64, CT_TH = 16, CT_RPT = CT_TH / 4;  // 4 waves x CT_RPT r
 //      row is read once and feeds the census words of all the rows whose
 //      window holds it (bits appended in row-major order, as the reference).
 // Both images in one launch: workgroup z selects (src0, ct0) or (src1, ct1).
+//
+// MASKED (sgm_set_weighted): CT_pts with WEIGHTED_COST on skips the taps whose
+// Gaussian weight is below 0.5 (cost.cpp:115-116), which is the disc weighted_tap_kept; the kept
+// taps' bits are appended in the same order, so the word narrows (7 x 9: 50 bits).  CensusBits
+// numbers them at compile time; the loops below are unrolled, so a dropped tap costs nothing.
 template <int HH, int HWW>
+struct CensusBits {
+    int k[2 * HH + 1][2 * HWW + 1];  // the tap's bit position (0 = first, MSB); -1: the centre, or dropped
+    int nb;
+    constexpr CensusBits() : k{}, nb(0) {
+        for (int di = 0; di <= 2 * HH; ++di)
+            for (int dj = 0; dj <= 2 * HWW; ++dj)
+                k[di][dj] = (di != HH || dj != HWW) && weighted_tap_kept(di - HH, dj - HWW) ? nb++ : -1;
+    }
+};
+
+template <int HH, int HWW, bool MASKED = false>
 __global__ __launch_bounds__(256) void census_kernel(const uint8_t *__restrict__ src0,
                                                      const uint8_t *__restrict__ src1, int rpitch,
                                                      int step, int H, int W, int blur,
@@ -113,7 +129,8 @@ __global__ __launch_bounds__(256) void census_kernel(const uint8_t *__restrict__
     }
     __syncthreads();
     const int tx = t & 63, r0 = wave_id() * CT_RPT;
-    constexpr int NB = (2 * HH + 1) * (2 * HWW + 1) - 1;  // census bits (62 at 7x9)
+    constexpr CensusBits<HH, HWW> CB{};
+    constexpr int NB = MASKED ? CB.nb : (2 * HH + 1) * (2 * HWW + 1) - 1;  // census bits (62 at 7x9)
     static_assert(NB <= 64, "census word");
     constexpr int NHI = NB > 32 ? NB - 32 : 0;            // bits in the high word
     int c[CT_RPT];
@@ -136,7 +153,9 @@ __global__ __launch_bounds__(256) void census_kernel(const uint8_t *__restrict__
             for (int dj = 0; dj <= 2 * HWW; ++dj) {
                 if (di == HH && dj == HWW) continue;
                 // bit position k (0 = first, MSB) of the reference's order
-                const int k = di * (2 * HWW + 1) + dj - (di * (2 * HWW + 1) + dj > HH * (2 * HWW + 1) + HWW ? 1 : 0);
+                const int k = MASKED ? CB.k[di][dj]
+                                     : di * (2 * HWW + 1) + dj - (di * (2 * HWW + 1) + dj > HH * (2 * HWW + 1) + HWW ? 1 : 0);
+                if (MASKED && k < 0) continue;
                 // (c - b) has its sign bit set iff b > c (bytes, no overflow):
                 // w << 1 | x >> 31 is one funnel shift (v_alignbit_b32)
                 const unsigned x = (unsigned)(c[p] - b[dj]);
@@ -172,10 +191,37 @@ static const CensusFn kCensusTable[5][5] = {SGM_CENSUS_ROW(0), SGM_CENSUS_ROW(1)
                                             SGM_CENSUS_ROW(3), SGM_CENSUS_ROW(4)};
 #undef SGM_CENSUS_ROW
 
+// The masked census of a weighted handle (sgm_set_weighted): an entry for every
+// accepted pair of half sizes whose corners lie outside the disc (7 x 9, 9 x 7, 7 x 7, 5 x 9,
+// 9 x 5); null where the disc keeps every tap and the unmasked kernel is the masked one.
+template <int HH, int HWW>
+constexpr CensusFn census_masked_fn() {
+    if constexpr (census_fn<HH, HWW>() == nullptr || weighted_bits(HH, HWW) == (2 * HH + 1) * (2 * HWW + 1) - 1)
+        return nullptr;
+    else
+        return census_kernel<HH, HWW, true>;
+}
+#define SGM_CENSUS_ROW(HH)                                                                                \
+    {                                                                                                     \
+        census_masked_fn<HH, 0>(), census_masked_fn<HH, 1>(), census_masked_fn<HH, 2>(),                   \
+            census_masked_fn<HH, 3>(), census_masked_fn<HH, 4>()                                           \
+    }
+static const CensusFn kCensusMaskedTable[5][5] = {SGM_CENSUS_ROW(0), SGM_CENSUS_ROW(1), SGM_CENSUS_ROW(2),
+                                                  SGM_CENSUS_ROW(3), SGM_CENSUS_ROW(4)};
+#undef SGM_CENSUS_ROW
+
 hipError_t launch_census(const uint8_t *src, int pitch, Geom g, Window win, int blur, uint64_t *ct,
                          hipStream_t st, bool bm_rows, const uint8_t *src2, uint64_t *ct2) {
     dim3 grid((g.W + CT_TW - 1) / CT_TW, (g.H + CT_TH - 1) / CT_TH, src2 ? 2 : 1);
     const int rpitch = bm_rows ? pitch : pitch * g.scale;
+    if (win.weighted) {
+        if (win.eh < 1 || win.ew < 1 || win.eh % 2 == 0 || win.ew % 2 == 0 || win.hh() > 4 || win.hw() > 4)
+            return hipErrorInvalidValue;
+        if (const CensusFn masked = kCensusMaskedTable[win.hh()][win.hw()]) {
+            hipLaunchKernelGGL(masked, grid, dim3(256), 0, st, src, src2, rpitch, g.scale, g.H, g.W, blur, ct, ct2);
+            return hipGetLastError();
+        }
+    }
     const Window def = default_window(g.scale);
     if (win.hh() != def.hh() || win.hw() != def.hw()) {
         if (win.eh < 1 || win.ew < 1 || win.hh() > 4 || win.hw() > 4 || !kCensusTable[win.hh()][win.hw()])

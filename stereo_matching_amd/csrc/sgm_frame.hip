@@ -297,7 +297,7 @@ int bm_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
         f.sky_l = h->d_sky[0];
         f.sky_pitch = g.W;
     }
-    HIPCHK(h, timed(h, "census", 2 * npx, st, [&] {
+    HIPCHK(h, timed(h, census_name(h), 2 * npx, st, [&] {
                return sgm::launch_census(f.left, f.pitch, g, h->win, h->p.blur, h->d_ct[0], st, true, f.right,
                                          h->d_ct[1]);
            }));
@@ -439,7 +439,7 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
         d_sky_r = right_only ? h->d_sky[0] : h->nviews == 2 ? h->d_sky[1] : nullptr;
         sky_pitch = g.W;
     }
-    HIPCHK(h, timed(h, "census", 2 * npx, st, [&] {  // both images, one launch
+    HIPCHK(h, timed(h, census_name(h), 2 * npx, st, [&] {  // both images, one launch
                return sgm::launch_census(f.left, f.pitch, g, h->win, h->p.blur, h->d_ct[0], st, false,
                                          f.right, h->d_ct[1]);
            }));
@@ -609,9 +609,9 @@ int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
 // volume_frame.  No census, no masks.
 int window_cost_stage(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     const Geom g = h->g;
-    HIPCHK(h, timed(h, "window_cost", vol_elems(g), st, [&] {
+    HIPCHK(h, timed(h, window_cost_name(h), vol_elems(g), st, [&] {
                return sgm::launch_window_cost(h->cost_kind, f.left, f.right, f.pitch, volume_raw_buf(h, 0),
-                                              h->min_disp, g, h->win, st);
+                                              h->min_disp, g, h->win, h->weights, st);
            }));
     if (h->nviews == 2)
         HIPCHK(h, timed(h, "vol_import", vol_elems(g), st, [&] {

@@ -59,6 +59,8 @@ struct sgm_handle {
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
     sgm::Window win;      // sgm_set_window over the scale: the census's and the window costs' window
     int win_h, win_w;     //   as set (the reference's WIN_H, WIN_W: 7, 9)
+    float weights[sgm::kWinMax * sgm::kWinMax];  // sgm_set_weighted (win.weighted): window_weights' table of
+                          //   win, rebuilt by the setters; read by the weighted producer's launches
     int cost_kind;        // sgm_set_cost: SGM_COST_CENSUS (frames as ever), or the SAD / SSD window cost
                           //   (frames: window_cost_stage + volume_frame, sgm_frame.hip)
     int vol_filter;       // sgm_set_volume_filter: the cost filters (SGM_FILTER_H | SGM_FILTER_V) every
@@ -245,6 +247,17 @@ void dfree(sgm_handle *h, T **p, size_t count) {
     if (it != h->allocs.end()) h->allocs.erase(it);
     h->bytes -= count * sizeof(T);
     *p = nullptr;
+}
+
+// The profile names of the two launches sgm_set_weighted changes: the masked
+// census where the disc drops a tap of the window (else the launch is the unmasked kernel's),
+// and the weighted producer.
+inline const char *census_name(const sgm_handle *h) {
+    const sgm::Window w = h->win;
+    return w.weighted && sgm::weighted_bits(w.hh(), w.hw()) < w.bits() ? "census_masked" : "census";
+}
+inline const char *window_cost_name(const sgm_handle *h) {
+    return h->win.weighted ? "window_cost_weighted" : "window_cost";
 }
 
 // elements of one view's cost volume

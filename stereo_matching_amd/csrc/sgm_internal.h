@@ -213,7 +213,8 @@ hipError_t launch_slant_down(const SlantArgs &a, Geom g, hipStream_t st);
 
 // bm_rows: BM.cpp:24-25 decimation (rows not strided by the scale); src2/ct2:
 // a second image censused in the same launch; win: the handle's matching window
-// (sgm_set_window; the default launches census_kernel<3, 4> / <1, 2> as ever)
+// (sgm_set_window; the default launches census_kernel<3, 4> / <1, 2> as ever; win.weighted:
+// the masked census of sgm_set_weighted)
 hipError_t launch_census(const uint8_t *src, int pitch, Geom g, Window win, int blur, uint64_t *ct,
                          hipStream_t st, bool bm_rows = false, const uint8_t *src2 = nullptr,
                          uint64_t *ct2 = nullptr);
@@ -356,9 +357,11 @@ hipError_t launch_volume_hfilter(const float *const *in, float *const *out, int 
 int volume_filter_block();
 // The SAD (kind 1) or SSD (kind 2) window cost of two grey images (sgm_window_cost.hip, DESIGN.md
 // 5o) as the dense fp32 HWD left volume, one launch: left, right of g.H * g.scale rows and g.W *
-// g.scale columns, pitch bytes per row, read decimated by g.scale and not blurred.
+// g.scale columns, pitch bytes per row, read decimated by g.scale and not blurred.  win.weighted
+// (sgm_set_weighted): the weighted producer, with weights = window_weights' table of
+// win (host memory, copied into the launch's arguments); else weights is not read.
 hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
-                              int min_disp, Geom g, Window win, hipStream_t st);
+                              int min_disp, Geom g, Window win, const float *weights, hipStream_t st);
 // consumers (sgm_consumers.hip): Solver::colormap and the node's point cloud
 // (min_disp: the map is in true disparity; the colours are those of disp - min_disp over g.D)
 hipError_t launch_colormap(const float *disp, int pitch, uint8_t *bgr, int bgr_pitch, int min_disp,

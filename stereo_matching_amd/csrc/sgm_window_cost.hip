@@ -157,13 +157,143 @@ hipError_t launch_window(int hw, bool ssd, const WinArgs &a, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------- weighted taps
+//
+// sgm_set_weighted: cost.cpp:19-22, :48-51 with WEIGHTED_COST on.  Every tap is
+// multiplied by its Gaussian weight, so a cost is a chain of (2 hh + 1)(2 hw + 1) fp32 multiplies
+// and adds in the reference's tap order (rows outer, columns inner, from 0.0f; never fused:
+// -ffp-contract=off), and no two outputs share a partial sum.  The tile, the staged rows and the
+// stores are window_cost_kernel's.  What is shared is the tap itself: (float)AD(row, column, d)
+// does not depend on the output it feeds, so a lane converts a staged row's NCA taps once and
+// feeds them to every output column of its group, and to the two output rows it carries at a
+// time (staged row rr + a is window row a of output row rr and a - 1 of rr + 1).  The lane's
+// outputs are paired by column (k, k + NC / 2) in two-float vectors, the form v_pk_mul_f32 /
+// v_pk_add_f32 take; the weights come from the kernel's arguments (scalar registers).  Two
+// correctly rounded divisions end the chain (HIP's default f32 division; div_win's proof covers
+// integer sums only).
+struct WinWeights {
+    float w[kWinMax * kWinMax];  // w[a * e_w + b], window_weights' table
+};
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int HW, int DC, bool SSD>
+__global__ __launch_bounds__(256) void window_cost_weighted_kernel(WinArgs a, WinWeights ww) {
+    const int SCALE = a.scale, HH = a.hh;
+    constexpr int TJ = kWinCostTileCols, RB = kWinCostBandRows;
+    constexpr int NC = TJ / (256 / DC);  // columns per group of DC lanes
+    constexpr int NH = NC / 2;           // output pairs (k, k + NH)
+    constexpr int NCA = NC + 2 * HW;     // taps of a staged row the group reads
+    constexpr int NG = NH + 2 * HW;      // tap pairs (c, c + NH)
+    constexpr int EW = 2 * HW + 1;       // e_w (weighted windows are odd)
+    constexpr int LC = win_l_cols(HW);
+    constexpr int RC_MAX = win_r_cols(HW, 1, DC), NR_MAX = win_rows(kWinMax / 2);
+    static_assert(RB % 2 == 0 && NC % 2 == 0, "two rows and two columns per step");
+    const int RC = win_r_cols(HW, SCALE, DC), NR = win_rows(HH);
+    __shared__ uint8_t sl[NR_MAX * LC];
+    __shared__ uint8_t sr[NR_MAX * RC_MAX];
+    const int ntj = (a.W + TJ - 1) / TJ;
+    const int i0 = (bid_x() / ntj) * RB, j0 = (bid_x() % ntj) * TJ, d0 = bid_y() * DC;
+    const int t = tid_x();
+    const int s_hi = (d0 + DC - 1 + a.min_disp) / SCALE;
+    for (int idx = t; idx < NR * LC; idx += 256) {
+        const int r = idx / LC, c = idx - r * LC;
+        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = clampi(j0 - HW + c, 0, a.W - 1);
+        sl[idx] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
+    }
+    for (int idx = t; idx < NR * RC; idx += 256) {
+        const int r = idx / RC, c = idx - r * RC;
+        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = win_r_col(j0, c, a.W, HW, s_hi);
+        sr[idx] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
+    }
+    __syncthreads();
+    const int c0 = (t / DC) * NC, d = d0 + t % DC;
+    const int s = (d + a.min_disp) / SCALE;
+    int ru[NCA];
+#pragma unroll
+    for (int c = 0; c < NCA; ++c) ru[c] = win_r_index(j0, c0 + c, a.W, HW, s_hi, s);
+    f32x2 g[NG];
+    // staged row r's taps, as floats: g[c] = (tap c, tap c + NH)
+    auto taps = [&](int r) {
+        float f[NCA];
+#pragma unroll
+        for (int c = 0; c < NCA; ++c) {
+            const int v = (int)sl[r * LC + c0 + c] - (int)sr[r * RC + ru[c]];
+            f[c] = (float)(SSD ? v * v : (v < 0 ? -v : v));
+        }
+#pragma unroll
+        for (int c = 0; c < NG; ++c) g[c] = f32x2{f[c], f[c + NH]};
+    };
+    // window row wr of the outputs in acc: cost = cost + AD * w, columns in order
+    auto row = [&](f32x2 *acc, int wr) {
+#pragma unroll
+        for (int b = 0; b < EW; ++b) {
+            const float w = ww.w[wr * EW + b];
+#pragma unroll
+            for (int k = 0; k < NH; ++k) acc[k] = acc[k] + g[k + b] * w;
+        }
+    };
+    const int rows = a.H - i0 < RB ? a.H - i0 : RB;
+    for (int rr = 0; rr < rows; rr += 2) {
+        f32x2 acc0[NH], acc1[NH];
+#pragma unroll
+        for (int k = 0; k < NH; ++k) acc0[k] = acc1[k] = f32x2{0.0f, 0.0f};
+        // output rows rr and rr + 1 read staged rows rr .. rr + 2 HH + 1 (< NR: rr <= RB - 2)
+        taps(rr);
+        row(acc0, 0);
+        for (int ap = 1; ap <= 2 * HH; ++ap) {
+            taps(rr + ap);
+            row(acc0, ap);
+            row(acc1, ap - 1);
+        }
+        taps(rr + 2 * HH + 1);
+        row(acc1, 2 * HH);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (rr + q >= rows) break;
+            float *o = a.dst + ((size_t)(i0 + rr + q) * a.W + j0 + c0) * a.D + d;
+            const f32x2 *acc = q ? acc1 : acc0;
+#pragma unroll
+            for (int k = 0; k < NH; ++k) {
+                if (j0 + c0 + k < a.W) o[(size_t)k * a.D] = acc[k].x / a.fh / a.fw;
+                if (j0 + c0 + k + NH < a.W) o[(size_t)(k + NH) * a.D] = acc[k].y / a.fh / a.fw;
+            }
+        }
+    }
+}
+
+template <int HW, int DC>
+hipError_t launch_weighted_t(bool ssd, const WinArgs &a, const WinWeights &ww, hipStream_t st) {
+    const long long ntj = (a.W + kWinCostTileCols - 1) / kWinCostTileCols;
+    const long long nb = (a.H + kWinCostBandRows - 1) / kWinCostBandRows;
+    if (ntj * nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(ntj * nb), (unsigned)(a.D / DC));
+    if (ssd)
+        hipLaunchKernelGGL((window_cost_weighted_kernel<HW, DC, true>), grid, dim3(256), 0, st, a, ww);
+    else
+        hipLaunchKernelGGL((window_cost_weighted_kernel<HW, DC, false>), grid, dim3(256), 0, st, a, ww);
+    return hipGetLastError();
+}
+
+template <int DC>
+hipError_t launch_weighted(int hw, bool ssd, const WinArgs &a, const WinWeights &ww, hipStream_t st) {
+    switch (hw) {
+    case 0: return launch_weighted_t<0, DC>(ssd, a, ww, st);
+    case 1: return launch_weighted_t<1, DC>(ssd, a, ww, st);
+    case 2: return launch_weighted_t<2, DC>(ssd, a, ww, st);
+    case 3: return launch_weighted_t<3, DC>(ssd, a, ww, st);
+    case 4: return launch_weighted_t<4, DC>(ssd, a, ww, st);
+    }
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
-                              int min_disp, Geom g, Window win, hipStream_t st) {
+                              int min_disp, Geom g, Window win, const float *weights, hipStream_t st) {
     if (!left || !right || !dst || (kind != kCostSad && kind != kCostSsd) || min_disp < 0 ||
         (g.scale != 1 && g.scale != 2) || g.D % 32 != 0 || win.eh < 1 || win.eh > kWinMax || win.ew < 1 ||
-        win.ew > kWinMax || win.bits() > 64)
+        win.ew > kWinMax || win.bits() > 64 || (win.weighted && (!weights || win.eh % 2 == 0 || win.ew % 2 == 0)))
         return hipErrorInvalidValue;
     WinArgs a{};
     a.left = left;
@@ -181,6 +311,11 @@ hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *righ
     a.fw = (float)win.ew;
     a.rw = 1.0f / a.fw;
     const bool ssd = kind == kCostSsd;
+    if (win.weighted) {
+        WinWeights ww{};
+        for (int k = 0; k < win.eh * win.ew; ++k) ww.w[k] = weights[k];
+        return g.D == 32 ? launch_weighted<32>(win.hw(), ssd, a, ww, st) : launch_weighted<64>(win.hw(), ssd, a, ww, st);
+    }
     const Window def = default_window(g.scale);
     if (win.eh != def.eh || win.ew != def.ew)
         return g.D == 32 ? launch_window<32>(win.hw(), ssd, a, st) : launch_window<64>(win.hw(), ssd, a, st);

@@ -23,9 +23,10 @@ constexpr int kCostCensus = 0, kCostSad = 1, kCostSsd = 2;
 // has 5 taps, and SAD / SSD divide by e_h and e_w, not by the tap counts.
 struct Window {
     int eh, ew;  // win_h / scale, win_w / scale
+    bool weighted = false;  // sgm_set_weighted: Gaussian SAD / SSD taps, the census's disc
     constexpr int hh() const { return eh / 2; }  // taps above and below
     constexpr int hw() const { return ew / 2; }  // taps left and right
-    constexpr int bits() const { return (2 * hh() + 1) * (2 * hw() + 1) - 1; }  // census bits
+    constexpr int bits() const { return (2 * hh() + 1) * (2 * hw() + 1) - 1; }  // census bits (unmasked)
 };
 constexpr int kWinH = 7, kWinW = 9;  // inc/Solver.h
 constexpr int kWinMax = 9;           // the largest e_h, e_w served (half sizes <= 4)
@@ -42,6 +43,42 @@ constexpr const char *window_refusal(int win_h, int win_w, int scale) {
         return "win_h / scale and win_w / scale must lie in 1..9";
     if (w.hh() == 0 && w.hw() == 0) return "the window has no tap beside its centre";
     if (w.bits() > 64) return "the census word holds 64 bits (a 9 x 9 window has 80)";
+    return nullptr;
+}
+
+// The reference's WEIGHTED_COST (inc/Solver.h:15).  Solver::Solver's table
+// (Solver.cpp:29-45) is weight[a * e_w + b] = exp(((a - hh)^2 + (b - hw)^2) / -25.0), computed in
+// double and stored as float; SAD and SSD multiply every tap by it, CT_pts skips the taps whose
+// weight is below 0.5.  exp(-17 / 25) = 0.5066 and exp(-18 / 25) = 0.4868, so the census keeps the
+// disc da^2 + db^2 <= 17 (weighted_args_main.cpp compares the two forms over every tap).
+constexpr int kWeightDisc = 17;
+constexpr bool weighted_tap_kept(int da, int db) { return da * da + db * db <= kWeightDisc; }
+// census bits of the window's disc (the centre skipped): 7 x 9 keeps 50 of 62
+constexpr int weighted_bits(int hh, int hw) {
+    int n = 0;
+    for (int da = -hh; da <= hh; ++da)
+        for (int db = -hw; db <= hw; ++db) n += (da || db) && weighted_tap_kept(da, db);
+    return n;
+}
+// The table of an odd window, e_h * e_w floats in row-major order (out: kWinMax * kWinMax at the
+// most); the count written.
+inline int window_weights(Window w, float *out) {
+    for (int a = 0; a < w.eh; ++a)
+        for (int b = 0; b < w.ew; ++b) {
+            const double da = a - w.hh(), db = b - w.hw();
+            out[a * w.ew + b] = (float)exp((da * da + db * db) / -25.0);
+        }
+    return w.eh * w.ew;
+}
+// Why a weighted handle refuses (win_h, win_w) at this scale, or null: window_refusal's rules, and
+// both effective sides odd.  With an even side the reference's loops run one tap past the table's
+// row (cost.cpp:21 with j + win_w / 2 = win_w) and, at the last row, past the table: no definition.
+constexpr const char *weighted_refusal(int win_h, int win_w, int scale) {
+    if (const char *why = window_refusal(win_h, win_w, scale)) return why;
+    const Window w = window_of(win_h, win_w, scale);
+    if (w.eh % 2 == 0 || w.ew % 2 == 0)
+        return "weighted windows need odd win_h / scale and win_w / scale (the reference reads past its "
+               "weight table with an even side)";
     return nullptr;
 }
 

@@ -70,7 +70,8 @@ class SGM:
                  aux_only: bool = False, view: str = "left", paths: int = 8,
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
                  input_size=None, rectify=None, input_format: str = "gray8", reproject=None,
-                 cost: str = "census", window=None, volume_filter=None, _solver: int = _capi.SGM_SOLVER_SGM):
+                 cost: str = "census", window=None, volume_filter=None, weighted: bool = False,
+                 _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # cost ("census" | "sad" | "ssd"): the matching cost of every frame
         # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost
@@ -164,6 +165,10 @@ class SGM:
             # reference's WIN_H, WIN_W before the division by s (set_window); None: (7, 9)
             if window is not None:
                 self.set_window(*window)
+            # weighted: the reference's WEIGHTED_COST on that window (set_weighted), applied
+            # after it, so that SGM(..., s=2, window=(14, 18), weighted=True) is accepted
+            if weighted:
+                self.set_weighted(True)
             # volume_filter = (horizontal, vertical): the reference's cost filters on every
             # volume frame (aggregate(), SAD / SSD frames; set_volume_filter); None: off
             if volume_filter is not None:
@@ -711,6 +716,35 @@ class SGM:
         check(self._lib.sgm_get_window(self._h, ctypes.byref(wh), ctypes.byref(ww)), self._h)
         return wh.value, ww.value
 
+    def set_weighted(self, enable: bool = True) -> None:
+        """sgm_set_weighted: the reference's WEIGHTED_COST (inc/Solver.h:15) on
+        the handle's window.  SAD and SSD multiply every tap by the Gaussian
+        weight exp(-(da^2 + db^2) / 25) of its offset from the centre (fp32
+        multiply, then add, in the reference's tap order); the census skips the
+        taps whose weight is below 0.5, a disc of da^2 + db^2 <= 17 (7 x 9 keeps
+        50 of 62 bits).  Frames, stage_census() and window_cost() follow it from
+        the next call on.  Only with win_h // s and win_w // s odd: otherwise,
+        and for a later set_window() to such a window, SGMError and nothing
+        changes.  Waits for the handle's work; re-capture graphs afterwards."""
+        check(self._lib.sgm_set_weighted(self._h, 1 if enable else 0), self._h)
+
+    @property
+    def weighted(self) -> bool:
+        """sgm_get_weighted."""
+        on = ctypes.c_int()
+        check(self._lib.sgm_get_weighted(self._h, ctypes.byref(on)), self._h)
+        return bool(on.value)
+
+    def window_weights(self):
+        """sgm_get_window_weights: the (win_h // s, win_w // s) float32 weight
+        table of a weighted handle (Solver.cpp:29-45)."""
+        n = ctypes.c_int()
+        check(self._lib.sgm_get_window_weights(self._h, None, 0, ctypes.byref(n)), self._h)
+        w = np.empty(n.value, np.float32)
+        check(self._lib.sgm_get_window_weights(self._h, _ptr(w), n.value, ctypes.byref(n)), self._h)
+        wh, ww = self.window
+        return w.reshape(wh // self.scale, ww // self.scale)
+
     def window_cost(self, left, right, kind: str = "sad", out=None, stream=None):
         """sgm_window_cost_device: the float32 (rows, cols, D) SAD or SSD cost
         volume of two torch uint8 device images of shape (h, w) (unit column
@@ -989,12 +1023,12 @@ class BM(SGM):
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
                  post_filter_launches: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8", reproject=None, window=None):
+                 input_format: str = "gray8", reproject=None, window=None, weighted: bool = False):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
                          post_filter_launches=post_filter_launches, input_size=input_size,
                          rectify=rectify, input_format=input_format, reproject=reproject,
-                         window=window, _solver=_capi.SGM_SOLVER_BM)
+                         window=window, weighted=weighted, _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -1008,11 +1042,11 @@ class GPU_SGM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8", reproject=None, window=None):
+                 input_format: str = "gray8", reproject=None, window=None, weighted: bool = False):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
                          post_filter_launches=post_filter_launches, min_disp=min_disp,
                          input_size=input_size, rectify=rectify, input_format=input_format,
-                         reproject=reproject, window=window)
+                         reproject=reproject, window=window, weighted=weighted)
 
 
 # sgm_camera_q without a handle: the pinhole Q of a camera, 4 x 4 float64
