@@ -726,15 +726,20 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
     return SGM_OK;
 }
 
+// The volume entry points take no hipStreamLegacy: a call's end recorded on the legacy stream is an
+// event the next call on another stream would wait on; that wait crashed the host in torch's HIP
+// runtime (sgm_hip.h).  `fn`: the entry point's name, for the message.
+static int refuse_legacy_stream(sgm_handle *h, const char *fn, void *stream) {
+    if (stream != (void *)hipStreamLegacy) return SGM_OK;
+    return set_err(h, SGM_ERR_INVALID_ARG,
+                   "%s: hipStreamLegacy is not accepted; pass a created stream, or NULL for the handle's own", fn);
+}
+
 // The checks a caller's volume passes before anything is enqueued (sgm_volume_args.h); `fn`: the
 // entry point's name, for the message.
 static int check_volume(sgm_handle *h, const char *fn, const sgm_volume *vol, void *stream) {
     if (!vol || !vol->d_cost) return set_err(h, SGM_ERR_INVALID_ARG, "%s: NULL volume", fn);
-    // (a call's end recorded on the legacy stream is an event the next call on another stream
-    // would wait on; that wait crashed the host in torch's HIP runtime: sgm_hip.h)
-    if (stream == (void *)hipStreamLegacy)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "%s: hipStreamLegacy is not accepted; pass a created stream, or NULL for the handle's own", fn);
+    if (int rc = refuse_legacy_stream(h, fn, stream)) return rc;
     char why[256];
     if (!sgm::volume_layout(vol->dtype, vol->stride_row, vol->stride_col, vol->stride_disp, h->g.H, h->g.W,
                             h->g.D, why, sizeof(why)))
@@ -816,11 +821,7 @@ int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const
     if (!h) return SGM_ERR_INVALID_ARG;
     if (const char *why = sgm::window_cost_refusal(kind, d_left, d_right, pitch, h->p.width, d_dst))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_window_cost_device: %s", why);
-    // (as check_volume: an end event recorded on the legacy stream is one the next call waits on)
-    if (stream == (void *)hipStreamLegacy)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_window_cost_device: hipStreamLegacy is not accepted; pass a created stream, or NULL "
-                       "for the handle's own");
+    if (int rc = refuse_legacy_stream(h, "sgm_window_cost_device", stream)) return rc;
     DeviceGuard guard(h->device);
     StreamScope scope(h, stream);
     hipStream_t st = scope.st;
@@ -884,11 +885,7 @@ int sgm_filter_volume_device(sgm_handle *h, float *d_cost, int filters, void *st
     if (filters < 1 || filters > (SGM_FILTER_H | SGM_FILTER_V))
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_filter_volume_device: filters must be SGM_FILTER_H, SGM_FILTER_V or both, got %d", filters);
-    // (as check_volume: an end event recorded on the legacy stream is one the next call waits on)
-    if (stream == (void *)hipStreamLegacy)
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_filter_volume_device: hipStreamLegacy is not accepted; pass a created stream, or NULL "
-                       "for the handle's own");
+    if (int rc = refuse_legacy_stream(h, "sgm_filter_volume_device", stream)) return rc;
     if (h->p.aux_only)
         return set_err(h, SGM_ERR_INVALID_ARG,
                        "sgm_filter_volume_device: handle created with aux_only (no Ch volume to filter through)");
@@ -1000,10 +997,8 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, cons
     HIPCHK(h, sgm::launch_cost_h(&s, 1, h->g.W, filters & 1, h->g, h->st));
     const float *res = h->d_ch[0];
     if (filters & 2) {  // the frame's own vfwd, in place when the frames run it so
-        const sgm::PairArgs pa = vfwd_args(h, 0);
-        float *out = cost_buf(h, 0);
-        HIPCHK(h, sgm::launch_vfwd(&res, &out, &pa, 1, nullptr, h->g, h->st));
-        res = out;
+        if (int rc = sgm::vfwd_view(h, 0, res, cost_buf(h, 0), (double)nvol, h->st)) return rc;
+        res = cost_buf(h, 0);
     }
     HIPCHK(h, hipMemcpyAsync(cost, res, nvol * 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));

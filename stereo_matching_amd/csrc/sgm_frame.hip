@@ -46,6 +46,15 @@ int sgm::shift_tables(sgm_handle *h, const sgm::CostSlot *s, int nviews, hipStre
     return SGM_OK;
 }
 
+// One view's vertical cost filter fused with its L3 forward pass (sgm_handle.h)
+int sgm::vfwd_view(sgm_handle *h, int view, const float *in, float *out, double elems, hipStream_t st,
+                   sgm::Band band) {
+    PairArgs pa = vfwd_args(h, view);
+    pa.band = band;
+    HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &out, &pa, 1, nullptr, h->g, st); }));
+    return SGM_OK;
+}
+
 // The slanted-tile schedule replaces the bands (above the Infinity Cache)
 // where it was measured faster (tools/slant_sizes.py,
 // profiles/r04_experiments/slant.txt, with the H pair beside the top-down
@@ -196,10 +205,7 @@ int aggregate(sgm_handle *h, const ViewRoles *r, int nv, hipStream_t st, bool fi
 int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
     const Geom g = h->g;
     const double elems = vol_elems(g);
-    PairArgs va = vfwd_args(h, view);
     ViewRoles b = r;
-    const float *in = h->d_ch[view];
-    float *out = cost_buf(h, view);
     // band edges at H - m*BR (multiples of 16 rows from the bottom, as
     // the backward bands): whole segments of every family
     const int H = g.H, FR = h->band_rows;
@@ -207,8 +213,8 @@ int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
     for (int m = nb - 1; m >= 0; --m) {
         const int rb = H - (m + 1) * FR > 0 ? H - (m + 1) * FR : 0, re = H - m * FR;
         const double be = (double)(re - rb) / H * elems;
-        va.band = {rb, re, h->d_carry[view][2]};
-        HIPCHK(h, timed(h, "vfwd", be, st, [&] { return sgm::launch_vfwd(&in, &out, &va, 1, nullptr, g, st); }));
+        if (int rc = sgm::vfwd_view(h, view, h->d_ch[view], cost_buf(h, view), be, st, {rb, re, h->d_carry[view][2]}))
+            return rc;
         b.l5.band = {rb, re, h->d_carry[view][0]};
         b.d6.band = {rb, re, h->d_carry[view][1]};
         HIPCHK(h, timed(h, "stage_a_d", be, st, [&] { return sgm::launch_stage_a_band(&b, g, st); }));
@@ -260,6 +266,15 @@ int aggregate4(sgm_handle *h, int nv, const ViewRoles *r, hipStream_t st) {
     return SGM_OK;
 }
 
+// Whole-volume passes over nv views' final volumes and L3 checkpoints: the 4-path handle's, or
+// the 8-path aggregation view after view
+int aggregate_whole(sgm_handle *h, const ViewRoles *r, int nv, hipStream_t st) {
+    if (h->paths4) return aggregate4(h, nv, r, st);
+    int rc = SGM_OK;
+    for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
+    return rc;
+}
+
 // The frame's view slots: the left view in slot 0 and, with two views, the
 // right view in slot 1; a right-view handle (SGM_VIEW_RIGHT) runs the right
 // view, DSI 1 under the right mask, in slot 0.
@@ -275,12 +290,7 @@ int cost_view(sgm_handle *h, const CostSlot *s, int view, int sky_pitch, hipStre
     const double elems = vol_elems(h->g);
     HIPCHK(h, timed(h, "cost_h", elems, st,
                     [&] { return sgm::launch_cost_h(&s[view], 1, sky_pitch, 1, h->g, st); }));
-    if (!vfwd) return SGM_OK;
-    const PairArgs pa = vfwd_args(h, view);
-    const float *in = s[view].ch;
-    float *out = s[view].c;
-    HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &out, &pa, 1, nullptr, h->g, st); }));
-    return SGM_OK;
+    return vfwd ? sgm::vfwd_view(h, view, s[view].ch, s[view].c, elems, st) : SGM_OK;
 }
 
 // BM::process (src/BM.cpp:9-97): census with BM's row decimation, the left
@@ -503,6 +513,37 @@ int finish_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     return SGM_OK;
 }
 
+// The views' roles for a frame's maps.  Returns direct_out: one view with a dense output map, whose
+// final pass writes the sub-pixel map straight into it (no device copy after the frame); else
+// the handle's sub-pixel layout for the LR check.  The raw WTA map, when asked for, is written
+// straight into f.raw by the left view's final pass; the right view's is never written.
+bool frame_roles(sgm_handle *h, const FrameIO &f, ViewRoles *r) {
+    const bool direct_out = h->nviews == 1 && f.out_pitch == h->g.W;
+    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
+    if (h->nviews == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    return direct_out;
+}
+
+// The frame from the views' sub-pixel maps on: the LR check, or the one view's map copied where
+// the final pass could not write it, then post_filter and LKRefine.
+int views_to_out(sgm_handle *h, const FrameIO &f, bool direct_out, hipStream_t st) {
+    const Geom g = h->g;
+    if (h->nviews == 2) {
+        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
+                   // (true-disparity maps: the invalid marker is D + min_disp + 1)
+                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
+                                                        h->p.lr_max_diff, h->gt, st)
+                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, f.out,
+                                                     f.out_pitch, h->p.lr_max_diff, h->gt, st);
+               }));
+    } else if (!direct_out) {
+        HIPCHK(h, hipMemcpy2DAsync(f.out, (size_t)f.out_pitch * sizeof(float), h->d_sub[0],
+                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
+                                   hipMemcpyDeviceToDevice, st));
+    }
+    return finish_frame(h, f, st);
+}
+
 // The frame's input slot (DESIGN.md "The input slot"): at most one launch, by
 // the handle's input stage (sgm_input_stage.h), writes both full-size grey
 // images into d_rs (every handle's census reads both), and the sky detector,
@@ -543,20 +584,16 @@ float *volume_raw_buf(sgm_handle *h, int v) {
 }
 
 // The frame from the cost volume on, given every view's raw volume in volume_raw_buf
-// (aggregate_volume's import, or window_cost_stage): the maps' wiring is
-// frame_maps'; stage_aggregate's passes -- the L3 checkpoints from the final
-// volume, then the whole-volume aggregation, whatever schedule the handle's
-// frames run --, the LR check or the one-view copy, post_filter and LKRefine.
+// (aggregate_volume's import, or window_cost_stage): frame_maps' wiring
+// (frame_roles); stage_aggregate's passes -- the L3 checkpoints from the final
+// volume, then aggregate_whole, whatever schedule the handle's frames run --,
+// and frame_maps' tail (views_to_out).
 int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     const Geom g = h->g;
     const int nv = h->nviews;
     const double elems = vol_elems(g);
-    // a dense one-view map straight from the final pass, the handle's sub-pixel layout for the
-    // LR check
-    const bool direct_out = nv == 1 && f.out_pitch == g.W;
     ViewRoles r[2] = {};
-    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
-    if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    const bool direct_out = frame_roles(h, f, r);
     int rc = SGM_OK;
     // the handle's cost filters (sgm_set_volume_filter), each view's volume on its
     // own as SGM::process filters each DSI it built: the horizontal one over both views in one
@@ -573,32 +610,14 @@ int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     }
     for (int v = 0; v < nv; ++v) {
         if (fl & SGM_FILTER_V) {
-            const PairArgs pa = vfwd_args(h, v);
-            const float *in = h->d_ch[v];
-            float *out = cost_buf(h, v);
-            HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &out, &pa, 1, nullptr, g, st); }));
+            if ((rc = sgm::vfwd_view(h, v, h->d_ch[v], cost_buf(h, v), elems, st)) != SGM_OK) return rc;
         } else {
             HIPCHK(h, timed(h, "pair_fwd_L3", elems, st,
                             [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r[v].fin, g, st); }));
         }
     }
-    if (h->paths4) rc = aggregate4(h, nv, r, st);
-    else
-        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
-    if (rc != SGM_OK) return rc;
-    if (nv == 2) {
-        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
-                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
-                                                        h->p.lr_max_diff, h->gt, st)
-                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, f.out, f.out_pitch,
-                                                     h->p.lr_max_diff, h->gt, st);
-               }));
-    } else if (!direct_out) {
-        HIPCHK(h, hipMemcpy2DAsync(f.out, (size_t)f.out_pitch * sizeof(float), h->d_sub[0],
-                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
-                                   hipMemcpyDeviceToDevice, st));
-    }
-    return finish_frame(h, f, st);
+    if ((rc = aggregate_whole(h, r, nv, st)) != SGM_OK) return rc;
+    return views_to_out(h, f, direct_out, st);
 }
 
 // The cost stage of a frame on a SAD or SSD handle (sgm_set_cost, DESIGN.md
@@ -642,14 +661,8 @@ int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
     }
     bool have_c = false;
     if ((rc = cost_stage(h, f, st, &have_c)) != SGM_OK) return rc;
-    // one view with a dense output map: the final pass writes the sub-pixel
-    // map straight into it (no device copy after the frame)
-    const bool direct_out = nv == 1 && f.out_pitch == g.W;
-    // (the raw WTA map, when asked for, is written straight into f.raw by the
-    // left view's final pass; the right view's is never written)
     ViewRoles r[2] = {};
-    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
-    if (nv == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    const bool direct_out = frame_roles(h, f, r);
     switch (h->sched) {
     case SCHED_PATHS4: rc = aggregate4(h, nv, r, st); break;
     case SCHED_SLANT: rc = slant_views(h, r, st, have_c); break;
@@ -673,25 +686,10 @@ int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
         HIPCHK(h, timed(h, "pair_bwd_L4_final", 2.0 * elems, st,
                         [&] { return sgm::launch_final(r, 2, false, g, st); }));
         break;
-    case SCHED_PER_VIEW:
-        for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
-        break;
+    case SCHED_PER_VIEW: rc = aggregate_whole(h, r, nv, st); break;
     }
     if (rc != SGM_OK) return rc;
-    if (nv == 2) {
-        HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
-                   // (true-disparity maps: the invalid marker is D + min_disp + 1)
-                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
-                                                        h->p.lr_max_diff, h->gt, st)
-                                    : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, f.out,
-                                                     f.out_pitch, h->p.lr_max_diff, h->gt, st);
-               }));
-    } else if (!direct_out) {
-        HIPCHK(h, hipMemcpy2DAsync(f.out, (size_t)f.out_pitch * sizeof(float), h->d_sub[0],
-                                   (size_t)g.W * sizeof(float), (size_t)g.W * sizeof(float), g.H,
-                                   hipMemcpyDeviceToDevice, st));
-    }
-    return finish_frame(h, f, st);
+    return views_to_out(h, f, direct_out, st);
 }
 
 }  // namespace
@@ -701,7 +699,7 @@ int sgm::stage_aggregate(sgm_handle *h, hipStream_t st) {
     // the L3 checkpoints from the final volume (frames get them from vfwd)
     HIPCHK(h, timed(h, "pair_fwd_L3", vol_elems(h->g), st,
                     [&] { return sgm::launch_pair_fwd(sgm::PAIR_V, r.fin, h->g, st); }));
-    return h->paths4 ? aggregate4(h, 1, &r, st) : aggregate(h, &r, 1, st, true);
+    return aggregate_whole(h, &r, 1, st);
 }
 
 int sgm::filter_volume(sgm_handle *h, float *d_cost, int filters, hipStream_t st) {
@@ -718,12 +716,8 @@ int sgm::filter_volume(sgm_handle *h, float *d_cost, int filters, hipStream_t st
         HIPCHK(h, timed(h, "vol_copy", elems, st, [&] { return sgm::launch_copy(d_cost, h->d_ch[0], g, st); }));
         in = h->d_ch[0];
     }
-    if (filters & SGM_FILTER_V) {
-        // (its L3 checkpoints land in view 0's, which every frame rewrites)
-        const PairArgs pa = vfwd_args(h, 0);
-        HIPCHK(h, timed(h, "vfwd", elems, st, [&] { return sgm::launch_vfwd(&in, &d_cost, &pa, 1, nullptr, g, st); }));
-    }
-    return SGM_OK;
+    // (vfwd's L3 checkpoints land in view 0's, which every frame rewrites)
+    return filters & SGM_FILTER_V ? sgm::vfwd_view(h, 0, in, d_cost, elems, st) : SGM_OK;
 }
 
 int sgm::aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out_pitch, uint16_t *d_raw,

@@ -352,6 +352,10 @@ int lk_refine(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int 
 // the cost stage's view slots (sgm_internal.h) and the shifted tables they read
 sgm::CostSlot cost_slot(sgm_handle *h, int slot, int dsi, const uint8_t *sky);
 int shift_tables(sgm_handle *h, const sgm::CostSlot *s, int nviews, hipStream_t st);
+// one view's vfwd launch (profile class "vfwd" over `elems`): in -> out, the L3 checkpoints into
+// the view's; band: forward_bands' rows (default: the whole volume)
+int vfwd_view(sgm_handle *h, int view, const float *in, float *out, double elems, hipStream_t st,
+              sgm::Band band = {});
 // sgm_stage_aggregate: view 0's aggregation from the final cost volume in
 // d_c[0], whole-volume passes on every handle, into d_disp[0] and d_sub[0]
 int stage_aggregate(sgm_handle *h, hipStream_t st);

@@ -20,7 +20,9 @@
 // division over every reachable sum by tests/cpp/window_cost_args_main.cpp).
 // The window is the handle's (sgm_set_window): the default 7 x 9
 // with every constant at compile time, any other through the instantiation of
-// its half width (window_cost_kernel's comment).
+// its half width (window_cost_kernel's comment).  The weighted kernel
+// (sgm_set_weighted, 5r) shares the tile: win_tile, stage_rows and WinLane are
+// both kernels' prologue, launch_tiles and by_half_width both kernels' launch.
 #include "sgm_device.h"
 
 #include "sgm_window_cost_args.h"
@@ -48,6 +50,62 @@ __device__ __forceinline__ float div_rt(float x, float f, float r) {
     return __builtin_fmaf(e, r, q0);
 }
 
+// A workgroup's tile: its first row, column and disparity, the chunk's largest column shift and
+// the columns a staged row of R takes at this scale.
+struct WinTile {
+    int i0, j0, d0, s_hi, RC;
+};
+
+template <int HW, int DC>
+__device__ __forceinline__ WinTile win_tile(const WinArgs &a, int SCALE) {
+    const int ntj = (a.W + kWinCostTileCols - 1) / kWinCostTileCols;
+    const int d0 = bid_y() * DC;
+    return {(bid_x() / ntj) * kWinCostBandRows, (bid_x() % ntj) * kWinCostTileCols, d0,
+            (d0 + DC - 1 + a.min_disp) / SCALE, win_r_cols(HW, SCALE, DC)};
+}
+
+// The band's rows of L and R into the kernel's LDS arrays as bytes at clamped coordinates.  SCALE,
+// HH: constants in the default window's instantiations (they fold after inlining), else WinArgs'.
+template <int HW>
+__device__ __forceinline__ void stage_rows(const WinArgs &a, WinTile t, int SCALE, int HH, uint8_t *sl, uint8_t *sr) {
+    constexpr int LC = win_l_cols(HW);
+    const int NR = win_rows(HH), RC = t.RC;
+    for (int idx = tid_x(); idx < NR * LC; idx += 256) {
+        const int r = idx / LC, c = idx - r * LC;
+        const int y = clampi(t.i0 - HH + r, 0, a.H - 1), x = clampi(t.j0 - HW + c, 0, a.W - 1);
+        sl[idx] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
+    }
+    for (int idx = tid_x(); idx < NR * RC; idx += 256) {
+        const int r = idx / RC, c = idx - r * RC;
+        const int y = clampi(t.i0 - HH + r, 0, a.H - 1), x = win_r_col(t.j0, c, a.W, HW, t.s_hi);
+        sr[idx] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
+    }
+    __syncthreads();
+}
+
+// A lane's place in the tile: its group's first tile column c0 (tile column c0 + c is image
+// column j0 - HW + c0 + c: output column k of the group takes its taps k .. k + 2 HW), its
+// disparity d, the columns ru[] of its taps in a staged row of R, and the tap itself.
+template <int HW, int DC, bool SSD>
+struct WinLane {
+    static constexpr int NC = kWinCostTileCols / (256 / DC);  // columns per group of DC lanes
+    static constexpr int NCA = NC + 2 * HW;                   // taps of a staged row the group reads
+    static constexpr int LC = win_l_cols(HW);
+    int c0, d, RC, ru[NCA];
+    const uint8_t *sl, *sr;
+    __device__ __forceinline__ WinLane(const WinArgs &a, WinTile t, int SCALE, const uint8_t *sl_, const uint8_t *sr_)
+        : c0((tid_x() / DC) * NC), d(t.d0 + tid_x() % DC), RC(t.RC), sl(sl_), sr(sr_) {
+        const int s = (d + a.min_disp) / SCALE;
+#pragma unroll
+        for (int c = 0; c < NCA; ++c) ru[c] = win_r_index(t.j0, c0 + c, a.W, HW, t.s_hi, s);
+    }
+    // AD(staged row r, the group's tap c, d)
+    __device__ __forceinline__ int ad(int r, int c) const {
+        const int v = (int)sl[r * LC + c0 + c] - (int)sr[r * RC + ru[c]];
+        return SSD ? v * v : (v < 0 ? -v : v);
+    }
+};
+
 // HW, the window's half width, sizes the register arrays and is always a template
 // argument.  SCALE_T, HH_T, WH_T, WW_T are the default window's constants (the
 // code of before sgm_set_window); 0, -1, 0, 0 leave the scale, the half height
@@ -59,46 +117,21 @@ __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
     constexpr bool FIXED = SCALE_T != 0;
     static_assert(FIXED == (HH_T >= 0) && FIXED == (WH_T != 0) && FIXED == (WW_T != 0), "all or none");
     const int SCALE = FIXED ? SCALE_T : a.scale, HH = FIXED ? HH_T : a.hh;
-    constexpr int TJ = kWinCostTileCols, RB = kWinCostBandRows;
-    constexpr int NC = TJ / (256 / DC);  // columns per group of DC lanes
-    constexpr int NCA = NC + 2 * HW;     // column sums a group keeps
-    constexpr int LC = win_l_cols(HW);
+    using Lane = WinLane<HW, DC, SSD>;
+    constexpr int RB = kWinCostBandRows, NC = Lane::NC, NCA = Lane::NCA;  // NCA column sums a group keeps
     constexpr int RC_MAX = win_r_cols(HW, FIXED ? SCALE_T : 1, DC), NR_MAX = win_rows(FIXED ? HH_T : kWinMax / 2);
-    const int RC = win_r_cols(HW, SCALE, DC), NR = win_rows(HH);
-    __shared__ uint8_t sl[NR_MAX * LC];
+    __shared__ uint8_t sl[NR_MAX * Lane::LC];
     __shared__ uint8_t sr[NR_MAX * RC_MAX];
-    const int ntj = (a.W + TJ - 1) / TJ;
-    const int i0 = (bid_x() / ntj) * RB, j0 = (bid_x() % ntj) * TJ, d0 = bid_y() * DC;
-    const int t = tid_x();
-    const int s_hi = (d0 + DC - 1 + a.min_disp) / SCALE;
-    for (int idx = t; idx < NR * LC; idx += 256) {
-        const int r = idx / LC, c = idx - r * LC;
-        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = clampi(j0 - HW + c, 0, a.W - 1);
-        sl[idx] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
-    }
-    for (int idx = t; idx < NR * RC; idx += 256) {
-        const int r = idx / RC, c = idx - r * RC;
-        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = win_r_col(j0, c, a.W, HW, s_hi);
-        sr[idx] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
-    }
-    __syncthreads();
-    // tile column c0 + c is image column j0 - HW + c0 + c: output column k of the group sums
-    // its column sums k .. k + 2 HW
-    const int c0 = (t / DC) * NC, d = d0 + t % DC;
-    const int s = (d + a.min_disp) / SCALE;
-    int ru[NCA];
-#pragma unroll
-    for (int c = 0; c < NCA; ++c) ru[c] = win_r_index(j0, c0 + c, a.W, HW, s_hi, s);
-    auto ad = [&](int r, int c) -> int {
-        const int v = (int)sl[r * LC + c0 + c] - (int)sr[r * RC + ru[c]];
-        return SSD ? v * v : (v < 0 ? -v : v);
-    };
+    const WinTile t = win_tile<HW, DC>(a, SCALE);
+    stage_rows<HW>(a, t, SCALE, HH, sl, sr);
+    const Lane ln(a, t, SCALE, sl, sr);
+    const int i0 = t.i0, j0 = t.j0, c0 = ln.c0, d = ln.d;
     int cs[NCA];
 #pragma unroll
     for (int c = 0; c < NCA; ++c) {
         cs[c] = 0;
 #pragma unroll
-        for (int r = 0; r <= 2 * HH; ++r) cs[c] += ad(r, c);
+        for (int r = 0; r <= 2 * HH; ++r) cs[c] += ln.ad(r, c);
     }
     const int rows = a.H - i0 < RB ? a.H - i0 : RB;
     for (int rr = 0; rr < rows; ++rr) {
@@ -119,42 +152,9 @@ __global__ __launch_bounds__(256) void window_cost_kernel(WinArgs a) {
         // the window moves down a row: staged row rr + 2 HH + 1 enters, rr leaves
         if (rr + 1 < rows) {
 #pragma unroll
-            for (int c = 0; c < NCA; ++c) cs[c] += ad(rr + 2 * HH + 1, c) - ad(rr, c);
+            for (int c = 0; c < NCA; ++c) cs[c] += ln.ad(rr + 2 * HH + 1, c) - ln.ad(rr, c);
         }
     }
-}
-
-template <int HW, int DC, int SCALE_T, int HH_T, int WH_T, int WW_T>
-hipError_t launch_t(bool ssd, const WinArgs &a, hipStream_t st) {
-    const long long ntj = (a.W + kWinCostTileCols - 1) / kWinCostTileCols;
-    const long long nb = (a.H + kWinCostBandRows - 1) / kWinCostBandRows;
-    if (ntj * nb > 0x7fffffffLL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)(ntj * nb), (unsigned)(a.D / DC));
-    if (ssd)
-        hipLaunchKernelGGL((window_cost_kernel<HW, DC, true, SCALE_T, HH_T, WH_T, WW_T>), grid, dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((window_cost_kernel<HW, DC, false, SCALE_T, HH_T, WH_T, WW_T>), grid, dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// the default window at SCALE: every constant at compile time
-template <int SCALE, int DC>
-hipError_t launch_default(bool ssd, const WinArgs &a, hipStream_t st) {
-    constexpr Window w = default_window(SCALE);
-    return launch_t<w.hw(), DC, SCALE, w.hh(), w.eh, w.ew>(ssd, a, st);
-}
-
-// any other accepted window: one instantiation per half width
-template <int DC>
-hipError_t launch_window(int hw, bool ssd, const WinArgs &a, hipStream_t st) {
-    switch (hw) {
-    case 0: return launch_t<0, DC, 0, -1, 0, 0>(ssd, a, st);
-    case 1: return launch_t<1, DC, 0, -1, 0, 0>(ssd, a, st);
-    case 2: return launch_t<2, DC, 0, -1, 0, 0>(ssd, a, st);
-    case 3: return launch_t<3, DC, 0, -1, 0, 0>(ssd, a, st);
-    case 4: return launch_t<4, DC, 0, -1, 0, 0>(ssd, a, st);
-    }
-    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------- weighted taps
@@ -180,47 +180,25 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int HW, int DC, bool SSD>
 __global__ __launch_bounds__(256) void window_cost_weighted_kernel(WinArgs a, WinWeights ww) {
     const int SCALE = a.scale, HH = a.hh;
-    constexpr int TJ = kWinCostTileCols, RB = kWinCostBandRows;
-    constexpr int NC = TJ / (256 / DC);  // columns per group of DC lanes
-    constexpr int NH = NC / 2;           // output pairs (k, k + NH)
-    constexpr int NCA = NC + 2 * HW;     // taps of a staged row the group reads
-    constexpr int NG = NH + 2 * HW;      // tap pairs (c, c + NH)
-    constexpr int EW = 2 * HW + 1;       // e_w (weighted windows are odd)
-    constexpr int LC = win_l_cols(HW);
+    using Lane = WinLane<HW, DC, SSD>;
+    constexpr int RB = kWinCostBandRows, NC = Lane::NC, NCA = Lane::NCA;
+    constexpr int NH = NC / 2;       // output pairs (k, k + NH)
+    constexpr int NG = NH + 2 * HW;  // tap pairs (c, c + NH)
+    constexpr int EW = 2 * HW + 1;   // e_w (weighted windows are odd)
     constexpr int RC_MAX = win_r_cols(HW, 1, DC), NR_MAX = win_rows(kWinMax / 2);
     static_assert(RB % 2 == 0 && NC % 2 == 0, "two rows and two columns per step");
-    const int RC = win_r_cols(HW, SCALE, DC), NR = win_rows(HH);
-    __shared__ uint8_t sl[NR_MAX * LC];
+    __shared__ uint8_t sl[NR_MAX * Lane::LC];
     __shared__ uint8_t sr[NR_MAX * RC_MAX];
-    const int ntj = (a.W + TJ - 1) / TJ;
-    const int i0 = (bid_x() / ntj) * RB, j0 = (bid_x() % ntj) * TJ, d0 = bid_y() * DC;
-    const int t = tid_x();
-    const int s_hi = (d0 + DC - 1 + a.min_disp) / SCALE;
-    for (int idx = t; idx < NR * LC; idx += 256) {
-        const int r = idx / LC, c = idx - r * LC;
-        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = clampi(j0 - HW + c, 0, a.W - 1);
-        sl[idx] = a.left[(size_t)y * a.rpitch + (size_t)x * SCALE];
-    }
-    for (int idx = t; idx < NR * RC; idx += 256) {
-        const int r = idx / RC, c = idx - r * RC;
-        const int y = clampi(i0 - HH + r, 0, a.H - 1), x = win_r_col(j0, c, a.W, HW, s_hi);
-        sr[idx] = a.right[(size_t)y * a.rpitch + (size_t)x * SCALE];
-    }
-    __syncthreads();
-    const int c0 = (t / DC) * NC, d = d0 + t % DC;
-    const int s = (d + a.min_disp) / SCALE;
-    int ru[NCA];
-#pragma unroll
-    for (int c = 0; c < NCA; ++c) ru[c] = win_r_index(j0, c0 + c, a.W, HW, s_hi, s);
+    const WinTile t = win_tile<HW, DC>(a, SCALE);
+    stage_rows<HW>(a, t, SCALE, HH, sl, sr);
+    const Lane ln(a, t, SCALE, sl, sr);
+    const int i0 = t.i0, j0 = t.j0, c0 = ln.c0, d = ln.d;
     f32x2 g[NG];
     // staged row r's taps, as floats: g[c] = (tap c, tap c + NH)
     auto taps = [&](int r) {
         float f[NCA];
 #pragma unroll
-        for (int c = 0; c < NCA; ++c) {
-            const int v = (int)sl[r * LC + c0 + c] - (int)sr[r * RC + ru[c]];
-            f[c] = (float)(SSD ? v * v : (v < 0 ? -v : v));
-        }
+        for (int c = 0; c < NCA; ++c) f[c] = (float)ln.ad(r, c);
 #pragma unroll
         for (int c = 0; c < NG; ++c) g[c] = f32x2{f[c], f[c + NH]};
     };
@@ -262,29 +240,35 @@ __global__ __launch_bounds__(256) void window_cost_weighted_kernel(WinArgs a, Wi
     }
 }
 
-template <int HW, int DC>
-hipError_t launch_weighted_t(bool ssd, const WinArgs &a, const WinWeights &ww, hipStream_t st) {
+// One launch of `kernel` over the volume's tiles: a.W x a.H in tiles by bands, D / DC chunks
+template <int DC, typename... Extra>
+hipError_t launch_tiles(void (*kernel)(WinArgs, Extra...), hipStream_t st, const WinArgs &a, const Extra &...extra) {
     const long long ntj = (a.W + kWinCostTileCols - 1) / kWinCostTileCols;
     const long long nb = (a.H + kWinCostBandRows - 1) / kWinCostBandRows;
     if (ntj * nb > 0x7fffffffLL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(ntj * nb), (unsigned)(a.D / DC));
-    if (ssd)
-        hipLaunchKernelGGL((window_cost_weighted_kernel<HW, DC, true>), grid, dim3(256), 0, st, a, ww);
-    else
-        hipLaunchKernelGGL((window_cost_weighted_kernel<HW, DC, false>), grid, dim3(256), 0, st, a, ww);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, a, extra...);
     return hipGetLastError();
 }
 
-template <int DC>
-hipError_t launch_weighted(int hw, bool ssd, const WinArgs &a, const WinWeights &ww, hipStream_t st) {
+// f(the half width 0 .. 4 as a compile-time constant)
+template <typename F>
+hipError_t by_half_width(int hw, F &&f) {
     switch (hw) {
-    case 0: return launch_weighted_t<0, DC>(ssd, a, ww, st);
-    case 1: return launch_weighted_t<1, DC>(ssd, a, ww, st);
-    case 2: return launch_weighted_t<2, DC>(ssd, a, ww, st);
-    case 3: return launch_weighted_t<3, DC>(ssd, a, ww, st);
-    case 4: return launch_weighted_t<4, DC>(ssd, a, ww, st);
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
     }
     return hipErrorInvalidValue;
+}
+
+// the default window at SCALE: every constant at compile time
+template <int SCALE, int DC, bool SSD>
+hipError_t launch_default(const WinArgs &a, hipStream_t st) {
+    constexpr Window w = default_window(SCALE);
+    return launch_tiles<DC>(window_cost_kernel<w.hw(), DC, SSD, SCALE, w.hh(), w.eh, w.ew>, st, a);
 }
 
 }  // namespace
@@ -310,17 +294,29 @@ hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *righ
     a.rh = 1.0f / a.fh;
     a.fw = (float)win.ew;
     a.rw = 1.0f / a.fw;
-    const bool ssd = kind == kCostSsd;
-    if (win.weighted) {
-        WinWeights ww{};
+    WinWeights ww{};
+    if (win.weighted)
         for (int k = 0; k < win.eh * win.ew; ++k) ww.w[k] = weights[k];
-        return g.D == 32 ? launch_weighted<32>(win.hw(), ssd, a, ww, st) : launch_weighted<64>(win.hw(), ssd, a, ww, st);
-    }
     const Window def = default_window(g.scale);
-    if (win.eh != def.eh || win.ew != def.ew)
-        return g.D == 32 ? launch_window<32>(win.hw(), ssd, a, st) : launch_window<64>(win.hw(), ssd, a, st);
-    if (g.scale == 1) return g.D == 32 ? launch_default<1, 32>(ssd, a, st) : launch_default<1, 64>(ssd, a, st);
-    return g.D == 32 ? launch_default<2, 32>(ssd, a, st) : launch_default<2, 64>(ssd, a, st);
+    // DC and SSD as compile-time constants: the weighted kernel and any window but the default by
+    // the instantiation of its half width, the default window with every constant at compile time
+    auto launch = [&](auto DC_C, auto SSD_C) -> hipError_t {
+        constexpr int DC = DC_C;
+        constexpr bool SSD = SSD_C;
+        if (win.weighted)
+            return by_half_width(win.hw(), [&](auto HW) {
+                return launch_tiles<DC>(window_cost_weighted_kernel<HW, DC, SSD>, st, a, ww);
+            });
+        if (win.eh != def.eh || win.ew != def.ew)
+            return by_half_width(win.hw(), [&](auto HW) {
+                return launch_tiles<DC>(window_cost_kernel<HW, DC, SSD, 0, -1, 0, 0>, st, a);
+            });
+        return g.scale == 1 ? launch_default<1, DC, SSD>(a, st) : launch_default<2, DC, SSD>(a, st);
+    };
+    using DC32 = std::integral_constant<int, 32>;
+    using DC64 = std::integral_constant<int, 64>;
+    auto by_dc = [&](auto SSD_C) { return g.D == 32 ? launch(DC32{}, SSD_C) : launch(DC64{}, SSD_C); };
+    return kind == kCostSsd ? by_dc(std::true_type{}) : by_dc(std::false_type{});
 }
 
 }  // namespace sgm

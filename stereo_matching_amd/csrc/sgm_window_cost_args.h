@@ -82,14 +82,6 @@ constexpr const char *weighted_refusal(int win_h, int win_w, int scale) {
     return nullptr;
 }
 
-// Solver::build_dsi's default window (Solver.cpp:98-99): WIN_H / scale x WIN_W / scale.
-// SAD and SSD (cost.cpp:8,14) loop over -win/2 .. win/2 on either side, so at
-// scale 2 (3 x 4) they sum 3 x 5 taps and divide by 3 and 4.
-constexpr int win_cost_h(int scale) { return default_window(scale).eh; }
-constexpr int win_cost_w(int scale) { return default_window(scale).ew; }
-constexpr int win_cost_hh(int scale) { return default_window(scale).hh(); }
-constexpr int win_cost_hw(int scale) { return default_window(scale).hw(); }
-
 // The largest window sum: 63 taps of 255 (SAD) or 255^2 (SSD); exact in int32 and in fp32.
 constexpr int kWinCostMaxSum = 63 * 255 * 255;
 
@@ -108,7 +100,6 @@ inline float win_div(float x, int win) {
 
 // cost.cpp:29,58: cost / win_h / win_w, two divisions in that order.
 inline float win_cost_value(int sum, Window w) { return win_div(win_div((float)sum, w.eh), w.ew); }
-inline float win_cost_value(int sum, int scale) { return win_cost_value(sum, default_window(scale)); }
 
 // The kernel's tile: a workgroup writes kWinCostTileCols columns of
 // kWinCostBandRows rows for a chunk of DC disparities (64; 32 at D = 32).
@@ -139,16 +130,6 @@ constexpr int win_r_col(int j0, int u, int W, int hw, int s_hi) {
 // = 4576), of the 64 KiB a workgroup may take.
 constexpr int win_lds_bytes(Window w, int scale, int DC) {
     return win_rows(w.hh()) * (win_l_cols(w.hw()) + win_r_cols(w.hw(), scale, DC));
-}
-// the default window's, by scale
-constexpr int win_cost_l_cols(int scale) { return win_l_cols(win_cost_hw(scale)); }
-constexpr int win_cost_r_cols(int scale, int DC) { return win_r_cols(win_cost_hw(scale), scale, DC); }
-constexpr int win_cost_rows(int scale) { return win_rows(win_cost_hh(scale)); }
-constexpr int win_cost_r_index(int j0, int t, int W, int scale, int s_hi, int s) {
-    return win_r_index(j0, t, W, win_cost_hw(scale), s_hi, s);
-}
-constexpr int win_cost_r_col(int j0, int u, int W, int scale, int s_hi) {
-    return win_r_col(j0, u, W, win_cost_hw(scale), s_hi);
 }
 
 // The checks sgm_window_cost_device makes before it enqueues anything: the

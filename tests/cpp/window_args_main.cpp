@@ -128,13 +128,6 @@ int main() {
                             for (int m : {0, 16}) staged_columns(win, W, j0, DC, scale, m);
                     }
             }
-    // the default window's helpers are the general ones at (7, 9)
-    for (int scale : {1, 2}) {
-        const sgm::Window d = sgm::default_window(scale);
-        EXPECT(sgm::win_cost_l_cols(scale) == sgm::win_l_cols(d.hw()));
-        EXPECT(sgm::win_cost_r_cols(scale, 64) == sgm::win_r_cols(d.hw(), scale, 64));
-        EXPECT(sgm::win_cost_rows(scale) == sgm::win_rows(d.hh()));
-    }
     if (failures) return 1;
     printf("window args ok\n");
     return 0;

@@ -25,7 +25,8 @@ static bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof(a)) == 0;
 // every window sum 0 .. 63 * 255^2 through the first division, each of those
 // quotients through the second: the FMA form against IEEE division
 static void divisions(int scale) {
-    const int wh = sgm::win_cost_h(scale), ww = sgm::win_cost_w(scale);
+    const sgm::Window win = sgm::default_window(scale);
+    const int wh = win.eh, ww = win.ew;
     volatile float fh = (float)wh, fw = (float)ww;  // (no constant folding into a reciprocal)
     long bad1 = 0, bad2 = 0, bad = 0;
     for (int x = 0; x <= sgm::kWinCostMaxSum; ++x) {
@@ -33,7 +34,7 @@ static void divisions(int scale) {
         const float g = sgm::win_div((float)x, wh);
         if (!same_bits(q, g)) ++bad1;
         if (!same_bits(q / fw, sgm::win_div(q, ww))) ++bad2;
-        if (!same_bits((float)x / fh / fw, sgm::win_cost_value(x, scale))) ++bad;
+        if (!same_bits((float)x / fh / fw, sgm::win_cost_value(x, win))) ++bad;
     }
     if (bad1 || bad2 || bad)
         fprintf(stderr, "scale %d: %ld first, %ld second, %ld composed divisions differ\n", scale, bad1, bad2, bad);
@@ -43,18 +44,18 @@ static void divisions(int scale) {
 // Every tap of every tile of a W-column row: the staged index lies inside the
 // staged row and stands for the column cost.cpp:16-18 reads.
 static void staged_columns(int W, int D, int scale, int min_disp) {
-    const int DC = D == 32 ? 32 : 64, hw = sgm::win_cost_hw(scale);
-    const int lc = sgm::win_cost_l_cols(scale), rc = sgm::win_cost_r_cols(scale, DC);
+    const int DC = D == 32 ? 32 : 64, hw = sgm::default_window(scale).hw();
+    const int lc = sgm::win_l_cols(hw), rc = sgm::win_r_cols(hw, scale, DC);
     std::vector<int> staged((size_t)rc);
     long bad = 0;
     for (int j0 = 0; j0 < W; j0 += sgm::kWinCostTileCols)
         for (int d0 = 0; d0 < D; d0 += DC) {
             const int s_hi = (d0 + DC - 1 + min_disp) / scale;
-            for (int u = 0; u < rc; ++u) staged[(size_t)u] = sgm::win_cost_r_col(j0, u, W, scale, s_hi);
+            for (int u = 0; u < rc; ++u) staged[(size_t)u] = sgm::win_r_col(j0, u, W, hw, s_hi);
             for (int t = 0; t < lc; ++t)
                 for (int dd = 0; dd < DC; ++dd) {
                     const int s = (d0 + dd + min_disp) / scale;
-                    const int u = sgm::win_cost_r_index(j0, t, W, scale, s_hi, s);
+                    const int u = sgm::win_r_index(j0, t, W, hw, s_hi, s);
                     int xl = j0 - hw + t;
                     xl = xl < 0 ? 0 : xl > W - 1 ? W - 1 : xl;
                     const int xr = xl - s > 0 ? xl - s : 0;
@@ -67,12 +68,13 @@ static void staged_columns(int W, int D, int scale, int min_disp) {
 
 int main() {
     EXPECT(sgm::kCostCensus == SGM_COST_CENSUS && sgm::kCostSad == SGM_COST_SAD && sgm::kCostSsd == SGM_COST_SSD);
-    EXPECT(sgm::win_cost_h(1) == 7 && sgm::win_cost_w(1) == 9 && sgm::win_cost_h(2) == 3 && sgm::win_cost_w(2) == 4);
-    EXPECT(sgm::win_cost_hh(1) == 3 && sgm::win_cost_hw(1) == 4 && sgm::win_cost_hh(2) == 1 && sgm::win_cost_hw(2) == 2);
+    const sgm::Window w1 = sgm::default_window(1), w2 = sgm::default_window(2);
+    EXPECT(w1.eh == 7 && w1.ew == 9 && w2.eh == 3 && w2.ew == 4);
+    EXPECT(w1.hh() == 3 && w1.hw() == 4 && w2.hh() == 1 && w2.hw() == 2);
     EXPECT(sgm::kWinCostMaxSum == 4096575);
     divisions(1);
     divisions(2);
-    EXPECT(same_bits(sgm::win_cost_value(sgm::kWinCostMaxSum, 1), 65025.0f));
+    EXPECT(same_bits(sgm::win_cost_value(sgm::kWinCostMaxSum, w1), 65025.0f));
 
     const int widths[] = {5, 33, 40, 63, 64, 65, 170, 300};
     for (int W : widths)

@@ -88,7 +88,7 @@ def main() -> int:
                     res = run(exe, tmp, L, R, 0, s, *cases.effective(win, s), 0)
                     t = np.fromfile(res, np.uint64).reshape(2, *L.shape)
                     out["l_" + cases.wid(win)], out["r_" + cases.wid(win)] = t[0], t[1]
-                save(wt.census_fixture(shape, s), out)
+                save(cases.census_fixture(shape, s, "weighted"), out)
         for name, s, win in wt.COST_FIXTURES:
             left, right = cases.cost_pair(name, s)
             L, R = cases.working(left, s), cases.working(right, s)
@@ -96,7 +96,7 @@ def main() -> int:
             for k, kind in enumerate(cases.KINDS):
                 res = run(exe, tmp, L, R, cases.COST_DMAX, s, *cases.effective(win, s), k + 1)
                 out[kind] = np.fromfile(res, np.float32).reshape(*L.shape, cases.COST_DMAX)
-            save(wt.cost_fixture(name, s, win), out)
+            save(cases.cost_fixture(name, s, win, "weighted"), out)
     return 0
 
 

@@ -90,8 +90,10 @@ def expected(shape, paths=4):
 
 
 def bits(a):
+    """An array as what the bit-exact comparisons compare: floats as their float32 bit patterns,
+    everything else as int64."""
     a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.int64)
+    return a.astype(np.float32, copy=False).view(np.uint32) if a.dtype.kind == "f" else a.astype(np.int64)
 
 
 def assert_bits_equal(got, want, what):

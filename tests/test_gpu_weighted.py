@@ -14,6 +14,7 @@ import torch
 
 import weighted_recipe as wt
 import window_cases as cases
+import window_recipe as wr
 from stereo_matching_amd import BM, SGM, _capi, synthetic
 from stereo_matching_amd._capi import SGMError
 
@@ -39,7 +40,7 @@ def test_masked_census_equals_the_reference(case):
     h, w = left.shape
     with SGM(h, w, s, 32, views=1, blur=False, window=win, weighted=True) as sgm:
         assert sgm.weighted and sgm.window == win
-        for img, want in zip((left, right), wt.ref_census(shape, s, win)):
+        for img, want in zip((left, right), cases.ref_census(shape, s, win, "weighted")):
             assert np.array_equal(sgm.stage_census(img), want)
 
 
@@ -49,7 +50,7 @@ def test_blurred_masked_census_equals_the_recipe(case):
     left, _ = cases.census_pair(shape, s)
     h, w = left.shape
     with SGM(h, w, s, 32, views=1, blur=True, window=win, weighted=True) as sgm:
-        assert np.array_equal(sgm.stage_census(left), wt.frame_census(left, win, s, blur=True))
+        assert np.array_equal(sgm.stage_census(left), wr.frame_census(left, win, s, blur=True, weighted=True))
 
 
 # ------------------------------------------------------- weighted producer
@@ -70,7 +71,7 @@ def test_weighted_window_cost_equals_the_recipe(case):
                 for kind in cases.KINDS:
                     got = sgm.stage_window_cost(left, right, kind)
                     want = wt.volume(left, right, D, kind, win, s, m)
-                    assert np.array_equal(wt.bits(got), wt.bits(want)), (D, m, kind)
+                    assert np.array_equal(wr.bits(got), wr.bits(want)), (D, m, kind)
 
 
 @pytest.mark.parametrize("case", wt.COST_FIXTURES, ids=lambda c: f"{c[0]}_s{c[1]}_{cases.wid(c[2])}")
@@ -80,8 +81,8 @@ def test_weighted_window_cost_equals_the_reference(case):
     h, w = left.shape
     with SGM(h, w, s, 64, aux_only=True, min_disp=16, window=win, weighted=True) as sgm:
         for kind in cases.KINDS:
-            want = np.ascontiguousarray(wt.ref_cost(name, s, win, kind)[:, :, 16:80])
-            assert np.array_equal(wt.bits(sgm.stage_window_cost(left, right, kind)), wt.bits(want)), kind
+            want = np.ascontiguousarray(cases.ref_cost(name, s, win, kind, "weighted")[:, :, 16:80])
+            assert np.array_equal(wr.bits(sgm.stage_window_cost(left, right, kind)), wr.bits(want)), kind
 
 
 @pytest.mark.parametrize("kind", cases.KINDS)
@@ -89,7 +90,7 @@ def test_a_second_disparity_chunk(kind):
     left, right = cases.cost_pair("20x70", 1)
     with SGM(20, 70, 1, 128, aux_only=True, weighted=True) as sgm:  # (7, 9): 63 taps, shifts up to 127
         got = sgm.stage_window_cost(left, right, kind)
-    assert np.array_equal(wt.bits(got), wt.bits(wt.volume(left, right, 128, kind, (7, 9))))
+    assert np.array_equal(wr.bits(got), wr.bits(wt.volume(left, right, 128, kind, (7, 9))))
 
 
 def test_window_cost_on_device_tensors_of_an_aux_only_handle():
@@ -97,8 +98,8 @@ def test_window_cost_on_device_tensors_of_an_aux_only_handle():
     with SGM(20, 70, 1, 64, aux_only=True, weighted=True) as sgm:
         got = sgm.window_cost(torch.from_numpy(left).to(DEV), torch.from_numpy(right).to(DEV), "sad")
         torch.cuda.synchronize(DEV)
-    want = np.ascontiguousarray(wt.ref_cost("20x70", 1, (7, 9), "sad")[:, :, :64])
-    assert np.array_equal(wt.bits(got.cpu().numpy()), wt.bits(want))
+    want = np.ascontiguousarray(cases.ref_cost("20x70", 1, (7, 9), "sad", "weighted")[:, :, :64])
+    assert np.array_equal(wr.bits(got.cpu().numpy()), wr.bits(want))
 
 
 def test_window_weights_are_the_recorded_table():
@@ -123,16 +124,16 @@ def pair(index=2):
 @functools.lru_cache(maxsize=None)
 def expected(views=2, paths=8, cost="census", solver="sgm", filters=(False, False), index=2):
     left, right = pair(index)
-    out = wt.recipe(left, right, D, (7, 9), 1, paths, 0, True, views, cost, solver, filters)
+    out = wr.recipe(left, right, D, (7, 9), 1, None, paths, 0, True, views, cost, solver, True, filters)
     for a in out.values():
         a.setflags(write=False)
     return out
 
 
 def check_frame(sgm, want, views):
-    wt.assert_bits_equal(sgm.get_raw_disp(), want["disp"], "disp")
-    wt.assert_bits_equal(sgm.get_lr_disp(), want["lr"] if views == 2 else want["sub"], "sub")
-    wt.assert_bits_equal(sgm.get_disp(), want["final"], "final")
+    wr.assert_bits_equal(sgm.get_raw_disp(), want["disp"], "disp")
+    wr.assert_bits_equal(sgm.get_lr_disp(), want["lr"] if views == 2 else want["sub"], "sub")
+    wr.assert_bits_equal(sgm.get_disp(), want["final"], "final")
 
 
 @pytest.mark.parametrize("paths", [8, 4])
@@ -168,7 +169,7 @@ def check_volume_frame(kind, **kw):
         got = frame_maps(sgm, lambda out, raw: sgm.process_device(dl.data_ptr(), dr.data_ptr(), out.data_ptr(),
                                                                   d_raw=raw.data_ptr()))
     for k in want:
-        assert np.array_equal(wt.bits(got[k]), wt.bits(want[k])), k
+        assert np.array_equal(wr.bits(got[k]), wr.bits(want[k])), k
     assert not (want["out"] == -77.0).all()
     return got
 
@@ -178,12 +179,12 @@ def check_volume_frame(kind, **kw):
 def test_sad_frame_equals_the_weighted_volume_through_aggregate(views, paths):
     got = check_volume_frame("sad", views=views, paths=paths)
     if views == 2:  # and the CPU oracle's stages on the same volume
-        wt.assert_bits_equal(got["out"], expected(2, paths, "sad")["lr"], "lr")
+        wr.assert_bits_equal(got["out"], expected(2, paths, "sad")["lr"], "lr")
 
 
 def test_ssd_frame_with_the_cost_filters():
     got = check_volume_frame("ssd", volume_filter=(True, True))
-    wt.assert_bits_equal(got["out"], expected(2, 8, "ssd", filters=(True, True))["lr"], "lr")
+    wr.assert_bits_equal(got["out"], expected(2, 8, "ssd", filters=(True, True))["lr"], "lr")
 
 
 def test_bm_frame():
@@ -192,8 +193,8 @@ def test_bm_frame():
     with BM(H, W, 1, D, weighted=True) as bm:
         assert bm.weighted
         bm.process(left, right)
-        wt.assert_bits_equal(bm.get_raw_disp(), want["disp"], "disp")
-        wt.assert_bits_equal(bm.get_disp(), want["final"], "final")
+        wr.assert_bits_equal(bm.get_raw_disp(), want["disp"], "disp")
+        wr.assert_bits_equal(bm.get_disp(), want["final"], "final")
 
 
 def test_right_view_handle_takes_the_setting():
@@ -213,7 +214,7 @@ def test_set_and_cleared_again_is_an_untouched_handle():
         fresh.process(left, right)
         sgm.process(left, right)
         for get in ("get_raw_disp", "get_lr_disp", "get_disp"):
-            wt.assert_bits_equal(getattr(sgm, get)(), getattr(fresh, get)(), get)
+            wr.assert_bits_equal(getattr(sgm, get)(), getattr(fresh, get)(), get)
         sgm.set_weighted(True)
         sgm.process(left, right)
         check_frame(sgm, expected(), 2)
@@ -296,8 +297,8 @@ def test_weighted_frame_replays_from_a_hip_graph():
                 graph.replay()
                 frame(out_e)
             torch.cuda.synchronize(DEV)
-            assert np.array_equal(wt.bits(out_g.cpu().numpy()), wt.bits(out_e.cpu().numpy())), k
-        wt.assert_bits_equal(out_g.cpu().numpy(), expected()["lr"], "replay")
+            assert np.array_equal(wr.bits(out_g.cpu().numpy()), wr.bits(out_e.cpu().numpy())), k
+        wr.assert_bits_equal(out_g.cpu().numpy(), expected()["lr"], "replay")
 
 
 # ---------------------------------------------------------------- launches

@@ -26,8 +26,8 @@ CENSUS_CASES = [(shape, s, win) for s in (1, 2) for shape in wt.CENSUS_SHAPES fo
 def test_masked_census_equals_the_reference(case):
     shape, s, win = case
     left, right = cases.census_pair(shape, s)
-    for img, want in zip((left, right), wt.ref_census(shape, s, win)):
-        assert np.array_equal(wt.census(cases.working(img, s), *cases.effective(win, s)), want)
+    for img, want in zip((left, right), cases.ref_census(shape, s, win, "weighted")):
+        assert np.array_equal(wr.census(cases.working(img, s), *cases.effective(win, s), weighted=True), want)
 
 
 @pytest.mark.parametrize("case", wt.COST_FIXTURES, ids=lambda c: f"{c[0]}_s{c[1]}_{cases.wid(c[2])}")
@@ -36,32 +36,32 @@ def test_weighted_volume_equals_the_reference(case, kind):
     name, s, win = case
     left, right = cases.cost_pair(name, s)
     got = wt.volume(left, right, cases.COST_DMAX, kind, win, s)
-    want = wt.ref_cost(name, s, win, kind)
-    assert got.dtype == np.float32 and np.array_equal(wt.bits(got), wt.bits(want))
+    want = cases.ref_cost(name, s, win, kind, "weighted")
+    assert got.dtype == np.float32 and np.array_equal(wr.bits(got), wr.bits(want))
 
 
 def test_a_min_disp_case_is_a_slice_of_the_fixture():
     left, right = cases.cost_pair("24x33", 2)
     got = wt.volume(left, right, 64, "sad", (14, 18), 2, min_disp=16)
-    want = np.ascontiguousarray(wt.ref_cost("24x33", 2, (14, 18), "sad")[:, :, 16:80])
-    assert np.array_equal(wt.bits(got), wt.bits(want))
+    want = np.ascontiguousarray(cases.ref_cost("24x33", 2, (14, 18), "sad", "weighted")[:, :, 16:80])
+    assert np.array_equal(wr.bits(got), wr.bits(want))
 
 
 @pytest.mark.parametrize("win", wt.COST_WINDOWS[1], ids=cases.wid)
 def test_weighting_off_is_the_unweighted_recipe(win):
     left, right = cases.cost_pair("24x33", 1)
     L, R = cases.working(left, 1), cases.working(right, 1)
-    assert np.array_equal(wt.census(L, *win, weighted=False), wr.census(L, *win))
+    assert np.array_equal(wr.census(L, *win, weighted=False), wr.census(L, *win))
     for kind in cases.KINDS:
         got = wt.window_volume(L, R, 40, kind, *win, 1, 16, weighted=False)
-        assert np.array_equal(wt.bits(got), wt.bits(wr.window_volume(L, R, 40, kind, *win, 1, 16)))
+        assert np.array_equal(wr.bits(got), wr.bits(wr.window_volume(L, R, 40, kind, *win, 1, 16)))
 
 
 def test_weighting_off_is_the_literal_window_cost():
     left, right = cases.cost_pair("3x5", 1)
     for kind in cases.KINDS:
         got = wt.window_volume(left, right, 8, kind, 7, 9, 1, 0, weighted=False)
-        assert np.array_equal(wt.bits(got), wt.bits(wc.build_dsi(left, right, 8, kind)))
+        assert np.array_equal(wr.bits(got), wr.bits(wc.build_dsi(left, right, 8, kind)))
 
 
 def test_weighting_changes_the_widest_windows_and_only_those():
@@ -69,13 +69,13 @@ def test_weighting_changes_the_widest_windows_and_only_those():
     for win, bits in wt.KEPT_BITS.items():
         full = win[0] * win[1] - 1
         assert int(wt.kept(*win).sum()) == bits <= full
-        same = np.array_equal(wt.census(left, *win), wt.census(left, *win, weighted=False))
+        same = np.array_equal(wr.census(left, *win, weighted=True), wr.census(left, *win, weighted=False))
         assert same == (bits == full), win
         # the disc of the issue, da^2 + db^2 <= 17
         a, b = np.meshgrid(np.arange(win[0]) - win[0] // 2, np.arange(win[1]) - win[1] // 2, indexing="ij")
         assert np.array_equal(wt.kept(*win), (a * a + b * b <= 17) & ((a != 0) | (b != 0)))
         # a masked word never carries more bits than it keeps
-        assert int(wt.census(left, *win).max()) < 1 << bits
+        assert int(wr.census(left, *win, weighted=True).max()) < 1 << bits
 
 
 def test_weight_table_equals_the_recorded_one():

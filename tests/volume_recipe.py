@@ -19,7 +19,7 @@ import numpy as np
 
 import oracle
 from confidence_recipe import ratio_of
-from paths4_recipe import aggregate as aggregate4, census
+from paths4_recipe import aggregate as aggregate4, bits, census  # noqa: F401
 from stereo_matching_amd import synthetic
 
 
@@ -148,5 +148,3 @@ def source(C, layout, dtype, variant):
     return store, off, (sr, sc, sd)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)

@@ -3,17 +3,17 @@ cost functions with WEIGHTED_COST on, restated literally.
 
   weights(e_h, e_w)      Solver::Solver's Gaussian table (Solver.cpp:29-45)
   refusal(window, s)     the rule of sgm_set_weighted / sgm_set_window on a weighted handle
-  census(img, e_h, e_w)  CT_pts (cost.cpp:99-129): taps of weight < 0.5 skipped
+  kept(e_h, e_w)         the taps CT_pts (cost.cpp:99-129) keeps: weight >= 0.5
   window_volume(...)     Solver::build_dsi over SAD / SSD (cost.cpp:4-59): the taps in the
                          reference's order (rows outer, columns inner), cost = cost + AD * w in
                          fp32 (numpy multiplies, rounds, then adds: no FMA), two fp32 divisions
-  recipe(...)            whole frames, composed from the oracle's stages as
-                         tests/window_recipe.py composes them
 
-and the case lists of the tests and of tests/golden/make_ref_weighted_golden.py,
+(the masked census and whole frames are tests/window_recipe.py's census, frame_census and
+recipe with weighted=True) and the case lists of the tests and of tests/golden/make_ref_weighted_golden.py,
 which writes the fixtures under tests/golden/weighted/ with the reference's own
 compiled functions; tests/test_weighted_cpu.py pins everything here to them.
-The images and shapes are tests/window_cases.py's.
+The images, the shapes and the fixture loaders (family="weighted") are
+tests/window_cases.py's.
 
 TEST INFRASTRUCTURE ONLY.
 """
@@ -25,16 +25,9 @@ import os
 
 import numpy as np
 
-import oracle
-import volume_filter_recipe
-import volume_recipe
-import window_cases as cases
-import window_recipe as wr
-from min_disp_recipe import shift_tables
-from paths4_recipe import aggregate, assert_bits_equal, cost_volume  # noqa: F401
-from window_cases import effective, wid, working  # noqa: F401
+from window_cases import GOLDEN, effective, working
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "weighted")
+GOLDEN_DIR = os.path.join(GOLDEN, "weighted")
 
 # ------------------------------------------------------------------- cases
 # windows as sgm_set_window takes them, by scale; every effective side odd
@@ -64,14 +57,6 @@ RULE = [
 ]
 
 
-def census_fixture(shape, s):
-    return os.path.join(GOLDEN_DIR, f"ref_weighted_ct_{shape[0]}x{shape[1]}_s{s}.npz")
-
-
-def cost_fixture(name, s, window):
-    return os.path.join(GOLDEN_DIR, f"ref_weighted_ad_{name}_s{s}_{wid(window)}.npz")
-
-
 WEIGHTS_FIXTURE = os.path.join(GOLDEN_DIR, "ref_weighted_weights.npz")
 
 
@@ -83,23 +68,6 @@ def weight_windows():
             if effective(w, s) not in out:
                 out.append(effective(w, s))
     return out
-
-
-@functools.lru_cache(maxsize=None)
-def ref_census(shape, s, window):
-    with np.load(census_fixture(shape, s)) as z:
-        out = z["l_" + wid(window)], z["r_" + wid(window)]
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def ref_cost(name, s, window, kind):
-    with np.load(cost_fixture(name, s, window)) as z:
-        v = z[kind]
-    v.setflags(write=False)
-    return v
 
 
 # ------------------------------------------------------------------ recipe
@@ -142,35 +110,6 @@ def kept(e_h, e_w, weighted=True):
     return k
 
 
-def census(img, e_h, e_w, weighted=True):
-    """CT_pts over a working-grid image with WEIGHTED_COST as given: the loops of cost.cpp:107-122;
-    a skipped tap shifts nothing."""
-    assert e_h % 2 == 1 and e_w % 2 == 1
-    H, W = img.shape
-    hh, hw = e_h // 2, e_w // 2
-    keep = kept(e_h, e_w, weighted)
-    out = np.zeros((H, W), np.uint64)
-    rows, cols = np.arange(H), np.arange(W)
-    for i in range(-hh, hh + 1):
-        y = np.minimum(np.maximum(rows + i, 0), H - 1)
-        for j in range(-hw, hw + 1):
-            if not keep[i + hh, j + hw]:
-                continue
-            x = np.minimum(np.maximum(cols + j, 0), W - 1)
-            out = (out << np.uint64(1)) | (img[y][:, x] > img).astype(np.uint64)
-    return out
-
-
-def frame_census(img, window, s, blur=True, bm_rows=False, weighted=True):
-    """The table a frame of a weighted handle builds of a full-size image (window_recipe's, masked)."""
-    if bm_rows:
-        h, w = img.shape
-        g = np.ascontiguousarray(img[:h // s, :(w // s) * s:s])
-    else:
-        g = working(img, s)
-    return census(oracle.blur(g) if blur else g, *effective(window, s), weighted=weighted)
-
-
 def window_volume(L, R, D, kind, e_h, e_w, s=1, min_disp=0, weighted=True):
     """Solver::build_dsi over SAD or SSD on working-grid images, tap by tap in the reference's
     order for every (row, column, d) at once: cost starts at 0.0f, each tap adds
@@ -202,40 +141,3 @@ def volume(left, right, D, kind, window, s=1, min_disp=0, weighted=True):
     """The left cost volume of two full-size grey images, as a weighted frame or window_cost builds it."""
     return window_volume(working(left, s), working(right, s), D, kind, *effective(window, s), s, min_disp,
                          weighted)
-
-
-def recipe(left, right, D, window=(7, 9), s=1, paths=8, m=0, blur=True, views=2, cost="census", solver="sgm",
-           filters=(False, False)):
-    """The maps of a frame on a weighted handle, oracle.process's keys (window_recipe.recipe with
-    the masked tables or the weighted volume in the place of its own)."""
-    if cost != "census":
-        C = volume(left, right, D, cost, window, s, m)
-        if any(filters):
-            return volume_filter_recipe.recipe(C, m, s, paths, (1 if filters[0] else 0) | (2 if filters[1] else 0))
-        return volume_recipe.recipe(C, m, s, paths)
-    if solver == "bm":
-        ctl, ctr = (frame_census(x, window, s, blur, bm_rows=True) for x in (left, right))
-        d = wr.bm_wta(cost_volume(ctl, ctr, D, s, 0, None))
-        return {"disp": d, "final": oracle.post_filter(d.astype(np.float32), D, s)}
-    ctl, ctr = frame_census(left, window, s, blur), frame_census(right, window, s, blur)
-    ctl_s, ctr_s = shift_tables(ctl, ctr, m // s)
-    out = {}
-    vols = [cost_volume(ctl, ctr_s, D, s, 0, None)]
-    if views == 2:
-        vols.append(cost_volume(ctl_s, ctr, D, s, 1, None))
-    for C, sfx in zip(vols, ("", "_beta")):
-        S = aggregate(C, paths)
-        d = oracle.wta(S)
-        out["disp" + sfx] = d + m
-        out["sub" + sfx] = (oracle.subpixel(d, S) + np.float32(m)).astype(np.float32)
-    if views == 2:
-        out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
-        out["final"] = oracle.post_filter(out["lr"], D + m, s)
-    else:
-        out["final"] = oracle.post_filter(out["sub"], D + m, s)
-    return out
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a

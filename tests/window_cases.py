@@ -14,8 +14,10 @@ import os
 
 import numpy as np
 
-# (a directory of their own: tests/test_reference_parity.py bounds the files of tests/golden itself)
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "window")
+# (directories of their own: tests/test_reference_parity.py bounds the files of tests/golden itself)
+# family "window": the plain windows' fixtures; "weighted": tests/weighted_recipe.py's
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_DIR = os.path.join(GOLDEN, "window")
 
 # ------------------------------------------------------------------ census
 # working-grid shapes around the census kernel's 64 x 16 tile (four waves of four rows)
@@ -91,18 +93,18 @@ def cost_fixture_cases():
     return out + [(name, 2, win) for name in COST_S2_SHAPES for win in COST_WINDOWS[2]]
 
 
-def census_fixture(shape, s):
-    return os.path.join(GOLDEN_DIR, f"ref_window_ct_{shape[0]}x{shape[1]}_s{s}.npz")
+def census_fixture(shape, s, family="window"):
+    return os.path.join(GOLDEN, family, f"ref_{family}_ct_{shape[0]}x{shape[1]}_s{s}.npz")
 
 
-def cost_fixture(name, s, window):
-    return os.path.join(GOLDEN_DIR, f"ref_window_ad_{name}_s{s}_{wid(window)}.npz")
+def cost_fixture(name, s, window, family="window"):
+    return os.path.join(GOLDEN, family, f"ref_{family}_ad_{name}_s{s}_{wid(window)}.npz")
 
 
 @functools.lru_cache(maxsize=None)
-def ref_census(shape, s, window):
+def ref_census(shape, s, window, family="window"):
     """(table of the left image, of the right image) by the reference's CT_pts; read-only."""
-    with np.load(census_fixture(shape, s)) as z:
+    with np.load(census_fixture(shape, s, family)) as z:
         out = z["l_" + wid(window)], z["r_" + wid(window)]
     for a in out:
         a.setflags(write=False)
@@ -110,9 +112,9 @@ def ref_census(shape, s, window):
 
 
 @functools.lru_cache(maxsize=None)
-def ref_cost(name, s, window, kind):
+def ref_cost(name, s, window, kind, family="window"):
     """The reference's SAD or SSD volume over disparities 0 .. COST_DMAX - 1; read-only."""
-    with np.load(cost_fixture(name, s, window)) as z:
+    with np.load(cost_fixture(name, s, window, family)) as z:
         v = z[kind]
     v.setflags(write=False)
     return v

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from paths4_recipe import bits  # noqa: F401
 from volume_recipe import derive_right  # noqa: F401  (the right view's volume of a left one)
 
 KINDS = ("sad", "ssd")
@@ -80,5 +81,3 @@ def volume(left, right, D, kind, scale=1, min_disp=0):
     return build_dsi_separable(working(left, scale), working(right, scale), D, kind, scale, min_disp)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)

@@ -13,43 +13,48 @@ from __future__ import annotations
 import numpy as np
 
 import oracle
+import volume_filter_recipe
 import volume_recipe
+import weighted_recipe
 import window_cost_recipe as wc
 from min_disp_recipe import shift_tables
-from paths4_recipe import aggregate, assert_bits_equal, cost_volume  # noqa: F401
+from paths4_recipe import aggregate, assert_bits_equal, bits, cost_volume  # noqa: F401
 from window_cases import effective, working  # noqa: F401
 
 DEFAULT = (7, 9)
 
 
-def census(img, e_h, e_w):
-    """CT_pts over a working-grid image: rows -e_h/2 .. e_h/2, columns -e_w/2 .. e_w/2 in
-    row-major order, the centre skipped, value = (value << 1) | (neighbour > centre) in a
-    64-bit word, coordinates clamped to the image."""
+def census(img, e_h, e_w, weighted=False):
+    """CT_pts over a working-grid image (cost.cpp:107-122): rows -e_h/2 .. e_h/2, columns
+    -e_w/2 .. e_w/2 in row-major order, the centre skipped, value = (value << 1) |
+    (neighbour > centre) in a 64-bit word, coordinates clamped to the image.  weighted:
+    WEIGHTED_COST on, the taps of weight < 0.5 skipped too; a skipped tap shifts nothing."""
     H, W = img.shape
     hh, hw = e_h // 2, e_w // 2
     assert (2 * hh + 1) * (2 * hw + 1) - 1 <= 64
+    assert not weighted or (e_h % 2 == 1 and e_w % 2 == 1)
+    keep = weighted_recipe.kept(2 * hh + 1, 2 * hw + 1, weighted)
     out = np.zeros((H, W), np.uint64)
     rows, cols = np.arange(H), np.arange(W)
     for i in range(-hh, hh + 1):
         y = np.minimum(np.maximum(rows + i, 0), H - 1)
         for j in range(-hw, hw + 1):
-            if i == 0 and j == 0:
+            if not keep[i + hh, j + hw]:
                 continue
             x = np.minimum(np.maximum(cols + j, 0), W - 1)
             out = (out << np.uint64(1)) | (img[y][:, x] > img).astype(np.uint64)
     return out
 
 
-def frame_census(img, window, s, blur=True, bm_rows=False):
+def frame_census(img, window, s, blur=True, bm_rows=False, weighted=False):
     """The table a frame builds of a full-size image: decimated (BM: the columns only,
-    BM.cpp:24-25), blurred, then CT_pts over the window at this scale."""
+    BM.cpp:24-25), blurred, then CT_pts over the window at this scale (weighted: masked)."""
     if bm_rows:
         h, w = img.shape
         g = np.ascontiguousarray(img[:h // s, :(w // s) * s:s])
     else:
         g = working(img, s)
-    return census(oracle.blur(g) if blur else g, *effective(window, s))
+    return census(oracle.blur(g) if blur else g, *effective(window, s), weighted)
 
 
 def window_volume(L, R, D, kind, e_h, e_w, s=1, min_disp=0):
@@ -115,18 +120,23 @@ def bm_wta(cost, uniq=0.7):
 
 
 def recipe(left, right, D, window=DEFAULT, s=1, sky=None, paths=8, m=0, blur=True, views=2, cost="census",
-           solver="sgm"):
+           solver="sgm", weighted=False, filters=(False, False)):
     """The maps of a frame on a handle with sgm_set_window(window): oracle.process's keys, in
     true disparity (min_disp m).  cost "sad" | "ssd": the window cost volume through
-    tests/volume_recipe.py (no cost filters).  solver "bm": "disp" (BM's raw
-    winner-take-all) and "final" (its post_filter) only."""
+    tests/volume_recipe.py, with `filters` (horizontal, vertical) through
+    tests/volume_filter_recipe.py (5q).  solver "bm": "disp" (BM's raw winner-take-all) and
+    "final" (its post_filter) only.  weighted: sgm_set_weighted's masked tables or weighted
+    volume (tests/weighted_recipe.py) in the place of the plain ones."""
     if cost != "census":
-        return volume_recipe.recipe(volume(left, right, D, cost, window, s, m), m, s, paths)
+        C = (weighted_recipe.volume if weighted else volume)(left, right, D, cost, window, s, m)
+        if any(filters):
+            return volume_filter_recipe.recipe(C, m, s, paths, (1 if filters[0] else 0) | (2 if filters[1] else 0))
+        return volume_recipe.recipe(C, m, s, paths)
     if solver == "bm":
-        ctl, ctr = (frame_census(x, window, s, blur, bm_rows=True) for x in (left, right))
+        ctl, ctr = (frame_census(x, window, s, blur, True, weighted) for x in (left, right))
         d = bm_wta(cost_volume(ctl, ctr, D, s, 0, sky))
         return {"disp": d, "final": oracle.post_filter(d.astype(np.float32), D, s)}
-    ctl, ctr = frame_census(left, window, s, blur), frame_census(right, window, s, blur)
+    ctl, ctr = (frame_census(x, window, s, blur, False, weighted) for x in (left, right))
     ctl_s, ctr_s = shift_tables(ctl, ctr, m // s)
     out = {}
     vols = [cost_volume(ctl, ctr_s, D, s, 0, sky)]
@@ -143,8 +153,3 @@ def recipe(left, right, D, window=DEFAULT, s=1, sky=None, paths=8, m=0, blur=Tru
     else:
         out["final"] = oracle.post_filter(out["sub"], D + m, s)
     return out
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
