@@ -38,8 +38,9 @@
  *   aggregate_device(vol, ...)   (not in the reference) a caller's DEVICE cost volume through the
  *                                path aggregation, the LR check and post_filter (sgm_aggregate_device);
  *                                import_volume_device(vol, view, dst) is its first launch alone
- *   set_cost(kind), cost()       Solver.cpp:96-117 over cost.cpp:4-59: frames match on the SAD or
- *                                SSD window cost instead of the census (sgm_set_cost);
+ *   set_cost(kind), cost()       Solver.cpp:96-117 over cost.cpp:4-96: frames match on the SAD or
+ *                                SSD window cost, or on CT (SGM_COST_CT, build_dsi's own
+ *                                per-disparity census), instead of the census (sgm_set_cost);
  *                                window_cost_device(kind, l, r, pitch, dst) is that volume alone
  *   set_volume_filter(bits)      Solver.cpp:296-368 on each view's volume of every volume frame
  *                                (sgm_set_volume_filter); filter_volume_device(d_cost, bits) is
@@ -414,8 +415,9 @@ public:
     }
 
     // The matching cost of every later frame (sgm_set_cost): SGM_COST_CENSUS
-    // (the default), or the reference's SAD / SSD window cost (Solver::build_dsi
-    // over cost.cpp:4-59: no blur, no cost filters; sky masks are then refused).
+    // (the default), or the reference's SAD / SSD window cost or its CT, SGM_COST_CT
+    // (Solver::build_dsi over cost.cpp:4-96: no blur, no cost filters; sky masks are
+    // then refused).
     void set_cost(int kind) {
         if (sgm_set_cost(handle_, kind) != SGM_OK) fail("set_cost", sgm_last_error(handle_));
     }
@@ -455,7 +457,7 @@ public:
         if (sgm_get_window_weights(handle_, w.data(), n, &n) != SGM_OK) fail("window_weights", sgm_last_error(handle_));
         return w;
     }
-    // The SAD / SSD volume alone (sgm_window_cost_device): DEVICE grey images of
+    // The SAD / SSD / CT volume alone (sgm_window_cost_device): DEVICE grey images of
     // the constructed size, `pitch` bytes per row, into the dense fp32 rows x
     // cols x D volume d_dst, which aggregate_device takes.  Enqueue only.
     void window_cost_device(int kind, const uint8_t *d_left, const uint8_t *d_right, int pitch, float *d_dst,

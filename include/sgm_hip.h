@@ -588,7 +588,7 @@ int sgm_volume_import_device(sgm_handle *h, const sgm_volume *vol, int view, flo
 int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int out_pitch,
                          uint16_t *d_raw, void *stream);
 
-/* ---- the matching cost of a frame: census, or a SAD / SSD window ----
+/* ---- the matching cost of a frame: census, or a SAD / SSD / CT window ----
  *
  * The reference's second way to build the disparity space image,
  * Solver::build_dsi (Solver.cpp:96-117) over the window costs SAD and SSD
@@ -605,14 +605,32 @@ int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int
  * divide by 3 and 4, as the reference's do.  The largest cost is 65025.
  * WEIGHTED_COST (0 in the reference, inc/Solver.h:15) is the handle setting
  * sgm_set_weighted below; an ensemble with the census (no formula in the
- * reference) is not built. */
-enum { SGM_COST_CENSUS = 0, SGM_COST_SAD = 1, SGM_COST_SSD = 2 };
+ * reference) is not built.
+ *
+ * SGM_COST_CT is CT (cost.cpp:62-96), the function build_dsi
+ * actually calls (Solver.cpp:110): a census per pixel and per disparity on the
+ * same unblurred images and the same window.  With disp = d + min_disp and
+ * k = disp / scale (integer division):
+ *   cl = L[i][j],  cr = R[i][max(j - disp, 0)]        (disp, not k: cost.cpp:69 as written)
+ *   C_L[i][j][d] = the number of taps (a, b) != (0, 0) -- on a weighted handle
+ *                  only those of sgm_set_weighted's disc -- with
+ *                  y = clamp(i + a, 0, rows - 1), x_l = clamp(j + b, 0, cols - 1),
+ *                  x_r = x_l - k >= 0 (a tap with x_r < 0 is skipped, not clamped)
+ *                  at which (L[y][x_l] > cl) != (R[y][x_r] > cr)
+ * an integer in [0, 62], stored as a float.  It is not the Hamming distance of
+ * two census tables: the right window follows the left one's clamped columns,
+ * taps off the left edge are skipped and the right centre is clamped on its own.
+ * At scale 2 the centre column uses disp while the taps use disp / 2; that is
+ * the reference's text, reproduced as it stands: the volume is what its
+ * compiled CT returns with `scale` passed (build_dsi itself passes none).
+ * The value 3 is no kind and stays refused. */
+enum { SGM_COST_CENSUS = 0, SGM_COST_SAD = 1, SGM_COST_SSD = 2, SGM_COST_CT = 4 };
 
 /* The cost every later frame of the handle matches on.  SGM_COST_CENSUS is
  * every handle's default and runs exactly as before.  A property of the handle
  * (like sgm_set_min_disp; sgm_params and SGM_HIP_VERSION are unchanged); it
  * allocates nothing and waits for nothing; re-capture graphs afterwards.
- * A frame on a SAD or SSD handle runs its input slot as before, then one launch
+ * A frame on a SAD, SSD or CT handle runs its input slot as before, then one launch
  * writes C_L into the handle's left cost buffer; with views == 2 the right
  * view's volume is derived from it by sgm_volume_import_device's rule,
  *   C_R[i, j, d] = C_L[i, min(j + (d + min_disp) / scale, cols - 1), d];
@@ -626,7 +644,7 @@ enum { SGM_COST_CENSUS = 0, SGM_COST_SAD = 1, SGM_COST_SSD = 2 };
  * SGM::process with build_dsi() in the place of the census DSI (SGM.cpp:66-72).
  * Sky masks have no meaning in build_dsi, so a frame call with a non-NULL mask
  * on such a handle returns SGM_ERR_INVALID_ARG.
- * SGM_ERR_INVALID_ARG, with a message, for a kind that is none of the three,
+ * SGM_ERR_INVALID_ARG, with a message, for a kind that is none of the four,
  * and for BM, aux_only, SGM_VIEW_RIGHT and sky_detect handles. */
 int sgm_set_cost(sgm_handle *h, int kind);
 int sgm_get_cost(const sgm_handle *h, int *kind);
@@ -635,12 +653,12 @@ int sgm_get_cost(const sgm_handle *h, int *kind);
  * two grey images, into d_dst, DEVICE memory.  d_left and d_right are the
  * images sgm_process_device takes on a handle with no input stage set: height x
  * width bytes, `pitch` bytes per row, read decimated by scale; the handle's
- * min_disp is the one used.  kind is SGM_COST_SAD or SGM_COST_SSD, whatever
- * sgm_set_cost says.  One launch on `stream` (NULL = the handle's stream), no
+ * min_disp is the one used.  kind is SGM_COST_SAD, SGM_COST_SSD or SGM_COST_CT,
+ * whatever sgm_set_cost says.  One launch on `stream` (NULL = the handle's stream), no
  * host wait, no allocation: capturable into a HIP graph.  Any handle of the
  * working size serves, aux_only included.  The volume goes straight into
  * sgm_aggregate_device (SGM_VOL_F32, strides cols * D, D, 1).  Timed under the
- * profile class "window_cost".  SGM_ERR_INVALID_ARG, with a message, for a bad
+ * profile class "window_cost" (CT: "window_cost_ct").  SGM_ERR_INVALID_ARG, with a message, for a bad
  * kind, a NULL or misaligned pointer, pitch < width, and hipStreamLegacy as the
  * stream (see sgm_volume_import_device). */
 int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const uint8_t *d_right, int pitch,

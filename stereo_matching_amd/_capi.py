@@ -59,7 +59,7 @@ EXPORTS = (
 SGM_FILTER_H = 1
 SGM_FILTER_V = 2
 # sgm_set_cost's kinds (SGM_COST_*), by name
-COST_KINDS = {"census": 0, "sad": 1, "ssd": 2}
+COST_KINDS = {"census": 0, "sad": 1, "ssd": 2, "ct": 4}  # (3 is no kind)
 # sgm_volume's element types (SGM_VOL_*)
 SGM_VOL_F32 = 0
 SGM_VOL_F16 = 1

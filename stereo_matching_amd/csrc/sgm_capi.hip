@@ -791,9 +791,10 @@ int sgm_aggregate_device(sgm_handle *h, const sgm_volume *vol, float *d_out, int
 
 int sgm_set_cost(sgm_handle *h, int kind) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (kind != SGM_COST_CENSUS && kind != SGM_COST_SAD && kind != SGM_COST_SSD)
+    if (kind != SGM_COST_CENSUS && !sgm::window_cost_kind(kind))
         return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_set_cost: kind must be SGM_COST_CENSUS, SGM_COST_SAD or SGM_COST_SSD, got %d", kind);
+                       "sgm_set_cost: kind must be SGM_COST_CENSUS, SGM_COST_SAD, SGM_COST_SSD or SGM_COST_CT, got %d",
+                       kind);
     if (h->p.aux_only || h->p.solver != SGM_SOLVER_SGM)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_set_cost: BM and aux_only handles run no SGM frames");
     if (h->p.view == SGM_VIEW_RIGHT)
@@ -825,7 +826,7 @@ int sgm_window_cost_device(sgm_handle *h, int kind, const uint8_t *d_left, const
     DeviceGuard guard(h->device);
     StreamScope scope(h, stream);
     hipStream_t st = scope.st;
-    HIPCHK(h, timed(h, window_cost_name(h), vol_elems(h->g), st, [&] {
+    HIPCHK(h, timed(h, window_cost_name(h, kind), vol_elems(h->g), st, [&] {
                return sgm::launch_window_cost(kind, d_left, d_right, pitch, d_dst, h->min_disp, h->g, h->win,
                                               h->weights, st);
            }));

@@ -620,15 +620,15 @@ int volume_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     return views_to_out(h, f, direct_out, st);
 }
 
-// The cost stage of a frame on a SAD or SSD handle (sgm_set_cost, DESIGN.md
-// 5o): one launch writes the left view's window cost volume into its C; with
+// The cost stage of a frame on a SAD, SSD or CT handle (sgm_set_cost, DESIGN.md
+// 5o, 5s): one launch writes the left view's window cost volume into its C; with
 // two views the import kernel's right-view role derives the right view's from
 // it (the handle's own left buffer as a dense fp32 HWD source), from the raw
 // volume: the handle's cost filters (sgm_set_volume_filter) run after it, in
 // volume_frame.  No census, no masks.
 int window_cost_stage(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     const Geom g = h->g;
-    HIPCHK(h, timed(h, window_cost_name(h), vol_elems(g), st, [&] {
+    HIPCHK(h, timed(h, window_cost_name(h, h->cost_kind), vol_elems(g), st, [&] {
                return sgm::launch_window_cost(h->cost_kind, f.left, f.right, f.pitch, volume_raw_buf(h, 0),
                                               h->min_disp, g, h->win, h->weights, st);
            }));

@@ -61,7 +61,7 @@ struct sgm_handle {
     int win_h, win_w;     //   as set (the reference's WIN_H, WIN_W: 7, 9)
     float weights[sgm::kWinMax * sgm::kWinMax];  // sgm_set_weighted (win.weighted): window_weights' table of
                           //   win, rebuilt by the setters; read by the weighted producer's launches
-    int cost_kind;        // sgm_set_cost: SGM_COST_CENSUS (frames as ever), or the SAD / SSD window cost
+    int cost_kind;        // sgm_set_cost: SGM_COST_CENSUS (frames as ever), or the SAD / SSD / CT window cost
                           //   (frames: window_cost_stage + volume_frame, sgm_frame.hip)
     int vol_filter;       // sgm_set_volume_filter: the cost filters (SGM_FILTER_H | SGM_FILTER_V) every
                           //   volume frame runs on each view's volume (aggregate_volume, SAD / SSD
@@ -256,7 +256,9 @@ inline const char *census_name(const sgm_handle *h) {
     const sgm::Window w = h->win;
     return w.weighted && sgm::weighted_bits(w.hh(), w.hw()) < w.bits() ? "census_masked" : "census";
 }
-inline const char *window_cost_name(const sgm_handle *h) {
+inline const char *window_cost_name(const sgm_handle *h, int kind) {
+    // (CT's weighting is a mask in the launch's arguments: one kernel, one class)
+    if (kind == sgm::kCostCt) return "window_cost_ct";
     return h->win.weighted ? "window_cost_weighted" : "window_cost";
 }
 

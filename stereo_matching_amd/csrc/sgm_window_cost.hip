@@ -1,6 +1,7 @@
 // sgm_window_cost.hip -- the reference's SAD / SSD window costs as a cost
 // volume: Solver::build_dsi (Solver.cpp:96-117) over SAD and SSD
-// (cost.cpp:4-59), one launch.
+// (cost.cpp:4-59), one launch; and over CT (cost.cpp:62-96), the
+// per-disparity census build_dsi calls, on the same tile (window_cost_ct_kernel).
 //
 //   AD(y, x, d)  = |L[y][x] - R[y][max(x - (d + min_disp) / scale, 0)]|   (SSD: its square)
 //   C[i][j][d]   = (sum over the (2 hh + 1) x (2 hw + 1) taps of
@@ -240,6 +241,104 @@ __global__ __launch_bounds__(256) void window_cost_weighted_kernel(WinArgs a, Wi
     }
 }
 
+// ---------------------------------------------------------------- CT
+//
+// SGM_COST_CT: cost.cpp:62-96, the census per pixel and per disparity that
+// Solver::build_dsi calls.  With k = (d + min_disp) / scale and the centres
+// cl = L[i][j], cr = R[i][max(j - (d + min_disp), 0)] (the disparity itself, whatever the scale),
+//   cost = the kept taps (a, b) with x_r = clamp(j + b, 0, W - 1) - k >= 0 at which
+//          (L[y][x_l] > cl) != (R[y][x_r] > cr)
+// The tile, the staged rows and the lane's columns are the SAD kernel's; the staged right rows
+// clamp at column 0 where CT skips, so a skipped tap is read like any other and masked out.  A
+// window row's taps are a word of 2 HW + 1 bits, bit b = tap column b:
+//   left   (L > cl) does not depend on d: the workgroup computes every output pixel's rows once,
+//          into LDS, and a lane reads them back as one broadcast word per row;
+//   right  a lane reads a staged row's NCA bytes once and shifts one compare per tap into the
+//          word of each of its NC columns;
+//   kept   cm.row[a]: not the centre, and on a weighted handle only the disc (scalar registers);
+//   valid  x_l - k >= 0 depends on the tap's image column alone: one word per lane, bit c = the
+//          group's tap column c, shifted by the output column.
+// cost += popcount((left ^ right) & kept & valid) over the window's rows: the reference's two
+// words shift alike and keep at most 62 taps, so its Hamming cost is this count.
+struct CtMasks {
+    unsigned row[kWinMax];  // ct_row_mask of window row a
+};
+
+// HW is always a template argument; SCALE_T, HH_T are the default window's constants, 0 and -1
+// leave them to WinArgs (window_cost_kernel's comment).
+template <int HW, int DC, int SCALE_T, int HH_T>
+__global__ __launch_bounds__(256) void window_cost_ct_kernel(WinArgs a, CtMasks cm) {
+    constexpr bool FIXED = SCALE_T != 0;
+    static_assert(FIXED == (HH_T >= 0), "both or none");
+    const int SCALE = FIXED ? SCALE_T : a.scale, HH = FIXED ? HH_T : a.hh;
+    using Lane = WinLane<HW, DC, false>;
+    constexpr int RB = kWinCostBandRows, TC = kWinCostTileCols, NC = Lane::NC, NCA = Lane::NCA, LC = Lane::LC;
+    constexpr int EW = 2 * HW + 1;
+    constexpr int RC_MAX = win_r_cols(HW, FIXED ? SCALE_T : 1, DC), NR_MAX = win_rows(FIXED ? HH_T : kWinMax / 2);
+    constexpr int EH_MAX = FIXED ? 2 * HH_T + 1 : kWinMax;
+    static_assert(NCA <= 32 && EW <= 16, "a lane's tap columns and a row's taps are one word each");
+    __shared__ uint8_t sl[NR_MAX * LC];
+    __shared__ uint8_t sr[NR_MAX * RC_MAX];
+    __shared__ uint16_t lb[RB * TC * EH_MAX];  // [(r * TC + c) * EH + a]: output pixel (r, c)'s left bits of window row a
+    const WinTile t = win_tile<HW, DC>(a, SCALE);
+    stage_rows<HW>(a, t, SCALE, HH, sl, sr);
+    const int EH = 2 * HH + 1;
+    for (int idx = tid_x(); idx < RB * TC * EH; idx += 256) {
+        const int p = idx / EH, wa = idx - p * EH;
+        const int r = p / TC, c = p - r * TC;
+        const int cl = sl[(r + HH) * LC + c + HW];
+        const uint8_t *row = sl + (r + wa) * LC + c;
+        unsigned w = 0;
+#pragma unroll
+        for (int b = 0; b < EW; ++b) w |= (unsigned)((int)row[b] > cl) << b;
+        lb[idx] = (uint16_t)w;
+    }
+    __syncthreads();
+    const Lane ln(a, t, SCALE, sl, sr);
+    const int i0 = t.i0, j0 = t.j0, c0 = ln.c0, d = ln.d, RC = t.RC;
+    const int disp = d + a.min_disp, k = disp / SCALE;
+    unsigned valid = 0;
+#pragma unroll
+    for (int c = 0; c < NCA; ++c) valid |= (unsigned)(clampi(j0 - HW + c0 + c, 0, a.W - 1) >= k) << c;
+    const int rows = a.H - i0 < RB ? a.H - i0 : RB;
+    for (int rr = 0; rr < rows; ++rr) {
+        // the right centres: at scale 1 the staged centre tap; at scale 2 column j - disp lies
+        // left of the staged span (its shifts are disp / 2): read from the image
+        int cr[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            if (SCALE == 1) {
+                cr[q] = sr[(rr + HH) * RC + ln.ru[q + HW]];
+            } else {
+                const int j = j0 + c0 + q < a.W ? j0 + c0 + q : a.W - 1;
+                const int x = j - disp > 0 ? j - disp : 0;
+                cr[q] = a.right[(size_t)(i0 + rr) * a.rpitch + (size_t)x * SCALE];
+            }
+        }
+        int cost[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) cost[q] = 0;
+        for (int wa = 0; wa < EH; ++wa) {
+            int rb[NCA];
+#pragma unroll
+            for (int c = 0; c < NCA; ++c) rb[c] = sr[(rr + wa) * RC + ln.ru[c]];
+            const unsigned kept = cm.row[wa];
+            const uint16_t *lrow = lb + ((rr * TC + c0) * EH + wa);
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                unsigned w = 0;  // bit b = R's tap b > cr: the sign of cr - tap, shifted in from b = 2 HW down
+#pragma unroll
+                for (int b = EW - 1; b >= 0; --b) w = (w << 1) | ((unsigned)(cr[q] - rb[q + b]) >> 31);
+                cost[q] += __builtin_popcount((w ^ lrow[q * EH]) & kept & (valid >> q));
+            }
+        }
+        float *o = a.dst + ((size_t)(i0 + rr) * a.W + j0 + c0) * a.D + d;
+#pragma unroll
+        for (int q = 0; q < NC; ++q)
+            if (j0 + c0 + q < a.W) o[(size_t)q * a.D] = (float)cost[q];
+    }
+}
+
 // One launch of `kernel` over the volume's tiles: a.W x a.H in tiles by bands, D / DC chunks
 template <int DC, typename... Extra>
 hipError_t launch_tiles(void (*kernel)(WinArgs, Extra...), hipStream_t st, const WinArgs &a, const Extra &...extra) {
@@ -275,7 +374,7 @@ hipError_t launch_default(const WinArgs &a, hipStream_t st) {
 
 hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *right, int pitch, float *dst,
                               int min_disp, Geom g, Window win, const float *weights, hipStream_t st) {
-    if (!left || !right || !dst || (kind != kCostSad && kind != kCostSsd) || min_disp < 0 ||
+    if (!left || !right || !dst || !window_cost_kind(kind) || min_disp < 0 ||
         (g.scale != 1 && g.scale != 2) || g.D % 32 != 0 || win.eh < 1 || win.eh > kWinMax || win.ew < 1 ||
         win.ew > kWinMax || win.bits() > 64 || (win.weighted && (!weights || win.eh % 2 == 0 || win.ew % 2 == 0)))
         return hipErrorInvalidValue;
@@ -298,6 +397,23 @@ hipError_t launch_window_cost(int kind, const uint8_t *left, const uint8_t *righ
     if (win.weighted)
         for (int k = 0; k < win.eh * win.ew; ++k) ww.w[k] = weights[k];
     const Window def = default_window(g.scale);
+    if (kind == kCostCt) {
+        // the default window's sizes with SCALE and HH at compile time (weighted or not: the disc
+        // is in the masks), any other window by the instantiation of its half width
+        CtMasks cm{};
+        for (int r = 0; r <= 2 * win.hh(); ++r) cm.row[r] = ct_row_mask(win, r);
+        auto ct = [&](auto DC_C) -> hipError_t {
+            constexpr int DC = DC_C;
+            if (win.eh != def.eh || win.ew != def.ew)
+                return by_half_width(win.hw(), [&](auto HW) {
+                    return launch_tiles<DC>(window_cost_ct_kernel<HW, DC, 0, -1>, st, a, cm);
+                });
+            constexpr Window d1 = default_window(1), d2 = default_window(2);
+            return g.scale == 1 ? launch_tiles<DC>(window_cost_ct_kernel<d1.hw(), DC, 1, d1.hh()>, st, a, cm)
+                                : launch_tiles<DC>(window_cost_ct_kernel<d2.hw(), DC, 2, d2.hh()>, st, a, cm);
+        };
+        return g.D == 32 ? ct(std::integral_constant<int, 32>{}) : ct(std::integral_constant<int, 64>{});
+    }
     // DC and SSD as compile-time constants: the weighted kernel and any window but the default by
     // the instantiation of its half width, the default window with every constant at compile time
     auto launch = [&](auto DC_C, auto SSD_C) -> hipError_t {

@@ -1,5 +1,5 @@
-// sgm_window_cost_args.h -- the host side of the SAD/SSD window costs
-// (sgm_window_cost.hip, DESIGN.md 5o): the cost kinds, the window and its two
+// sgm_window_cost_args.h -- the host side of the SAD/SSD window costs and of CT
+// (sgm_window_cost.hip, DESIGN.md 5o, 5s): the cost kinds, the window and its two
 // divisions, the argument checks of the C-ABI and the tile geometry the kernel
 // indexes its staged rows by.  Plain C++ with no HIP in it, so that
 // tests/cpp/window_cost_args_main.cpp can run it on the CPU under a sanitizer;
@@ -15,6 +15,10 @@ namespace sgm {
 
 // The cost kinds of include/sgm_hip.h (SGM_COST_*), by value.
 constexpr int kCostCensus = 0, kCostSad = 1, kCostSsd = 2;
+// CT, build_dsi's per-disparity census.  3 stays refused: the reference's cost.cpp has
+// three functions beside CT_pts, and the value is pinned as invalid by the tests of before CT.
+constexpr int kCostCt = 4;
+constexpr bool window_cost_kind(int kind) { return kind == kCostSad || kind == kCostSsd || kind == kCostCt; }
 
 // The matching window: sgm_set_window's (win_h, win_w) are the
 // reference's WIN_H, WIN_W; Solver::build_dsi and build_cost_table divide them by
@@ -82,6 +86,25 @@ constexpr const char *weighted_refusal(int win_h, int win_w, int scale) {
     return nullptr;
 }
 
+// CT (cost.cpp:62-96) keeps the taps CT_pts keeps: every tap but the centre, and on
+// a weighted handle only the disc's.  Window row a's kept taps as a bit mask, bit b = tap column b
+// (a = 0 .. 2 hh, b = 0 .. 2 hw): the kernel ANDs it over the row's XORed census bits.
+constexpr unsigned ct_row_mask(Window w, int a) {
+    unsigned m = 0;
+    for (int b = 0; b <= 2 * w.hw(); ++b) {
+        const int da = a - w.hh(), db = b - w.hw();
+        if ((da || db) && (!w.weighted || weighted_tap_kept(da, db))) m |= 1u << b;
+    }
+    return m;
+}
+// the taps it keeps in all: the largest CT cost (62 at the most)
+constexpr int ct_taps(Window w) {
+    int n = 0;
+    for (int a = 0; a <= 2 * w.hh(); ++a)
+        for (unsigned m = ct_row_mask(w, a); m; m &= m - 1) ++n;
+    return n;
+}
+
 // The largest window sum: 63 taps of 255 (SAD) or 255^2 (SSD); exact in int32 and in fp32.
 constexpr int kWinCostMaxSum = 63 * 255 * 255;
 
@@ -136,7 +159,7 @@ constexpr int win_lds_bytes(Window w, int scale, int DC) {
 // reason a call is refused, or null.  width: the images' columns (bytes per row).
 inline const char *window_cost_refusal(int kind, const void *left, const void *right, int pitch, int width,
                                        const void *dst) {
-    if (kind != kCostSad && kind != kCostSsd) return "kind must be SGM_COST_SAD or SGM_COST_SSD";
+    if (!window_cost_kind(kind)) return "kind must be SGM_COST_SAD, SGM_COST_SSD or SGM_COST_CT";
     if (!left || !right) return "NULL image";
     if (pitch < width) return "pitch below the image width";
     if (!dst) return "d_dst is NULL";

@@ -73,9 +73,9 @@ class SGM:
                  cost: str = "census", window=None, volume_filter=None, weighted: bool = False,
                  _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
-        # cost ("census" | "sad" | "ssd"): the matching cost of every frame
-        # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost
-        # (Solver::build_dsi over cost.cpp:4-59) with no cost filters after it
+        # cost ("census" | "sad" | "ssd" | "ct"): the matching cost of every frame
+        # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost or
+        # its CT (Solver::build_dsi over cost.cpp:4-96) with no cost filters after it
         if cost not in _capi.COST_KINDS:
             raise ValueError(f"cost must be one of {sorted(_capi.COST_KINDS)}, got {cost!r}")
         # paths (8 | 4): 4 is the reference's USE_8_PATH = false (inc/SGM.h:7):
@@ -630,7 +630,8 @@ class SGM:
 
     # ------------------------------------------------------ the matching cost
     def set_cost(self, kind: str) -> None:
-        """sgm_set_cost: "census" (the default), "sad" or "ssd".  With a window
+        """sgm_set_cost: "census" (the default), "sad", "ssd" or "ct" (CT,
+        build_dsi's own per-disparity census: DESIGN.md 5s).  With a window
         cost every later frame builds the reference's build_dsi volume (one
         launch), derives the right view's from it and runs what aggregate()
         runs; the cost filters run only when set_volume_filter says so, and sky
@@ -746,15 +747,15 @@ class SGM:
         return w.reshape(wh // self.scale, ww // self.scale)
 
     def window_cost(self, left, right, kind: str = "sad", out=None, stream=None):
-        """sgm_window_cost_device: the float32 (rows, cols, D) SAD or SSD cost
+        """sgm_window_cost_device: the float32 (rows, cols, D) SAD, SSD or CT cost
         volume of two torch uint8 device images of shape (h, w) (unit column
         stride; read decimated by the scale, not blurred), as a torch tensor on
         the same device (`out`, allocated when None).  One launch on `stream`
         (default: the device's current torch stream; the tensors' lifetime on
         another stream is the caller's, as for aggregate).  The result goes
         straight into aggregate()."""
-        if kind not in ("sad", "ssd"):
-            raise ValueError(f"kind must be 'sad' or 'ssd', got {kind!r}")
+        if kind not in ("sad", "ssd", "ct"):
+            raise ValueError(f"kind must be 'sad', 'ssd' or 'ct', got {kind!r}")
         import torch
         for name, img in (("left", left), ("right", right)):
             if isinstance(img, np.ndarray) or not hasattr(img, "data_ptr"):
@@ -780,8 +781,8 @@ class SGM:
     def stage_window_cost(self, left, right, kind: str = "sad") -> np.ndarray:
         """sgm_stage_window_cost: the same volume from host numpy (h, w) uint8
         images, as a numpy (rows, cols, D) float32 array (tests)."""
-        if kind not in ("sad", "ssd"):
-            raise ValueError(f"kind must be 'sad' or 'ssd', got {kind!r}")
+        if kind not in ("sad", "ssd", "ct"):
+            raise ValueError(f"kind must be 'sad', 'ssd' or 'ct', got {kind!r}")
         l, r = _u8(left, (self.h, self.w), "left"), _u8(right, (self.h, self.w), "right")
         cost = np.empty((self.rows, self.cols, self.max_disp), np.float32)
         check(self._lib.sgm_stage_window_cost(self._h, _capi.COST_KINDS[kind], _ptr(l), _ptr(r), self.w,
