@@ -91,7 +91,7 @@ def expected(shape, paths=4):
 
 def bits(a):
     """An array as what the bit-exact comparisons compare: floats as their float32 bit patterns,
-    everything else as int64."""
+    everything else as int64 (a meaning of its own: neither support.bits nor support.f32_bits)."""
     a = np.ascontiguousarray(a)
     return a.astype(np.float32, copy=False).view(np.uint32) if a.dtype.kind == "f" else a.astype(np.int64)
 

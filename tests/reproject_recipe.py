@@ -21,6 +21,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from support import bits  # noqa: F401  (re-exported: the reproject tests compare through rp.bits)
+
 MISSING_BITS = 0x7FC00000
 XYZ, DEPTH, DEPTH16 = 1, 2, 4
 OUTPUT_BITS = {"xyz": XYZ, "depth": DEPTH, "depth16": DEPTH16}
@@ -74,12 +76,6 @@ def reproject(disp, q, invalid, scale=1, max_range=0.0, depth_scale=1000.0):
     depth = Z.view(np.uint32).copy()
     depth[missing] = MISSING_BITS
     return {"xyz": xyz.view(np.float32), "depth": depth.view(np.float32), "depth16": depth16, "missing": missing}
-
-
-def bits(a):
-    """A float32 array as its uint32 bit patterns (other arrays unchanged)."""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def skewed_q():

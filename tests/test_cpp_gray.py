@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gray_recipe as gr
+import support
 from stereo_matching_amd import _capi, synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,15 +20,7 @@ SURFACE_SRC = os.path.join(ROOT, "tests", "cpp", "sgm_gray_surface.cpp")
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "sgm_gray_surface")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    SURFACE_SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SURFACE_SRC)
 
 
 def test_surface_compiles_and_checks_its_arguments(exe):

@@ -10,7 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from stereo_matching_amd import _capi, synthetic
+import support
+from stereo_matching_amd import synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "post_filter_async.cpp")
@@ -22,16 +23,7 @@ BUDGET = -(-W // 64) * H + 1
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "post_filter_async")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
-                    "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-pthread", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SRC, hip_headers=True, pthread=True)
 
 
 def test_program_compiles_against_the_headers(exe):

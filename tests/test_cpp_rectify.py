@@ -15,24 +15,17 @@ import numpy as np
 import pytest
 
 import rectify_recipe as rc
-from stereo_matching_amd import SGM, _capi, synthetic
+import support
+from stereo_matching_amd import SGM, synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAPS_SRC = os.path.join(ROOT, "tests", "cpp", "rectify_maps_main.cpp")
 SURFACE_SRC = os.path.join(ROOT, "tests", "cpp", "sgm_rectify_surface.cpp")
-BUILDS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
 
 
-@pytest.fixture(scope="module", params=list(BUILDS))
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
 def maps_exe(request, tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("maps") / f"rectify_maps_{request.param}")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + BUILDS[request.param] + [MAPS_SRC, "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
-
-
-def run(exe, *args):
-    return subprocess.run([exe, *args], capture_output=True, text=True, timeout=60)     # directly: no preload
+    return support.host_program(tmp_path_factory.mktemp("maps"), MAPS_SRC, sanitized=request.param == "sanitized")
 
 
 def small_maps():
@@ -64,7 +57,7 @@ def test_conversion_matches_the_recipe(maps_exe, tmp_path, pitch):
             buf = np.full((h, pitch), np.nan, np.float32)     # (padding the conversion must not read as map)
             buf[:, :w] = m
             f.write(buf.tobytes())
-    r = run(maps_exe, "convert", path, str(h), str(w), str(pitch), "5", "7")
+    r = support.run(maps_exe, "convert", path, str(h), str(w), str(pitch), "5", "7")
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.array([[int(a, 16), int(b, 16), int(v)] for a, b, v in (ln.split() for ln in r.stdout.splitlines())],
                    np.int64).reshape(h, w, 3)
@@ -78,7 +71,7 @@ def test_conversion_matches_the_recipe(maps_exe, tmp_path, pitch):
 
 
 def test_argument_checks(maps_exe):
-    r = run(maps_exe, "args")
+    r = support.run(maps_exe, "args")
     assert r.returncode == 0 and "rectify args ok" in r.stdout, r.stdout + r.stderr
     lines = dict(ln.split(": ", 1) for ln in r.stdout.splitlines() if ": " in ln)
     for ok in ("off", "smallest", "largest", "left dense", "right padded"):
@@ -88,21 +81,13 @@ def test_argument_checks(maps_exe):
                 "map_pitch below width", "map_pitch negative", "view 2", "view -1", "src_pitch below src_cols",
                 "dst_pitch below width"):
         assert lines[bad].startswith("refused: ") and len(lines[bad]) > len("refused: "), bad
-    r = run(maps_exe)
+    r = support.run(maps_exe)
     assert r.returncode == 64 and "usage" in r.stderr
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "sgm_rectify_surface")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    SURFACE_SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SURFACE_SRC)
 
 
 def test_surface_compiles_and_checks_its_arguments(exe):

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import resize_recipe as rr
-from stereo_matching_amd import SGM, _capi, synthetic
+import support
+from stereo_matching_amd import SGM, synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "sgm_resize_surface.cpp")
@@ -19,15 +20,7 @@ SRC = os.path.join(ROOT, "tests", "cpp", "sgm_resize_surface.cpp")
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "sgm_resize_surface")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SRC)
 
 
 def test_surface_compiles_and_checks_its_arguments(exe):

@@ -11,7 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from stereo_matching_amd import _capi, synthetic
+import support
+from stereo_matching_amd import synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "sgm_class_surface.cpp")
@@ -19,17 +20,8 @@ SRC = os.path.join(ROOT, "tests", "cpp", "sgm_class_surface.cpp")
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "sgm_class_surface")
-    libdir = os.path.dirname(_capi.LIB_PATH)
     # BatchSGM.h uses the HIP runtime API on the host (plain g++, no hipcc)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
-                    "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-pthread", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SRC, hip_headers=True, pthread=True)
 
 
 def _has_gpu() -> bool:

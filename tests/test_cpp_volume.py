@@ -9,33 +9,21 @@ import subprocess
 
 import pytest
 
-from stereo_matching_amd import _capi
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SURFACE_SRC = os.path.join(ROOT, "tests", "cpp", "sgm_volume_surface.cpp")
 
 
 def test_stride_rule_runs_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "volume_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "volume_args_main.cpp"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "volume_args_main.cpp"))
+    r = support.run(exe)
     assert r.returncode == 0 and "volume args ok" in r.stdout, r.stdout + r.stderr
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "sgm_volume_surface")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
-                    "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                    SURFACE_SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SURFACE_SRC, hip_headers=True)
 
 
 def test_surface_compiles_and_checks_its_arguments(exe):

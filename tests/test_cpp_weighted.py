@@ -4,16 +4,14 @@ indices as a stand-alone program under sanitizers."""
 from __future__ import annotations
 
 import os
-import subprocess
+
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_table_mask_rule_and_indices_run_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "weighted_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "cpp", "weighted_args_main.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "weighted_args_main.cpp"),
+                               fp_contract_off=True)
+    r = support.run(exe, timeout=300)
     assert r.returncode == 0 and "weighted args ok" in r.stdout, r.stdout + r.stderr

@@ -14,34 +14,23 @@ import numpy as np
 import pytest
 
 import window_recipe as wr
-from stereo_matching_amd import _capi, synthetic
+import support
+from stereo_matching_amd import synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SURFACE_SRC = os.path.join(ROOT, "tests", "cpp", "sgm_window_surface.cpp")
 
 
 def test_rule_divisions_and_indices_run_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "window_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    os.path.join(ROOT, "tests", "cpp", "window_args_main.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "window_args_main.cpp"),
+                               fp_contract_off=True)
+    r = support.run(exe, timeout=300)
     assert r.returncode == 0 and "window args ok" in r.stdout, r.stdout + r.stderr
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("cpp") / "sgm_window_surface")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
-                    "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                    SURFACE_SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-L", "/opt/rocm/lib",
-                    "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
+    return support.library_program(tmp_path_factory, SURFACE_SRC, hip_headers=True)
 
 
 def test_surface_compiles_and_checks_its_arguments(exe):

@@ -8,13 +8,13 @@ from __future__ import annotations
 
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ct_cost_recipe as ct
 import window_recipe
+import support
 from stereo_matching_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,11 +94,8 @@ def test_identity_with_the_census_tables(name):
 
 
 def test_kernel_arithmetic_runs_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "ct_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "ct_args_main.cpp"), "-o", exe],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "ct_args_main.cpp"))
+    r = support.run(exe, timeout=300)
     assert r.returncode == 0 and "ct args ok" in r.stdout, r.stdout + r.stderr
 
 

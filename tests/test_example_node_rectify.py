@@ -14,7 +14,8 @@ import pytest
 
 import pyref
 import rectify_recipe as rc
-from stereo_matching_amd import SGM, _capi, synthetic
+import support
+from stereo_matching_amd import SGM, synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "examples", "stereo_node.cpp")
@@ -23,20 +24,7 @@ CAM = (721.5377, 721.5377, 609.5593, 172.854)   # the example's defaults (KITTI 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("node") / "stereo_node")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
-
-
-def _pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, np.uint8).tobytes())
+    return support.library_program(tmp_path_factory, SRC, link_hip=False)
 
 
 def test_usage_names_the_maps_argument(exe):
@@ -54,8 +42,8 @@ def test_example_node_rectifies_raw_images(exe, tmp_path):
     left[: sh // 5] //= 4          # a darker, flat band on top for the sky detector
     right[: sh // 5] //= 4
     ml, mr = rc.maps(h, w, sh, sw, 0), rc.maps(h, w, sh, sw, 1)
-    _pgm(tmp_path / "l.pgm", left)
-    _pgm(tmp_path / "r.pgm", right)
+    support.write_pgm(tmp_path / "l.pgm", left)
+    support.write_pgm(tmp_path / "r.pgm", right)
     np.stack([*ml, *mr]).astype(np.float32).tofile(tmp_path / "maps.f32")
     prefix = str(tmp_path / "out")
     r = subprocess.run([exe, str(tmp_path / "l.pgm"), str(tmp_path / "r.pgm"), prefix, "1", str(D)]

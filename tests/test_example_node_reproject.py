@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import reproject_recipe as rp
-from stereo_matching_amd import _capi, synthetic
+import support
+from stereo_matching_amd import synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "examples", "stereo_node.cpp")
@@ -21,20 +22,7 @@ MR = "20.5"
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("node") / "stereo_node")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
-
-
-def _pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, np.uint8).tobytes())
+    return support.library_program(tmp_path_factory, SRC, link_hip=False)
 
 
 def test_usage_names_the_q_file(exe):
@@ -48,8 +36,8 @@ def test_example_node_writes_xyz_and_depth_of_its_own_map(exe, tmp_path, scale, 
     D = 64
     h, w = 60 * scale, 200 * scale
     left, right = synthetic.stereo_pair(h, w, D, pair_index=0, kind="road")
-    _pgm(tmp_path / "l.pgm", left)
-    _pgm(tmp_path / "r.pgm", right)
+    support.write_pgm(tmp_path / "l.pgm", left)
+    support.write_pgm(tmp_path / "r.pgm", right)
     q = rp.camera_q(721.5377, 721.5377, 609.5593, 172.854, 0.54)
     q.tofile(tmp_path / "Q.f64")
     prefix = str(tmp_path / "out")

@@ -13,7 +13,8 @@ import pytest
 
 import pyref
 import resize_recipe as rr
-from stereo_matching_amd import _capi, synthetic
+import support
+from stereo_matching_amd import synthetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "examples", "stereo_node.cpp")
@@ -22,20 +23,7 @@ CAM = (721.5377, 721.5377, 609.5593, 172.854)   # the example's defaults (KITTI 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    if not os.path.exists(_capi.LIB_PATH):
-        _capi.build()
-    out = str(tmp_path_factory.mktemp("node") / "stereo_node")
-    libdir = os.path.dirname(_capi.LIB_PATH)
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    SRC, "-L", libdir, "-lsgm_hip", f"-Wl,-rpath,{libdir}", "-o", out],
-                   check=True, capture_output=True, text=True)
-    return out
-
-
-def _pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, np.uint8).tobytes())
+    return support.library_program(tmp_path_factory, SRC, link_hip=False)
 
 
 def test_usage_names_the_size_arguments_and_twelve_arguments_are_refused(exe):
@@ -55,8 +43,8 @@ def test_example_node_resizes_to_the_configured_size(exe, tmp_path, scale, raw, 
     left, right = synthetic.stereo_pair(sh, sw, D, pair_index=21, kind="road")
     left[: sh // 5] //= 4          # a darker, flat band on top for the sky detector
     right[: sh // 5] //= 4
-    _pgm(tmp_path / "l.pgm", left)
-    _pgm(tmp_path / "r.pgm", right)
+    support.write_pgm(tmp_path / "l.pgm", left)
+    support.write_pgm(tmp_path / "r.pgm", right)
     prefix = str(tmp_path / "out")
     r = subprocess.run([exe, str(tmp_path / "l.pgm"), str(tmp_path / "r.pgm"), prefix, str(scale), str(D)]
                        + [repr(c) for c in CAM] + ["0", str(w), str(h)],

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle
+from support import f32_bits as bits
 from stereo_matching_amd import SGM
 
 pytestmark = pytest.mark.gpu
@@ -35,10 +36,6 @@ CASES = [
     (32, 2, 5, 4033, True, "scale 2, masked: global, window 2"),
 ]
 IDS = [f"D{D}-s{s}-{H}x{W}{'-sky' if sky else ''}" for D, s, H, W, sky, _ in CASES]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("D,s,H,W,sky,what", CASES, ids=IDS)

@@ -16,13 +16,10 @@ import numpy as np
 import pytest
 
 import oracle
+from support import f32_bits as _bits
 from stereo_matching_amd import SGM, synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.timeout(300)

@@ -12,13 +12,10 @@ import pytest
 import torch
 
 import oracle
+from support import f32_bits as bits
 from stereo_matching_amd import SGM, synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.timeout(120)

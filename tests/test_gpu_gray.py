@@ -18,6 +18,7 @@ import torch
 import gray_recipe as gr
 import rectify_recipe as rc
 import resize_recipe as rr
+from support import bits
 from stereo_matching_amd import BM, SGM, _capi, synthetic
 from stereo_matching_amd._capi import SGMError
 
@@ -31,11 +32,6 @@ HEIGHTS = (1, 2, 17)
 
 def _p(a):
     return ctypes.c_void_p(a.ctypes.data)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 # ------------------------------------------------------- stand-alone conversion

@@ -10,13 +10,10 @@ import numpy as np
 import pytest
 
 import oracle
+from support import f32_bits as bits
 from stereo_matching_amd import SGM, synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def check(sgm, left, right, disp, D, s):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle
+from support import bits
 from stereo_matching_amd import SGM, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -34,10 +35,6 @@ CASES = [
 ]
 IDS = [f"{h}x{w}_D{D}_s{s}_{k}{'_sky' if sk else ''}{'' if b else '_noblur'}"
        for h, w, D, s, k, sk, b in CASES]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else a.dtype)
 
 
 def assert_bits_equal(got, want, what):

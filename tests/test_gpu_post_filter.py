@@ -13,13 +13,10 @@ import pytest
 
 import oracle
 import postfilter_maps
+from support import f32_bits as bits
 from stereo_matching_amd import BM, SGM, synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def check_map(sgm, F, D, scale):

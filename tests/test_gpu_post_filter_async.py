@@ -21,6 +21,7 @@ import torch
 
 import oracle
 import postfilter_maps
+from support import f32_bits as bits
 from stereo_matching_amd import BM, SGM, SGMError, _capi, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def bound(H, W):
     return -(-W // 64) * H + 1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 # ------------------------------------------------------------ bit-exactness

@@ -18,15 +18,12 @@ import numpy as np
 import pytest
 
 import oracle
+from support import f32_bits as _bits
 from stereo_matching_amd import SGM, synthetic
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "sky_000017_14.npz")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def _pair(D, layered):

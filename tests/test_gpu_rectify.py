@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import rectify_recipe as rc
+from support import bits
 from stereo_matching_amd import BM, SGM, _capi, synthetic
 from stereo_matching_amd._capi import SGMError
 
@@ -116,11 +117,6 @@ VARIANTS = {
     "config5": dict(views=2, sky_detect=True, post_filter=True, lk_refine=True, post_filter_launches=8),
     "bm": dict(cls=BM),
 }
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def make(variant, rectify=None):

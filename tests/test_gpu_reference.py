@@ -23,6 +23,7 @@ import os
 import numpy as np
 import pytest
 
+from support import bits
 from stereo_matching_amd import BM, SGM
 
 pytestmark = pytest.mark.gpu
@@ -35,11 +36,6 @@ _spec.loader.exec_module(gen)
 with open(os.path.join(GOLDEN, "ref_hashes.json")) as _fh:
     HASHES = json.load(_fh)["volumes"]
 NAMES = list(gen.CASES)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def same_map(got, want, what):

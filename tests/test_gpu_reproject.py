@@ -30,6 +30,7 @@ import gray_recipe as gr
 import oracle
 import reproject_recipe as rp
 import resize_recipe as rr
+from support import bits
 from stereo_matching_amd import BM, SGM, _capi, camera_q, synthetic
 from stereo_matching_amd._capi import SGMError
 
@@ -46,10 +47,6 @@ D0 = 32
 CAM = (700.5, 699.25, 31.5, 8.25, 0.12)
 NAMES = {XYZ: "xyz", DEPTH: "depth", DEPTH16: "depth16"}
 CH = {XYZ: 3, DEPTH: 1, DEPTH16: 1}
-
-
-def bits(a):
-    return rp.bits(a)
 
 
 def range_for(disp, q, invalid, scale):

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import resize_recipe as rr
+from support import bits
 from stereo_matching_amd import BM, SGM, _capi, synthetic
 from stereo_matching_amd._capi import SGMError
 
@@ -106,11 +107,6 @@ VARIANTS = {
     "bm": dict(cls=BM),
     "config5": dict(views=2, sky_detect=True, post_filter=True, lk_refine=True, post_filter_launches=8),
 }
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def make(variant, input_size=None):

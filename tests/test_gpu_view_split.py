@@ -30,7 +30,7 @@ torch.cuda.init()
 import oracle
 from stereo_matching_amd import SGM, synthetic
 
-def bits(t):
+def bits(t):     # the child script's own (support.f32_bits takes no tensors, and tests/ is not on this path)
     a = t.cpu().numpy() if isinstance(t, torch.Tensor) else t
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 

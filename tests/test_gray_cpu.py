@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gray_recipe as gr
+import support
 from stereo_matching_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,10 +85,6 @@ def test_header_binding_and_build_list_carry_the_feature():
 
 def test_host_side_checks_run_clean_under_sanitizers(tmp_path):
     # the format table and the pitch checks (csrc/sgm_gray_args.h) as a stand-alone CPU program
-    import subprocess
-    exe = str(tmp_path / "gray_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "gray_args_main.cpp"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "gray_args_main.cpp"))
+    r = support.run(exe)
     assert r.returncode == 0 and "gray args ok" in r.stdout, r.stdout + r.stderr

@@ -5,17 +5,15 @@ under sanitizers; the build list carries the new source file and header."""
 from __future__ import annotations
 
 import os
-import subprocess
+
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_input_stage_runs_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "input_stage")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "input_stage_main.cpp"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "input_stage_main.cpp"))
+    r = support.run(exe)
     assert r.returncode == 0 and "input stage ok" in r.stdout, r.stdout + r.stderr
 
 

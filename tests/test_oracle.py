@@ -20,13 +20,10 @@ import pytest
 
 import oracle
 import pyref
+from support import f32_bits as bits
 from stereo_matching_amd import synthetic
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 # ------------------------------------------------------- known answers

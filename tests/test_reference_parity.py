@@ -25,6 +25,7 @@ import pytest
 
 import oracle
 import pyref
+from support import bits
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _spec = importlib.util.spec_from_file_location("make_ref_golden", os.path.join(GOLDEN, "make_ref_golden.py"))
@@ -44,11 +45,6 @@ def few_threads():
     oracle.set_threads(min(before, 4))
     yield
     oracle.set_threads(before)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def same_map(got, want, what):

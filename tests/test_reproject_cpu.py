@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import reproject_recipe as rp
+import support
 from stereo_matching_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -152,10 +153,6 @@ def test_header_binding_and_build_list_carry_the_feature():
 
 def test_host_side_checks_run_clean_under_sanitizers(tmp_path):
     # the setter's and the device call's checks (csrc/sgm_reproject_args.h) as a stand-alone CPU program
-    import subprocess
-    exe = str(tmp_path / "reproject_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "reproject_args_main.cpp"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "reproject_args_main.cpp"))
+    r = support.run(exe)
     assert r.returncode == 0 and "reproject args ok" in r.stdout, r.stdout + r.stderr

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import resize_recipe as rr
+import support
 from stereo_matching_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,10 +84,6 @@ def test_header_binding_and_build_list_carry_the_feature():
 
 def test_host_side_checks_run_clean_under_sanitizers(tmp_path):
     # the size checks and scale factors (csrc/sgm_resize_args.h) as a stand-alone CPU program
-    import subprocess
-    exe = str(tmp_path / "resize_args")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "resize_args_main.cpp"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    exe = support.host_program(tmp_path, os.path.join(ROOT, "tests", "cpp", "resize_args_main.cpp"))
+    r = support.run(exe)
     assert r.returncode == 0 and "resize args ok" in r.stdout, r.stdout + r.stderr

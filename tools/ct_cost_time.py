@@ -15,47 +15,21 @@ element count, not measured.
 """
 from __future__ import annotations
 
-import ctypes
-import statistics
+import functools
 import sys
 
 import torch
 
+import event_time
+from event_time import DEV, class_means, fmt, profile_of
 from stereo_matching_amd import SGM, _capi, synthetic
 
-DEV = torch.device("cuda", 0)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 25
-
-
-def timed(stream, fn, n=N, warm=3):
-    ms = []
-    for k in range(warm + n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record(stream)
-            fn()
-            b.record(stream)
-        b.synchronize()
-        if k >= warm:
-            ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
-
-
-def profile_of(s, frame):
-    s.set_profiling(True)
-    s.get_profile()
-    for _ in range(N):
-        frame()
-    torch.cuda.synchronize(DEV)
-    prof = s.get_profile()
-    s.set_profiling(False)
-    return {k: v[1] / v[0] for k, v in prof.items()}
+timed = functools.partial(event_time.timed, n=N)
 
 
 def main():
     _capi.lib()
-    hip = ctypes.CDLL(_capi.hip_runtimes()[0])
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     print(f"# median of {N} (min..max), HIP events around the call")
     for h, w, D in ((375, 1242, 128), (1080, 1920, 256)):
         left, right = synthetic.stereo_pair(h, w, D, pair_index=0)
@@ -65,22 +39,22 @@ def main():
             stream = torch.cuda.ExternalStream(s.stream, device=DEV)
             out = torch.empty((h, w, D), dtype=torch.float32, device=DEV)
             twin = torch.rand((h, w, D), dtype=torch.float32, device=DEV)
-            copy = timed(stream, lambda: hip.hipMemcpyAsync(out.data_ptr(), twin.data_ptr(), nvol * 4, 3,
-                                                             ctypes.c_void_p(s.stream)))
-            print(f"{h}x{w}x{D} memcpy d2d {nvol * 4 / 1e6:8.1f} MB out: {copy[0]:7.3f} ms ({copy[1]:.3f}..{copy[2]:.3f})")
+            d2d = event_time.d2d_copy(s.stream)
+            copy = timed(stream, lambda: d2d(out.data_ptr(), twin.data_ptr(), nvol * 4))
+            print(f"{h}x{w}x{D} memcpy d2d {nvol * 4 / 1e6:8.1f} MB out: {fmt(copy)}")
             del twin
             for kind in ("sad", "ct"):
                 t = timed(stream, lambda: s.window_cost(d_l, d_r, kind, out=out, stream=s.stream))
-                print(f"{h}x{w}x{D} window_cost {kind:3s}: {t[0]:7.3f} ms ({t[1]:.3f}..{t[2]:.3f})  "
+                print(f"{h}x{w}x{D} window_cost {kind:3s}: {fmt(t)}  "
                       f"{nvol * 4 / t[0] / 1e9:5.2f} TB/s written  {t[0] / copy[0]:5.2f} x the copy")
             s.set_weighted(True)
             t = timed(stream, lambda: s.window_cost(d_l, d_r, "ct", out=out, stream=s.stream))
-            print(f"{h}x{w}x{D} window_cost ct weighted: {t[0]:7.3f} ms ({t[1]:.3f}..{t[2]:.3f})")
+            print(f"{h}x{w}x{D} window_cost ct weighted: {fmt(t)}")
             del out
         with SGM(h, w, 1, D, views=1) as s:
             res = torch.empty((h, w), dtype=torch.float32, device=DEV)
-            prof = profile_of(s, lambda: s.process_device(d_l.data_ptr(), d_r.data_ptr(), res.data_ptr(),
-                                                          stream=s.stream))
+            prof = class_means(profile_of(s, n=N, frame=lambda: s.process_device(
+                d_l.data_ptr(), d_r.data_ptr(), res.data_ptr(), stream=s.stream)))
             print(f"{h}x{w}x{D} census frame, per launch class (mean ms): " +
                   ", ".join(f"{k} {v:.3f}" for k, v in prof.items()))
         # elements outside hw <= j <= W - 1 - hw and j - disp >= hw (hw = 4), of a row's W * D
@@ -101,10 +75,10 @@ def main():
             for kind in ("census", "sad", "ct"):
                 s.set_cost(kind)
                 f = timed(stream, frame)
-                print(f"K128 views={views} {kind:6s} frame: {f[0]:7.3f} ms ({f[1]:.3f}..{f[2]:.3f})")
+                print(f"K128 views={views} {kind:6s} frame: {fmt(f)}")
                 if kind == "ct":
                     print("    per launch class (mean ms): " +
-                          ", ".join(f"{k} {v:.3f}" for k, v in profile_of(s, frame).items()))
+                          ", ".join(f"{k} {v:.3f}" for k, v in class_means(profile_of(s, frame, N)).items()))
             s.check()
 
 

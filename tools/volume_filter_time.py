@@ -10,54 +10,26 @@ kept in profiles/volume_filter_ab.txt.
 """
 from __future__ import annotations
 
-import ctypes
-import statistics
+import functools
 import sys
 
 import torch
 
+import event_time
+from event_time import DEV, class_means, fmt, profile_of
 from stereo_matching_amd import SGM, _capi, synthetic
 
-DEV = torch.device("cuda", 0)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 15
+timed = functools.partial(event_time.timed, n=N)
 
 
-def timed(stream, fn, n=N, warm=3):
-    ms = []
-    for k in range(warm + n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record(stream)
-            fn()
-            b.record(stream)
-        b.synchronize()
-        if k >= warm:
-            ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
-
-
-def fmt(t):
-    return f"{t[0]:7.3f} ms ({t[1]:.3f}..{t[2]:.3f})"
-
-
-def classes(s, fn, n=N):
-    """Mean ms per launch class over n calls of fn."""
-    fn()
-    torch.cuda.synchronize(DEV)
-    s.set_profiling(True)
-    s.get_profile()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize(DEV)
-    prof = s.get_profile()
-    s.set_profiling(False)
-    return {k: v[1] / v[0] for k, v in prof.items()}
+def classes(s, fn):
+    """Mean ms per launch class over N calls of fn, after one unprofiled call."""
+    return class_means(profile_of(s, fn, N, warm=1))
 
 
 def main():
     _capi.lib()
-    hip = ctypes.CDLL(_capi.hip_runtimes()[0])
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     print(f"# median of {N} (min..max) after 3 discarded runs, HIP events around the call; "
           f"block = {_capi.lib().sgm_volume_filter_block()} steps")
     for h, w, D in ((375, 1242, 128), (1080, 1920, 256)):
@@ -72,8 +44,8 @@ def main():
                 twin = torch.empty((h, w, D), dtype=torch.float32, device=DEV)
                 tag = f"{h}x{w}x{D} views={views}"
                 if views == 1:
-                    c = timed(stream, lambda: hip.hipMemcpyAsync(twin.data_ptr(), vol.data_ptr(), nvol * 4, 3,
-                                                                 ctypes.c_void_p(s.stream)))
+                    d2d = event_time.d2d_copy(s.stream)
+                    c = timed(stream, lambda: d2d(twin.data_ptr(), vol.data_ptr(), nvol * 4))
                     print(f"{tag} memcpy d2d of one view: {fmt(c)}")
                     f1 = timed(stream, lambda: s.filter_volume(twin, True, False, stream=s.stream))
                     print(f"{tag} filter_volume H in place: {fmt(f1)}")

@@ -15,37 +15,22 @@ which exists only inside sgm_aggregate_device) is the library's own event pair
 """
 from __future__ import annotations
 
-import ctypes
-import statistics
+import functools
 import sys
 
 import numpy as np
 import torch
 
+import event_time
+from event_time import DEV, fmt, profile_of
 from stereo_matching_amd import SGM, _capi, synthetic
 
-DEV = torch.device("cuda", 0)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 25
-
-
-def timed(stream, fn, n=N, warm=3):
-    ms = []
-    for k in range(warm + n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record(stream)
-            fn()
-            b.record(stream)
-        b.synchronize()
-        if k >= warm:
-            ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
+timed = functools.partial(event_time.timed, n=N)
 
 
 def main():
     _capi.lib()
-    hip = ctypes.CDLL(_capi.hip_runtimes()[0])
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     print(f"# median of {N} (min..max), HIP events around the launch; TB/s = (bytes read + written) / time")
     for h, w, D in ((375, 1242, 128), (1080, 1920, 256)):
         with SGM(h, w, 1, D, aux_only=True) as s, SGM(h, w, 1, D, views=2) as s2:
@@ -53,8 +38,8 @@ def main():
             nvol = h * w * D
             out = torch.empty((h, w, D), dtype=torch.float32, device=DEV)
             twin = torch.empty_like(out)
-            med, lo, hi = timed(stream, lambda: hip.hipMemcpyAsync(out.data_ptr(), twin.data_ptr(), nvol * 4, 3,
-                                                                     ctypes.c_void_p(s.stream)))
+            d2d = event_time.d2d_copy(s.stream)
+            med, lo, hi = timed(stream, lambda: d2d(out.data_ptr(), twin.data_ptr(), nvol * 4))
             print(f"{h}x{w}x{D} memcpy d2d {nvol * 4 / 1e6:8.1f} MB out: {med:7.3f} ms ({lo:.3f}..{hi:.3f})  "
                   f"{2 * nvol * 4 / med / 1e9:5.2f} TB/s")
             for layout in ("hwd", "dhw"):
@@ -71,15 +56,8 @@ def main():
                     # both views in one launch: the library's own event pair (profile class vol_import)
                     if nvol * 4 < 1 << 30:
                         res = torch.empty((h, w), dtype=torch.float32, device=DEV)
-                        s2.aggregate(cost, layout=layout, out=res, stream=s2.stream)
-                        torch.cuda.synchronize(DEV)
-                        s2.set_profiling(True)
-                        s2.get_profile()
-                        for _ in range(N):
-                            s2.aggregate(cost, layout=layout, out=res, stream=s2.stream)
-                        torch.cuda.synchronize(DEV)
-                        n, total, _ = s2.get_profile()["vol_import"]
-                        s2.set_profiling(False)
+                        n, total, _ = profile_of(s2, lambda: s2.aggregate(cost, layout=layout, out=res,
+                                                                          stream=s2.stream), N, warm=1)["vol_import"]
                         moved = nvol * (eb + 8)
                         print(f"{h}x{w}x{D} {layout} {str(dt)[6:]:8s} both : {total / n:7.3f} ms (mean of {n})  "
                               f"{moved / 1e6:8.1f} MB  {moved / (total / n) / 1e9:5.2f} TB/s (source counted once)")
@@ -93,12 +71,12 @@ def main():
             d_l, d_r = torch.from_numpy(left).to(DEV), torch.from_numpy(right).to(DEV)
             res = torch.empty((h, w), dtype=torch.float32, device=DEV)
             f = timed(stream, lambda: s.process_device(d_l.data_ptr(), d_r.data_ptr(), res.data_ptr(), stream=s.stream))
-            print(f"K128 views={views} process_device frame: {f[0]:7.3f} ms ({f[1]:.3f}..{f[2]:.3f})")
+            print(f"K128 views={views} process_device frame: {fmt(f)}")
             for layout, dt in (("dhw", torch.float16), ("dhw", torch.float32), ("hwd", torch.float32)):
                 shape = (h, w, D) if layout == "hwd" else (D, h, w)
                 cost = (torch.rand(shape, device=DEV) * 64).to(dt)
                 a = timed(stream, lambda: s.aggregate(cost, layout=layout, out=res, stream=s.stream))
-                print(f"K128 views={views} aggregate({layout} {str(dt)[6:]}): {a[0]:7.3f} ms ({a[1]:.3f}..{a[2]:.3f})")
+                print(f"K128 views={views} aggregate({layout} {str(dt)[6:]}): {fmt(a)}")
             s.check()
 
 

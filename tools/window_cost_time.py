@@ -15,36 +15,21 @@ count bytes read and written.
 """
 from __future__ import annotations
 
-import ctypes
-import statistics
+import functools
 import sys
 
 import torch
 
+import event_time
+from event_time import DEV, class_means, fmt, profile_of
 from stereo_matching_amd import SGM, _capi, synthetic
 
-DEV = torch.device("cuda", 0)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 25
-
-
-def timed(stream, fn, n=N, warm=3):
-    ms = []
-    for k in range(warm + n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record(stream)
-            fn()
-            b.record(stream)
-        b.synchronize()
-        if k >= warm:
-            ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
+timed = functools.partial(event_time.timed, n=N)
 
 
 def main():
     _capi.lib()
-    hip = ctypes.CDLL(_capi.hip_runtimes()[0])
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     print(f"# median of {N} (min..max), HIP events around the call")
     for h, w, D in ((375, 1242, 128), (1080, 1920, 256)):
         left, right = synthetic.stereo_pair(h, w, D, pair_index=0)
@@ -54,16 +39,16 @@ def main():
             d_l, d_r = torch.from_numpy(left).to(DEV), torch.from_numpy(right).to(DEV)
             out = torch.empty((h, w, D), dtype=torch.float32, device=DEV)
             twin = torch.rand((h, w, D), dtype=torch.float32, device=DEV)
-            copy = timed(stream, lambda: hip.hipMemcpyAsync(out.data_ptr(), twin.data_ptr(), nvol * 4, 3,
-                                                             ctypes.c_void_p(s.stream)))
-            print(f"{h}x{w}x{D} memcpy d2d {nvol * 4 / 1e6:8.1f} MB out: {copy[0]:7.3f} ms ({copy[1]:.3f}..{copy[2]:.3f})  "
+            d2d = event_time.d2d_copy(s.stream)
+            copy = timed(stream, lambda: d2d(out.data_ptr(), twin.data_ptr(), nvol * 4))
+            print(f"{h}x{w}x{D} memcpy d2d {nvol * 4 / 1e6:8.1f} MB out: {fmt(copy)}  "
                   f"{2 * nvol * 4 / copy[0] / 1e9:5.2f} TB/s read + written")
             imp = timed(stream, lambda: s.import_volume(twin, 0, layout="hwd", out=out, stream=s.stream))
-            print(f"{h}x{w}x{D} import hwd float32 left: {imp[0]:7.3f} ms ({imp[1]:.3f}..{imp[2]:.3f})  "
+            print(f"{h}x{w}x{D} import hwd float32 left: {fmt(imp)}  "
                   f"{imp[0] / copy[0]:5.2f} x the copy")
             for kind in ("sad", "ssd"):
                 t = timed(stream, lambda: s.window_cost(d_l, d_r, kind, out=out, stream=s.stream))
-                print(f"{h}x{w}x{D} window_cost {kind}: {t[0]:7.3f} ms ({t[1]:.3f}..{t[2]:.3f})  "
+                print(f"{h}x{w}x{D} window_cost {kind}: {fmt(t)}  "
                       f"{nvol * 4 / t[0] / 1e9:5.2f} TB/s written  {t[0] / copy[0]:5.2f} x the copy  "
                       f"{t[0] / imp[0]:5.2f} x the import")
             del out, twin
@@ -85,21 +70,14 @@ def main():
                 s.aggregate(vol, layout="hwd", out=res, stream=s.stream)
 
             c = timed(stream, frame)
-            print(f"K128 views={views} census frame:               {c[0]:7.3f} ms ({c[1]:.3f}..{c[2]:.3f})")
+            print(f"K128 views={views} census frame:               {fmt(c)}")
             t = timed(stream, two_calls)
-            print(f"K128 views={views} window_cost -> aggregate:   {t[0]:7.3f} ms ({t[1]:.3f}..{t[2]:.3f})")
+            print(f"K128 views={views} window_cost -> aggregate:   {fmt(t)}")
             s.set_cost("sad")
             f = timed(stream, frame)
-            print(f"K128 views={views} SAD frame:                  {f[0]:7.3f} ms ({f[1]:.3f}..{f[2]:.3f})")
-            s.set_profiling(True)
-            s.get_profile()
-            for _ in range(N):
-                frame()
-            torch.cuda.synchronize(DEV)
-            prof = s.get_profile()
-            s.set_profiling(False)
+            print(f"K128 views={views} SAD frame:                  {fmt(f)}")
             print("    per launch class (mean ms): " +
-                  ", ".join(f"{k} {v[1] / v[0]:.3f}" for k, v in prof.items()))
+                  ", ".join(f"{k} {v:.3f}" for k, v in class_means(profile_of(s, frame, N)).items()))
             s.check()
 
 

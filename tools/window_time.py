@@ -11,43 +11,25 @@ through SGM_HIP_LIB and its own tree) is timed at its fixed 7x9 with
 """
 from __future__ import annotations
 
-import ctypes
-import statistics
+import functools
 import sys
 
 import torch
 
+import event_time
+from event_time import DEV
 from stereo_matching_amd import SGM, _capi, synthetic
 
-DEV = torch.device("cuda", 0)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 N = int(ARGS[0]) if ARGS else 25
 DEFAULT_ONLY = "--default-only" in sys.argv
 WINDOWS = [(7, 9)] if DEFAULT_ONLY else [(7, 9), (3, 3), (5, 5), (9, 7)]
-
-
-def timed(stream, fn, n=N, warm=3):
-    ms = []
-    for k in range(warm + n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record(stream)
-            fn()
-            b.record(stream)
-        b.synchronize()
-        if k >= warm:
-            ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
-
-
-def fmt(t):
-    return f"{t[0]:7.4f} ms ({t[1]:.4f}..{t[2]:.4f})"
+timed = functools.partial(event_time.timed, n=N)
+fmt = functools.partial(event_time.fmt, digits=4)
 
 
 def main():
     _capi.lib()
-    hip = ctypes.CDLL(_capi.hip_runtimes()[0])
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     print(f"# median of {N} (min..max), HIP events around the call")
     h, w, D = 375, 1242, 128
     left, right = synthetic.stereo_pair(h, w, D, pair_index=0)
@@ -58,8 +40,8 @@ def main():
         out = torch.empty((h, w, D), dtype=torch.float32, device=DEV)
         twin = torch.rand((h, w, D), dtype=torch.float32, device=DEV)
         nvol = h * w * D
-        copy = timed(stream, lambda: hip.hipMemcpyAsync(out.data_ptr(), twin.data_ptr(), nvol * 4, 3,
-                                                         ctypes.c_void_p(s.stream)))
+        d2d = event_time.d2d_copy(s.stream)
+        copy = timed(stream, lambda: d2d(out.data_ptr(), twin.data_ptr(), nvol * 4))
         print(f"{h}x{w}x{D} memcpy d2d {nvol * 4 / 1e6:.1f} MB out: {fmt(copy)}")
 
         def frame():
@@ -71,14 +53,7 @@ def main():
             name = f"{win[0]}x{win[1]}"
             f = timed(stream, frame)
             print(f"K128 views=1 census frame, window {name}: {fmt(f)}")
-            s.set_profiling(True)
-            s.get_profile()
-            for _ in range(N):
-                frame()
-            torch.cuda.synchronize(DEV)
-            prof = s.get_profile()
-            s.set_profiling(False)
-            c = prof["census"]
+            c = event_time.profile_of(s, frame, N)["census"]
             print(f"    census launch (both images, {h}x{w}), window {name}: {c[1] / c[0]:.4f} ms mean of {c[0]}")
             for kind in ("sad", "ssd"):
                 t = timed(stream, lambda: s.window_cost(d_l, d_r, kind, out=out, stream=s.stream))
