@@ -1,10 +1,11 @@
 // sgm_capi.hip -- the C-ABI of libsgm_hip.so (include/sgm_hip.h).
 //
-// Parameter checks, sgm_create / sgm_destroy and the setters, the extern "C"
-// entry points and the sgm_stage_* functions of the parity tests.  The input
-// stage's part of the C-ABI is in sgm_input.hip; what a frame enqueues is in
-// sgm_frame.hip; sgm_create picks its schedule (enum Schedule, sgm_handle.h)
-// once.
+// sgm_create / sgm_destroy and the setters, the extern "C" entry points and the
+// sgm_stage_* functions of the parity tests.  The input stage's part of the
+// C-ABI is in sgm_input.hip; what a frame enqueues is in sgm_frame.hip.
+// sgm_create checks the parameters and plans the handle (valid_params,
+// plan_handle: sgm_plan.h) before it allocates; the plan sizes the buffers and
+// is the schedule of every frame.
 // All device memory is allocated at sgm_create (the reference allocates its
 // scratch in the constructors, Solver.cpp:18-27 and SGM.cpp:7-24), apart from
 // the maps the setters switch on and off.
@@ -12,84 +13,12 @@
 #include "sgm_volume_args.h"
 #include "sgm_window_cost_args.h"
 
-#include <float.h>
 #include <stdlib.h>
 #include <new>
 
 using namespace sgm;
 
 namespace {
-
-bool valid_params(const sgm_params *p, char *why, size_t n) {
-    if (!p) { snprintf(why, n, "params is NULL"); return false; }
-    // Solver.cpp:6-10 (d widened to 256), plus the filter windows' minimum size.
-    if (p->height <= 0 || p->width <= 0 || p->scale <= 0 || p->max_disp <= 0) {
-        snprintf(why, n, "h, w, s, d must be > 0 (Solver.cpp:6)");
-        return false;
-    }
-    if (p->scale != 1 && p->scale != 2) { snprintf(why, n, "scale must be 1 or 2 (Solver.cpp:8)"); return false; }
-    if (p->max_disp != 32 && p->max_disp != 64 && p->max_disp != 128 && p->max_disp != 256) {
-        snprintf(why, n, "max_disp must be 32, 64, 128 or 256 (Solver.cpp:10, widened)");
-        return false;
-    }
-    const int H = p->height / p->scale, W = p->width / p->scale;
-    if (W < 5 || H < 3) { snprintf(why, n, "working size %dx%d below the 5x3 cost window", H, W); return false; }
-    if (p->views != 1 && p->views != 2) { snprintf(why, n, "views must be 1 or 2"); return false; }
-    if (p->paths != 0 && p->paths != 4 && p->paths != 8) {
-        snprintf(why, n, "paths must be 8 (or 0) or 4 (USE_8_PATH, inc/SGM.h:7)");
-        return false;
-    }
-    // SGM.cpp:374-408 keeps the previous pixel's sec_min_d when a pixel has no
-    // second distinct cost; that stale index decides a pixel when
-    // min/FLT_MAX > UNIQUE_RATIO.  A path cost is at most C + P2 (SGM.cpp:
-    // 93-117: L = min(...) + C - minLp <= P2 + C), C at most 999999 (the sky
-    // override, Solver.cpp:167-176), so min <= 8 (P2 + 999999); a ratio above
-    // that / FLT_MAX can never see the stale index, which this build's WTA
-    // does not keep.  Ratios at or below it (0 and negatives included) are
-    // rejected.
-    if (!(p->uniqueness > 0.0f) ||
-        (double)p->uniqueness * FLT_MAX <= 8.0 * ((double)p->p2 + 999999.0)) {
-        snprintf(why, n, "uniqueness must be > 8*(p2 + 999999)/FLT_MAX (SGM.cpp:392-408 would read "
-                         "the previous pixel's sec_min_d)");
-        return false;
-    }
-    if (p->view != SGM_VIEW_LEFT && p->view != SGM_VIEW_RIGHT) {
-        snprintf(why, n, "view must be SGM_VIEW_LEFT or SGM_VIEW_RIGHT");
-        return false;
-    }
-    if (p->view == SGM_VIEW_RIGHT &&
-        (p->views != 1 || p->solver != SGM_SOLVER_SGM || p->post_filter || p->lk_refine)) {
-        snprintf(why, n, "SGM_VIEW_RIGHT needs views == 1, the SGM solver and no post_filter/lk_refine");
-        return false;
-    }
-    // the sky detector keeps a row of borders (W <= 8192) and the top half of a
-    // 64-column strip (H/2 + 2 rows of 68 B <= ~159 KiB) in LDS (sgm_sky.hip)
-    if (p->sky_detect && (W > 8192 || (size_t)(H / 2 + 2) * 68 > 160 * 1024 - 1024)) {
-        snprintf(why, n, "sky_detect supports working grids up to 8192 x %d", 2 * ((160 * 1024 - 1024) / 68 - 2));
-        return false;
-    }
-    if (p->solver != SGM_SOLVER_SGM && p->solver != SGM_SOLVER_BM) {
-        snprintf(why, n, "solver must be SGM_SOLVER_SGM or SGM_SOLVER_BM");
-        return false;
-    }
-    // the path DP's start handling relies on non-negative penalties (SGM.cpp:27-28 uses 10, 100)
-    if (p->p1 < 0 || p->p2 < 0) { snprintf(why, n, "p1 and p2 must be >= 0"); return false; }
-    if ((size_t)H * W > (size_t)0x7fffffff) { snprintf(why, n, "image too large"); return false; }
-    return true;
-}
-
-// The aggregation schedule of every frame of a handle (sgm_frame.hip
-// run_frame; BM and aux_only handles never read it), by volume size against
-// the 256 MB Infinity Cache.
-Schedule schedule_for(const sgm_handle *h) {
-    const double vol_bytes = vol_elems(h->g) * sizeof(float), cache = 256.0 * 1024 * 1024;
-    if (h->paths4) return SCHED_PATHS4;
-    if (h->slant) return SCHED_SLANT;
-    if (h->nviews == 2 && h->band_rows == 0 && 2.0 * vol_bytes <= cache) return SCHED_JOINT;
-    if (h->band_rows > 0) return SCHED_BANDS;
-    if (h->nviews == 2 && vol_bytes > cache) return SCHED_WHOLE_FINAL2;
-    return SCHED_PER_VIEW;
-}
 
 // Frees what the handle owns (it is deleted next): every dalloc still on the
 // list, then the host-pinned buffers, streams and events.
@@ -107,6 +36,160 @@ void free_all(sgm_handle *h) {
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     h->pending.clear();
     h->ev_pool.clear();
+}
+
+// sgm_create's steps, in its order; each returns an rc, with the reason in
+// h->err where there is one.  (The order of the device allocations is kept as
+// it ever was: inputs, per-view buffers, common buffers, the slanted
+// schedule's.)
+
+int create_streams(sgm_handle *h) {
+    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) return SGM_ERR_HIP;
+    hipEvent_t *evs[] = {&h->ev_pf, &h->ev_last};
+    for (auto e : evs) {
+        // stream-to-stream ordering on this device needs no system-scope
+        // fence (L2 writeback/invalidate); the post filter's host
+        // readback (ev_pf) keeps it
+        const unsigned fl = hipEventDisableTiming | (e == &h->ev_pf ? 0u : hipEventDisableSystemFence);
+        if (hipEventCreateWithFlags(e, fl) != hipSuccess) return SGM_ERR_HIP;
+    }
+    return SGM_OK;
+}
+
+// Every handle's input buffers: the staged images, the sky masks, the census tables.
+int alloc_inputs(sgm_handle *h) {
+    const size_t npx = (size_t)h->g.H * h->g.W, nin = (size_t)h->p.height * h->p.width;
+    for (int v = 0; v < 2; ++v) {
+        if (int rc = dalloc(h, &h->d_in[v], nin)) return rc;
+        if (int rc = dalloc(h, &h->d_sky[v], npx)) return rc;
+        if (int rc = dalloc(h, &h->d_ct[v], npx)) return rc;
+        h->d_cts[v] = h->d_ct[v];  // (min_disp = 0: the tables themselves)
+    }
+    return SGM_OK;
+}
+
+// Each view's volumes, maps, checkpoints and band carries (aux_only handles:
+// the side stages' maps alone).
+int alloc_views(sgm_handle *h) {
+    const Geom g = h->g;
+    const size_t npx = (size_t)g.H * g.W, nvol = npx * g.D;
+    const bool paths4 = h->plan.paths4;
+    for (int v = 0; v < (h->p.aux_only ? 0 : h->nviews); ++v) {
+        // the final pass addresses T (which reuses d_ch) in chunks from
+        // their top row, which for the partial last chunk lies up to K-1
+        // rows above row 0: d_ch carries that guard in front; the
+        // row-walking passes prefetch up to PF positions past the end of
+        // the last row of C (never consumed): both carry kVolGuard behind
+        const size_t guard = (size_t)sgm::t_guard_rows(g.D) * g.W * g.D;
+        if (int rc = dalloc(h, &h->d_ch_base[v], guard + nvol + sgm::kVolGuard)) return rc;
+        h->d_ch[v] = h->d_ch_base[v] + guard;
+        if (int rc = dalloc(h, &h->d_c[v], nvol + sgm::kVolGuard)) return rc;
+        if (int rc = dalloc(h, &h->d_s[v], nvol)) return rc;
+        if (int rc = dalloc(h, &h->d_disp[v], npx)) return rc;
+        if (int rc = dalloc(h, &h->d_sub[v], npx)) return rc;
+        // (a 4-path handle has no diagonal pair and never runs bands)
+        for (int f = 0; f < 3; ++f)
+            if (!(paths4 && f == sgm::PAIR_D2))
+                if (int rc = dalloc(h, &h->d_ck[v][f], sgm::pair_ckpt_floats(f, g))) return rc;
+        // slot 2 also holds vfwd's forward-band state (3 D-vectors per column)
+        for (int f = 0; f < 3 && !paths4; ++f)
+            if (int rc = dalloc(h, &h->d_carry[v][f], (size_t)g.W * g.D * (f == 2 ? 3 : 1))) return rc;
+    }
+    if (h->p.aux_only) {  // the side stages' maps (stage_lr, the raw map copy)
+        for (int v = 0; v < 2; ++v) {
+            if (int rc = dalloc(h, &h->d_disp[v], npx)) return rc;
+            if (int rc = dalloc(h, &h->d_sub[v], npx)) return rc;
+        }
+    } else if (h->nviews == 1) {  // stage_lr needs a second sub-pixel map
+        if (int rc = dalloc(h, &h->d_sub[1], npx)) return rc;
+    }
+    return SGM_OK;
+}
+
+// What every handle has beside them: the output map, the zero page, the
+// scratch of the post filter, LKRefine, the sky detector and the point cloud.
+int alloc_common(sgm_handle *h) {
+    const size_t npx = (size_t)h->g.H * h->g.W;
+    int rc = dalloc(h, &h->d_cloud_counts, (size_t)h->g.H + 1);
+    if (!rc) rc = dalloc(h, &h->d_out, npx);
+    if (!rc) rc = dalloc(h, &h->d_min, npx);
+    if (!rc) rc = dalloc(h, &h->d_zero, 256);
+    if (!rc) rc = dalloc(h, &h->d_pf_orig, npx);
+    if (!rc) rc = dalloc(h, &h->d_pf_work, npx);
+    if (!rc) rc = dalloc(h, &h->d_pf_label, npx);
+    if (!rc) rc = dalloc(h, &h->d_pf_count, npx);
+    if (!rc) rc = dalloc(h, &h->d_pf_area, npx);
+    if (!rc) rc = dalloc(h, &h->d_pf_snap, sgm::post_snapshot_floats(h->g));
+    if (!rc) rc = dalloc(h, &h->d_lk_in, npx);
+    if (!rc) rc = dalloc(h, &h->d_sky_scratch, 2 * sgm::sky_scratch_bytes(h->g));
+    if (!rc) rc = dalloc(h, &h->d_pf_changes, (size_t)kMedianMaxLaunches);
+    if (rc) return rc;
+    if (hipHostMalloc((void **)&h->h_pf_changes, sizeof(int), hipHostMallocDefault) != hipSuccess)
+        return set_err(h, SGM_ERR_HIP, "hipHostMalloc of the post-filter counter failed");
+    if (hipHostMalloc((void **)&h->h_pf_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&h->d_pf_err, h->h_pf_err, 0) != hipSuccess)
+        return set_err(h, SGM_ERR_HIP, "hipHostMalloc of the post filter's verdict word failed");
+    *h->h_pf_err = 0;
+    return SGM_OK;
+}
+
+// The slanted schedule's buffers (plan.slant), last: its two large ones, the L3
+// volumes and the hand-off granules (about 28 GB for a 4K256 pair, whose whole
+// handle is about 80 GB: INTEGRATION.md 5), come after every other buffer, so
+// that the fallback covers any shortage they cause.  Where the schedule was
+// chosen by size, not asked for (plan.slant_forced), and the device cannot hold
+// them, the handle is planned again without it -- the banded schedule,
+// bit-identical maps, no extra volume -- instead of failing sgm_create.
+int alloc_slant(sgm_handle *h) {
+    if (!h->plan.slant) return SGM_OK;
+    const size_t nvol = (size_t)h->g.H * h->g.W * h->g.D, ng = sgm::slant_gran_count(h->g, h->nviews);
+    int rc = SGM_OK;
+    for (int v = 0; v < h->nviews && !rc; ++v) rc = dalloc(h, &h->d_l3[v], nvol);
+    if (!rc) rc = dalloc(h, &h->d_gran, ng);
+#ifdef SGM_SLANT_DEBUG
+    if (!rc && getenv("SGM_SLANT_NO_MEMORY"))  // (tests the fallback below)
+        rc = set_err(h, SGM_ERR_HIP, "hipMalloc: out of memory (forced, SGM_SLANT_NO_MEMORY)");
+#endif
+    if (rc && !h->plan.slant_forced) {
+        for (int v = 0; v < 2; ++v) dfree(h, &h->d_l3[v], nvol);
+        dfree(h, &h->d_gran, ng);
+        (void)hipGetLastError();  // (the failed hipMalloc's error is not the next launch's)
+        h->err[0] = 0;
+        h->plan = sgm::plan_without_slant(h->plan);
+        return SGM_OK;
+    }
+    if (!rc) rc = dalloc(h, &h->d_slant_ctl, 2);
+    if (!rc) rc = dalloc(h, &h->d_slant_dummy, 512);
+    if (rc) return rc;
+    if (hipHostMalloc((void **)&h->h_slant_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&h->d_slant_err, h->h_slant_err, 0) != hipSuccess)
+        return set_err(h, SGM_ERR_HIP, "hipHostMalloc of the slanted schedule's hang-guard word failed");
+    *h->h_slant_err = 0;
+    // (the H pair's stream beside the top-down pass, its fork and join)
+    if (hipStreamCreateWithFlags(&h->st_h, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess)
+        return set_err(h, SGM_ERR_HIP, "creating the slanted schedule's H-pair stream failed");
+    return SGM_OK;
+}
+
+// What has to read as zero before the first frame.
+int clear_buffers(sgm_handle *h) {
+    if (hipMemset(h->d_zero, 0, 256 * sizeof(float)) != hipSuccess)
+        return set_err(h, SGM_ERR_HIP, "hipMemset of the zero page failed");
+    if (h->plan.slant &&
+        (hipMemset(h->d_gran, 0, sgm::slant_gran_count(h->g, h->nviews) * sizeof(unsigned long long)) != hipSuccess ||
+         hipMemset(h->d_slant_ctl, 0, 2 * sizeof(sgm::SlantCtl)) != hipSuccess))
+        return set_err(h, SGM_ERR_HIP, "hipMemset of the slanted schedule's hand-off state failed");
+    return SGM_OK;
+}
+
+// SGM_CONFIDENCE=1: handles start with the confidence maps on (timing the
+// feature's cost under tools that create their own handles, tools/ab_env.sh)
+int start_confidence(sgm_handle *h) {
+    const char *e = getenv("SGM_CONFIDENCE");
+    if (!e || *e != '1' || h->p.aux_only || h->p.solver != SGM_SOLVER_SGM) return SGM_OK;
+    return sgm_set_confidence(h, 1) != SGM_OK ? SGM_ERR_OUT_OF_MEMORY : SGM_OK;
 }
 
 // Pinned staging for the host-buffer API: user rows are packed into pinned
@@ -178,23 +261,7 @@ extern "C" {
 
 int sgm_default_params(sgm_params *p, int h, int w, int s, int d) {
     if (!p) return SGM_ERR_INVALID_ARG;
-    p->height = h;
-    p->width = w;
-    p->scale = s;
-    p->max_disp = d;
-    p->p1 = 10;              // SGM.cpp:27
-    p->p2 = 100;             // SGM.cpp:28
-    p->uniqueness = 0.7f;    // inc/Solver.h:14
-    p->lr_max_diff = 1.0f;   // inc/Solver.h:16
-    p->blur = 1;             // Solver.cpp:124-125
-    p->views = 2;            // SGM.cpp:448-818
-    p->post_filter = 0;      // out = LR-checked map (SGM.cpp:818); 1: + post_filter (:821)
-    p->lk_refine = 0;        // 1: + LKRefine (SGM.cpp:824, commented out in the reference)
-    p->sky_detect = 0;       // 1: masks from SkyAreaDetector::detect on the GPU (node.cpp:80-93)
-    p->solver = SGM_SOLVER_SGM;
-    p->aux_only = 0;
-    p->view = SGM_VIEW_LEFT;
-    p->paths = 8;            // USE_8_PATH = true (inc/SGM.h:7)
+    sgm::default_params(p, h, w, s, d);
     return SGM_OK;
 }
 
@@ -215,182 +282,29 @@ int sgm_create(const sgm_params *p, int device, sgm_handle **out) {
     if (!h) return SGM_ERR_OUT_OF_MEMORY;
     h->p = *p;
     h->device = device;
-    h->g.scale = p->scale;
-    h->g.H = p->height / p->scale;
-    h->g.W = p->width / p->scale;
-    h->g.D = p->max_disp;
+    h->plan = plan_handle(*p, slant_cus(), plan_env());
+    h->g = h->plan.g;
     h->gt = h->g;  // (min_disp = 0 until sgm_set_min_disp)
+    h->nviews = h->plan.nviews;
     h->win_h = sgm::kWinH;  // (the reference's window until sgm_set_window)
     h->win_w = sgm::kWinW;
     h->win = sgm::default_window(h->g.scale);
-    h->nviews = p->views;
-    const size_t npx = (size_t)h->g.H * h->g.W;
-    const size_t nvol = npx * h->g.D;
-    const size_t nin = (size_t)p->height * p->width;
     h->mf_rows = sgm::median_rows_default(h->g);
-    // the 4-path schedule (BM and aux_only handles aggregate nothing: ignored)
-    h->paths4 = p->paths == 4 && !p->aux_only && p->solver == SGM_SOLVER_SGM;
-    if (h->paths4) {
-        // Its one choice by size, forced either way by SGM_P4_HPAIR (read
-        // here): the H pair as one launch of one-wave rows (0),
-        // or as a forward launch and a backward launch of two-wave rows (1).
-        // With fewer rows in the launch than the device has SIMDs each SIMD
-        // holds at most one chain and the pair's time is its chain latency,
-        // which the two-wave rows cut (K128 one view 299 -> 235 us, two views
-        // 376 -> 336, K64 two views 278 -> 189); with more rows the SIMDs are
-        // filled either way and the single launch measured faster (HD256 two
-        // views 2585 vs 2679 us; profiles/paths4_timing.txt)
-        const char *e = getenv("SGM_P4_HPAIR");
-        h->p4_split = e && (*e == '0' || *e == '1') ? *e == '1'
-                                                    : (long long)h->nviews * h->g.H < 4LL * slant_cus();
-    }
-    int rc = SGM_OK;
-    do {
-        if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) { rc = SGM_ERR_HIP; break; }
-        hipEvent_t *evs[] = {&h->ev_pf, &h->ev_last};
-        for (auto e : evs) {
-            // stream-to-stream ordering on this device needs no system-scope
-            // fence (L2 writeback/invalidate); the post filter's host
-            // readback (ev_pf) keeps it
-            const unsigned fl = hipEventDisableTiming | (e == &h->ev_pf ? 0u : hipEventDisableSystemFence);
-            if (hipEventCreateWithFlags(e, fl) != hipSuccess) { rc = SGM_ERR_HIP; break; }
-        }
-        if (rc) break;
-        for (int v = 0; v < 2 && !rc; ++v) {
-            if ((rc = dalloc(h, &h->d_in[v], nin))) break;
-            if ((rc = dalloc(h, &h->d_sky[v], npx))) break;
-            if ((rc = dalloc(h, &h->d_ct[v], npx))) break;
-            h->d_cts[v] = h->d_ct[v];  // (min_disp = 0: the tables themselves)
-        }
-        for (int v = 0; v < (p->aux_only ? 0 : h->nviews) && !rc; ++v) {
-            // the final pass addresses T (which reuses d_ch) in chunks from
-            // their top row, which for the partial last chunk lies up to K-1
-            // rows above row 0: d_ch carries that guard in front; the
-            // row-walking passes prefetch up to PF positions past the end of
-            // the last row of C (never consumed): both carry kVolGuard behind
-            const size_t guard = (size_t)sgm::t_guard_rows(h->g.D) * h->g.W * h->g.D;
-            if ((rc = dalloc(h, &h->d_ch_base[v], guard + nvol + sgm::kVolGuard))) break;
-            h->d_ch[v] = h->d_ch_base[v] + guard;
-            if ((rc = dalloc(h, &h->d_c[v], nvol + sgm::kVolGuard))) break;
-            if ((rc = dalloc(h, &h->d_s[v], nvol))) break;
-            if ((rc = dalloc(h, &h->d_disp[v], npx))) break;
-            if ((rc = dalloc(h, &h->d_sub[v], npx))) break;
-            // (a 4-path handle has no diagonal pair and never runs bands)
-            for (int f = 0; f < 3 && !rc; ++f)
-                if (!(h->paths4 && f == sgm::PAIR_D2))
-                    rc = dalloc(h, &h->d_ck[v][f], sgm::pair_ckpt_floats(f, h->g));
-            // slot 2 also holds vfwd's forward-band state (3 D-vectors per column)
-            for (int f = 0; f < 3 && !rc && !h->paths4; ++f)
-                rc = dalloc(h, &h->d_carry[v][f], (size_t)h->g.W * h->g.D * (f == 2 ? 3 : 1));
-        }
-        h->band_rows = h->paths4 ? 0 : band_rows_for(h->g);
-        if (!rc && p->aux_only) {  // the side stages' maps (stage_lr, the raw map copy)
-            for (int v = 0; v < 2 && !rc; ++v) {
-                if ((rc = dalloc(h, &h->d_disp[v], npx))) break;
-                rc = dalloc(h, &h->d_sub[v], npx);
-            }
-        } else if (!rc && h->nviews == 1) {  // stage_lr needs a second sub-pixel map
-            rc = dalloc(h, &h->d_sub[1], npx);
-        }
-        if (!rc) rc = dalloc(h, &h->d_cloud_counts, (size_t)h->g.H + 1);
-        if (!rc) rc = dalloc(h, &h->d_out, npx);
-        if (!rc) rc = dalloc(h, &h->d_min, npx);
-        if (!rc) rc = dalloc(h, &h->d_zero, 256);
-        if (!rc) rc = dalloc(h, &h->d_pf_orig, npx);
-        if (!rc) rc = dalloc(h, &h->d_pf_work, npx);
-        if (!rc) rc = dalloc(h, &h->d_pf_label, npx);
-        if (!rc) rc = dalloc(h, &h->d_pf_count, npx);
-        if (!rc) rc = dalloc(h, &h->d_pf_area, npx);
-        if (!rc) rc = dalloc(h, &h->d_pf_snap, sgm::post_snapshot_floats(h->g));
-        if (!rc) rc = dalloc(h, &h->d_lk_in, npx);
-        if (!rc) rc = dalloc(h, &h->d_sky_scratch, 2 * sgm::sky_scratch_bytes(h->g));
-        if (!rc) rc = dalloc(h, &h->d_pf_changes, (size_t)kMedianMaxLaunches);
-        if (!rc && hipHostMalloc((void **)&h->h_pf_changes, sizeof(int), hipHostMallocDefault) !=
-                       hipSuccess)
-            rc = set_err(h, SGM_ERR_HIP, "hipHostMalloc of the post-filter counter failed");
-        if (!rc && (hipHostMalloc((void **)&h->h_pf_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
-                    hipHostGetDevicePointer((void **)&h->d_pf_err, h->h_pf_err, 0) != hipSuccess))
-            rc = set_err(h, SGM_ERR_HIP, "hipHostMalloc of the post filter's verdict word failed");
-        if (!rc) *h->h_pf_err = 0;
-        if (!rc && hipMemset(h->d_zero, 0, 256 * sizeof(float)) != hipSuccess)
-            rc = set_err(h, SGM_ERR_HIP, "hipMemset of the zero page failed");
-        bool slant_forced = false;
-        {
-            // the slanted schedule: by size (slant_default), SGM_SLANT=1/0
-            // forces it on/off (the parity tests run it at every size)
-            const char *e = getenv("SGM_SLANT");
-            slant_forced = e && *e == '1';
-            const bool want = e && *e ? slant_forced : slant_default(h->g, h->nviews);
-            h->slant = !p->aux_only && p->solver == SGM_SOLVER_SGM && want && !h->paths4;
-            if (h->paths4) slant_forced = false;  // (SGM_SLANT is ignored: the tiles are built around L5..L8)
-            const char *ev = getenv("SGM_VSTRIP");
-            h->vstrip = !(ev && *ev == '0');
-        }
-        const size_t ng = h->slant ? sgm::slant_gran_count(h->g, h->nviews) : 0;
-        if (!rc && h->slant) {
-            // its two large buffers: the L3 volumes and the hand-off granules
-            // (about 28 GB for a 4K256 pair, whose whole handle is about 80 GB:
-            // INTEGRATION.md 5), allocated after every common buffer, so that
-            // the fallback below covers any shortage they cause
-            int arc = SGM_OK;
-            for (int v = 0; v < h->nviews && !arc; ++v) arc = dalloc(h, &h->d_l3[v], nvol);
-            if (!arc) arc = dalloc(h, &h->d_gran, ng);
-#ifdef SGM_SLANT_DEBUG
-            if (!arc && getenv("SGM_SLANT_NO_MEMORY"))  // (tests the fallback below)
-                arc = set_err(h, SGM_ERR_HIP, "hipMalloc: out of memory (forced, SGM_SLANT_NO_MEMORY)");
-#endif
-            if (arc && !slant_forced) {
-                // chosen by size, not asked for: when the device cannot hold
-                // them, the banded schedule (bit-identical maps, no extra
-                // volume) instead of failing sgm_create
-                for (int v = 0; v < 2; ++v) dfree(h, &h->d_l3[v], nvol);
-                dfree(h, &h->d_gran, ng);
-                (void)hipGetLastError();  // (the failed hipMalloc's error is not the next launch's)
-                h->err[0] = 0;
-                h->slant = false;
-            } else {
-                rc = arc;
-            }
-        }
-        if (!rc && h->slant) {
-            if (!rc) rc = dalloc(h, &h->d_slant_ctl, 2);
-            if (!rc) rc = dalloc(h, &h->d_slant_dummy, 512);
-            if (!rc && (hipHostMalloc((void **)&h->h_slant_err, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
-                        hipHostGetDevicePointer((void **)&h->d_slant_err, h->h_slant_err, 0) != hipSuccess))
-                rc = set_err(h, SGM_ERR_HIP, "hipHostMalloc of the slanted schedule's hang-guard word failed");
-            if (!rc) *h->h_slant_err = 0;
-            if (!rc && (hipStreamCreateWithFlags(&h->st_h, hipStreamNonBlocking) != hipSuccess ||
-                        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
-                        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess))
-                rc = set_err(h, SGM_ERR_HIP, "creating the slanted schedule's H-pair stream failed");
-            if (!rc && (hipMemset(h->d_gran, 0, ng * sizeof(unsigned long long)) != hipSuccess ||
-                        hipMemset(h->d_slant_ctl, 0, 2 * sizeof(sgm::SlantCtl)) != hipSuccess))
-                rc = set_err(h, SGM_ERR_HIP, "hipMemset of the slanted schedule's hand-off state failed");
-        }
-    } while (0);
+
+    int rc = create_streams(h);
+    if (!rc) rc = alloc_inputs(h);
+    if (!rc) rc = alloc_views(h);
+    if (!rc) rc = alloc_common(h);
+    if (!rc) rc = alloc_slant(h);  // (may leave the slanted schedule: h->plan is final after it)
+    if (!rc) rc = clear_buffers(h);
+    if (!rc) rc = start_confidence(h);
     if (rc) {
         fprintf(stderr, "sgm_create: %s\n", h->err[0] ? h->err : "HIP stream/event creation failed");
         free_all(h);
         delete h;
         return rc;
     }
-    // (after the fallback above: it can leave the slanted schedule)
-    h->sched = schedule_for(h);
-    // two views: the final passes write column-major sub-pixel maps (whole
-    // cache lines; lr_cm_kernel reads them through LDS tiles); the slanted
-    // pass writes row-major ones
-    h->sub_cm = h->nviews == 2 && !h->slant;
     *out = h;
-    // SGM_CONFIDENCE=1: handles start with the confidence maps on (timing the
-    // feature's cost under tools that create their own handles, tools/ab_env.sh)
-    if (const char *e = getenv("SGM_CONFIDENCE"))
-        if (*e == '1' && !p->aux_only && p->solver == SGM_SOLVER_SGM && sgm_set_confidence(h, 1) != SGM_OK) {
-            fprintf(stderr, "sgm_create: %s\n", h->err);
-            *out = nullptr;
-            free_all(h);
-            delete h;
-            return SGM_ERR_OUT_OF_MEMORY;
-        }
     return SGM_OK;
 }
 
@@ -654,19 +568,29 @@ int sgm_post_filter_proved_at(sgm_handle *h, int *launch) {
     return SGM_OK;
 }
 
+// The checks a frame's arguments pass before anything is enqueued (host or device pointers alike);
+// `fn`: the entry point's name, for the message.
+static int check_frame_args(sgm_handle *h, const char *fn, const uint8_t *left, const uint8_t *right, int pitch,
+                            const uint8_t *sky_l, const uint8_t *sky_r, int sky_pitch, const float *out,
+                            int out_pitch) {
+    if (!left || !right || !out || pitch < h->in.row_bytes(h->p.width) || out_pitch < h->g.W ||
+        ((sky_l || sky_r) && sky_pitch < h->g.W))
+        return set_err(h, SGM_ERR_INVALID_ARG, "%s: bad pointer or pitch", fn);
+    if (h->p.aux_only) return set_err(h, SGM_ERR_INVALID_ARG, "%s: handle created with aux_only", fn);
+    if (h->cost_kind != SGM_COST_CENSUS && (sky_l || sky_r))
+        return set_err(h, SGM_ERR_INVALID_ARG, "%s: sky masks have no meaning with a SAD or SSD cost (sgm_set_cost)",
+                       fn);
+    return SGM_OK;
+}
+
 int sgm_process_device(sgm_handle *h, const uint8_t *d_left, const uint8_t *d_right, int pitch,
                        const uint8_t *d_sky_l, const uint8_t *d_sky_r, int sky_pitch,
                        float *d_out, int out_pitch, uint16_t *d_raw_disp, void *stream) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (int rc = check_frame_err(h)) return rc;
-    if (!d_left || !d_right || !d_out || pitch < h->in.row_bytes(h->p.width) || out_pitch < h->g.W ||
-        ((d_sky_l || d_sky_r) && sky_pitch < h->g.W))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: bad pointer or pitch");
-    if (h->p.aux_only)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process_device: handle created with aux_only");
-    if (h->cost_kind != SGM_COST_CENSUS && (d_sky_l || d_sky_r))
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_process_device: sky masks have no meaning with a SAD or SSD cost (sgm_set_cost)");
+    if (int rc = check_frame_args(h, "sgm_process_device", d_left, d_right, pitch, d_sky_l, d_sky_r, sky_pitch, d_out,
+                                  out_pitch))
+        return rc;
     DeviceGuard guard(h->device);
     StreamScope scope(h, stream);
     return run_frame(h, {d_left, d_right, pitch, d_sky_l, d_sky_r, sky_pitch, d_out, out_pitch, d_raw_disp},
@@ -677,15 +601,8 @@ int sgm_process(sgm_handle *h, const uint8_t *left, const uint8_t *right, int pi
                 const uint8_t *sky_l, const uint8_t *sky_r, int sky_pitch, float *out,
                 int out_pitch, uint16_t *raw_disp) {
     if (!h) return SGM_ERR_INVALID_ARG;
-    if (!left || !right || !out || pitch < h->in.row_bytes(h->p.width) || out_pitch < h->g.W ||
-        ((sky_l || sky_r) && sky_pitch < h->g.W))
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: bad pointer or pitch");
-    if (h->p.aux_only)
-        return set_err(h, SGM_ERR_INVALID_ARG, "sgm_process: handle created with aux_only");
-    if (h->cost_kind != SGM_COST_CENSUS && (sky_l || sky_r))
-        return set_err(h, SGM_ERR_INVALID_ARG,
-                       "sgm_process: sky masks have no meaning with a SAD or SSD cost (sgm_set_cost)");
     int rc;
+    if ((rc = check_frame_args(h, "sgm_process", left, right, pitch, sky_l, sky_r, sky_pitch, out, out_pitch))) return rc;
     if ((rc = check_frame_err(h))) return rc;
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);
@@ -1009,7 +926,7 @@ int sgm_stage_cost(sgm_handle *h, const uint64_t *ctl, const uint64_t *ctr, cons
 int sgm_stage_path(sgm_handle *h, int dir, const float *cost, float *L, float *minL) {
     if (!h || !cost || !L || dir < 0 || dir > 7) return SGM_ERR_INVALID_ARG;
     if (h->p.aux_only) return set_err(h, SGM_ERR_INVALID_ARG, "stage needs cost volumes (aux_only)");
-    if (h->paths4 && dir >= SGM_DIR_L5)
+    if (h->plan.paths4 && dir >= SGM_DIR_L5)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_path: a 4-path handle serves L1..L4 only");
     DeviceGuard guard(h->device);
     StreamScope scope(h, nullptr);

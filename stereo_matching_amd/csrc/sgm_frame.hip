@@ -1,7 +1,7 @@
 // sgm_frame.hip -- everything that enqueues a frame: the cost stage, the six
-// aggregation schedules (enum Schedule, sgm_handle.h; DESIGN.md "Frame
-// schedule"), the LR check, post_filter and LKRefine, and the choices by frame
-// size that sgm_create makes for them (slant_default, band_rows_for).
+// aggregation schedules (DESIGN.md "Frame schedule"), the LR check, post_filter
+// and LKRefine.  Which schedule a handle's frames run is decided once, at
+// sgm_create, by plan_handle (sgm_plan.h); the frames read it from h->plan.
 // Concurrency between independent roles comes from sharing a launch (stage
 // A/B), not from streams (the runtime may map streams onto one hardware
 // queue): a frame runs on one stream, at 73.5 B of HBM traffic per
@@ -55,58 +55,8 @@ int sgm::vfwd_view(sgm_handle *h, int view, const float *in, float *out, double 
     return SGM_OK;
 }
 
-// The slanted-tile schedule replaces the bands (above the Infinity Cache)
-// where it was measured faster (tools/slant_sizes.py,
-// profiles/r04_experiments/slant.txt, with the H pair beside the top-down
-// pass): at D = 256 once views * W >= 0.5 * NW * CUs, i.e. half a full-height
-// tile of work per workgroup (round 6; 0.7 before), at D = 128 from 0.9
-// (round 4 at 0.7: HD256 two views -18.6%, 4K256 one view -20%,
-// two views -24%, 720p D = 256 two views -9.4%, HD128 two views -9.6%,
-// 4K128 two views -18.8%; HD256 one view +2.0%, HD128 one view +24.9%,
-// 1056x512 D = 128 two views +10.3%); never at D = 64 (HD64 two views
-// +16.8%, 4K64 +4.2%; round 5: +11.4%, +2.2%).  Below that the tile-to-tile
-// hand-off chain, not the bytes, sets the passes' time.  At D = 128 the
-// threshold is 0.9 tiles per workgroup (below).
-bool sgm::slant_default(Geom g, int nviews) {
-    if (vol_elems(g) * sizeof(float) <= 256.0 * 1024 * 1024 || g.D < 128) return false;
-    const int cus = slant_cus();
-    // round 5 re-sweep with the prioritised receiver (profiles/r05_experiments/
-    // r05m_slant_sizes.txt): 720p D = 256 two views (0.71 tiles per
-    // workgroup) -6.2%, but 720p D = 128 two views (0.71) +7.7%: at D = 128
-    // the crossover lies between 0.71 and HD128's 1.07 (-9.6%).  Round 6's
-    // dataflow passes (profiles/r06_experiments/r06c_sizes_sweep.txt,
-    // r06f_share_order_sweep.txt) moved D = 256 down: HD256 one view (0.54)
-    // -5.0..-9.7%; at D = 128, 720p two views (0.71) stays +5.3%, HD128 one
-    // view (0.54) +24%
-    return 10LL * nviews * g.W >= (g.D >= 256 ? 5LL : 9LL) * sgm::kSlantNW * cus;
-}
-
-// Rows per band of the backward phase (stage B's diagonal pair, the L8
-// sweep, the final pass) for cost volumes above the 256 MB Infinity Cache:
-// about 192 MB of cost volume per band, so that a band's C and T stay in the
-// cache from one pass to the next (tools/band_probe.hip: 1.27-1.35x for the
-// three passes' streams alone; in the frame HD256 -3.5%, 4K256 -5%; 94-126 MB
-// bands gain less).  A volume the cache already holds (K128) loses by it.
-// Band edges sit on multiples of 16 rows from the bottom: whole segments of
-// every pair family.
-// SGM_BAND_ROWS overrides (0: whole-volume passes).
-int sgm::band_rows_for(Geom g) {
-    const char *e = getenv("SGM_BAND_ROWS");
-    const double row_bytes = (double)g.W * g.D * sizeof(float);
-    int rows;
-    if (e && *e) {
-        rows = atoi(e);
-    } else {
-#ifdef SGM_NO_BANDS
-        return 0;
-#endif
-        if (row_bytes * g.H <= 256.0 * 1024 * 1024) return 0;
-        rows = (int)(192.0 * 1024 * 1024 / row_bytes);
-    }
-    rows -= rows % 16;
-    return rows <= 0 || rows >= g.H ? 0 : rows;
-}
-
+// The device's CU count: plan_handle's argument (sgm_create) and the slanted
+// top-down pass's share of the grid.
 int sgm::slant_cus() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -208,7 +158,7 @@ int forward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) {
     ViewRoles b = r;
     // band edges at H - m*BR (multiples of 16 rows from the bottom, as
     // the backward bands): whole segments of every family
-    const int H = g.H, FR = h->band_rows;
+    const int H = g.H, FR = h->plan.band_rows;
     const int nb = (H + FR - 1) / FR;
     for (int m = nb - 1; m >= 0; --m) {
         const int rb = H - (m + 1) * FR > 0 ? H - (m + 1) * FR : 0, re = H - m * FR;
@@ -226,7 +176,7 @@ int backward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) 
     const Geom g = h->g;
     const double elems = vol_elems(g);
     ViewRoles b = r;
-    const int H = g.H, BR = h->band_rows;
+    const int H = g.H, BR = h->plan.band_rows;
     // bottom band first: the backward passes walk up
     for (int kb = 0; kb < H; kb += BR) {
         const int ke = kb + BR < H ? kb + BR : H;
@@ -253,7 +203,7 @@ int backward_bands(sgm_handle *h, int view, const ViewRoles &r, hipStream_t st) 
 int aggregate4(sgm_handle *h, int nv, const ViewRoles *r, hipStream_t st) {
     const Geom g = h->g;
     const double elems = vol_elems(g);
-    if (h->p4_split) {
+    if (h->plan.p4_split) {
         HIPCHK(h, timed(h, "hpair4_fwd", nv * elems, st,
                         [&] { return sgm::launch_h_fwd4(r, nv, g, st); }));
         HIPCHK(h, timed(h, "hpair4_bwd", nv * elems, st,
@@ -269,7 +219,7 @@ int aggregate4(sgm_handle *h, int nv, const ViewRoles *r, hipStream_t st) {
 // Whole-volume passes over nv views' final volumes and L3 checkpoints: the 4-path handle's, or
 // the 8-path aggregation view after view
 int aggregate_whole(sgm_handle *h, const ViewRoles *r, int nv, hipStream_t st) {
-    if (h->paths4) return aggregate4(h, nv, r, st);
+    if (h->plan.paths4) return aggregate4(h, nv, r, st);
     int rc = SGM_OK;
     for (int v = 0; v < nv && rc == SGM_OK; ++v) rc = aggregate(h, &r[v], 1, st, true);
     return rc;
@@ -463,11 +413,11 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
     const bool joint = nv == 2 && sgm::cost_h_staged(s, 2, g);
     // banded frames run vfwd in forward bands (forward_bands); the slanted
     // schedule runs its own vertical pass
-    const bool vfwd_here = h->sched != SCHED_BANDS && h->sched != SCHED_SLANT;
+    const bool vfwd_here = h->plan.sched != sgm::SCHED_BANDS && h->plan.sched != sgm::SCHED_SLANT;
     // the slanted schedule's cost stage as checkpoints + strips (sgm_vstrip.hip):
     // C and the L3 volumes in one pass, 9 B per element instead of cost_h's
     // 4 and vfwd_l3's 12
-    const bool vstrip = h->slant && h->vstrip && sgm::vstrip_supported(s, nv, g);
+    const bool vstrip = h->plan.slant && h->plan.vstrip && sgm::vstrip_supported(s, nv, g);
     if (vstrip) {
         HIPCHK(h, timed(h, "cost_ck", elems, st, [&] { return sgm::launch_cost_ck(s, nv, sky_pitch, g, st); }));
         // (a masked frame's sky flags go to the strip pass as words)
@@ -519,8 +469,8 @@ int finish_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
 // straight into f.raw by the left view's final pass; the right view's is never written.
 bool frame_roles(sgm_handle *h, const FrameIO &f, ViewRoles *r) {
     const bool direct_out = h->nviews == 1 && f.out_pitch == h->g.W;
-    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->sub_cm);
-    if (h->nviews == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->sub_cm);
+    r[0] = view_roles(h, 0, f.raw, direct_out ? f.out : h->d_sub[0], h->plan.sub_cm);
+    if (h->nviews == 2) r[1] = view_roles(h, 1, nullptr, h->d_sub[1], h->plan.sub_cm);
     return direct_out;
 }
 
@@ -531,7 +481,7 @@ int views_to_out(sgm_handle *h, const FrameIO &f, bool direct_out, hipStream_t s
     if (h->nviews == 2) {
         HIPCHK(h, timed(h, "lr", (double)g.H * g.W, st, [&] {
                    // (true-disparity maps: the invalid marker is D + min_disp + 1)
-                   return h->sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
+                   return h->plan.sub_cm ? sgm::launch_lr_cm(h->d_sub[0], h->d_sub[1], f.out, f.out_pitch,
                                                         h->p.lr_max_diff, h->gt, st)
                                     : sgm::launch_lr(h->d_sub[0], g.W, h->d_sub[1], g.W, f.out,
                                                      f.out_pitch, h->p.lr_max_diff, h->gt, st);
@@ -663,11 +613,11 @@ int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
     if ((rc = cost_stage(h, f, st, &have_c)) != SGM_OK) return rc;
     ViewRoles r[2] = {};
     const bool direct_out = frame_roles(h, f, r);
-    switch (h->sched) {
-    case SCHED_PATHS4: rc = aggregate4(h, nv, r, st); break;
-    case SCHED_SLANT: rc = slant_views(h, r, st, have_c); break;
-    case SCHED_JOINT: rc = aggregate(h, r, 2, st, true); break;
-    case SCHED_BANDS: {
+    switch (h->plan.sched) {
+    case sgm::SCHED_PATHS4: rc = aggregate4(h, nv, r, st); break;
+    case sgm::SCHED_SLANT: rc = slant_views(h, r, st, have_c); break;
+    case sgm::SCHED_JOINT: rc = aggregate(h, r, 2, st, true); break;
+    case sgm::SCHED_BANDS: {
         // the views' forward bands, then their H pairs in one launch, then
         // each view's backward bands
         for (int v = 0; v < nv; ++v)
@@ -677,7 +627,7 @@ int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
             if ((rc = backward_bands(h, v, r[v], st)) != SGM_OK) return rc;
         break;
     }
-    case SCHED_WHOLE_FINAL2:
+    case sgm::SCHED_WHOLE_FINAL2:
         // whole-volume passes above the Infinity Cache (SGM_BAND_ROWS=0):
         // nothing is gained by finishing the left view first, so both
         // views' final passes run as one launch (fewer workgroup rounds)
@@ -686,7 +636,7 @@ int frame_maps(sgm_handle *h, FrameIO f, hipStream_t st) {
         HIPCHK(h, timed(h, "pair_bwd_L4_final", 2.0 * elems, st,
                         [&] { return sgm::launch_final(r, 2, false, g, st); }));
         break;
-    case SCHED_PER_VIEW: rc = aggregate_whole(h, r, nv, st); break;
+    case sgm::SCHED_PER_VIEW: rc = aggregate_whole(h, r, nv, st); break;
     }
     if (rc != SGM_OK) return rc;
     return views_to_out(h, f, direct_out, st);

@@ -1,12 +1,15 @@
 // sgm_handle.h -- the handle behind include/sgm_hip.h and the host helpers
 // every function that works on it uses: shared by the C-ABI (sgm_capi.hip, and
 // sgm_input.hip for the input stage) and the frame schedules (sgm_frame.hip).
+// The handle holds the plan sgm_create made for it (sgm_plan.h: the schedule
+// of its frames) once, as `plan`.
 // Host-only; not part of the public interface.
 #pragma once
 
 #include "../../include/sgm_hip.h"
 #include "sgm_input_stage.h"
 #include "sgm_internal.h"
+#include "sgm_plan.h"
 
 #include <algorithm>
 #include <stdarg.h>
@@ -16,27 +19,17 @@
 
 using sgm::Geom;
 using sgm::SweepArgs;
-
-// How run_frame aggregates (DESIGN.md "Frame schedule"): fixed at sgm_create by
-// the handle's paths, views, volume size and the SGM_SLANT / SGM_BAND_ROWS
-// switches.
-enum Schedule {
-    SCHED_PATHS4,        // the 4-path passes, both views per launch
-    SCHED_SLANT,         // the slanted tiles
-    SCHED_JOINT,         // two views whose volumes fit the Infinity Cache together: joint launches
-    SCHED_BANDS,         // forward bands, the H pair, backward bands (volumes above the cache)
-    SCHED_WHOLE_FINAL2,  // two views above the cache, unbanded: whole-volume passes, one final launch
-    SCHED_PER_VIEW       // whole-volume passes, view after view
-};
+using sgm::vol_elems;
 
 struct sgm_handle {
     sgm_params p;
-    Geom g;
+    sgm::HandlePlan plan; // the schedule of the handle's frames (plan_handle, sgm_plan.h)
+    Geom g;               // plan.g
     Geom gt;              // g with D + min_disp for D: the geometry of every stage that works on
                           // true-disparity maps (LR check, post filter, LKRefine, confidence
                           // filter, point cloud: valid <= D+m-1, invalid D+m+1)
     int device;
-    int nviews;
+    int nviews;           // plan.nviews
     size_t bytes;         // of the device allocations below
     std::vector<void *> allocs;  // every live dalloc (free_all frees these; dfree removes one)
     hipStream_t st;      // the handle's own stream (host API, stages)
@@ -82,18 +75,10 @@ struct sgm_handle {
     float *d_zero;        // 256 zero floats (PairArgs::zero)
     float *d_ck[2][3];    // checkpoints per view and pair family (H, V, D2)
     float *d_carry[2][3]; // banded backward passes: chain state at band edges (L7, L8, L4)
-    bool slant;           // the slanted-tile schedule (sgm_slant.hip, DESIGN.md "Slanted tiles")
-    bool vstrip;          //   its cost stage as checkpoints + strips (sgm_vstrip.hip; SGM_VSTRIP=0: off)
-    float *d_l3[2];       // slant: the full L3 volume per view
+    float *d_l3[2];       // slant (plan.slant): the full L3 volume per view
     unsigned long long *d_gran;  // slant: hand-off granules (both views)
     sgm::SlantCtl *d_slant_ctl;  // slant: launch bookkeeping of the passes
     float *d_slant_dummy;        // slant: the target of inactive lanes' stores
-    bool paths4;          // params.paths == 4: the 4-path schedule (aggregate4; no bands, no slant)
-    bool p4_split;        //   its H pair as forward + two-wave backward launches (SGM_P4_HPAIR)
-    int band_rows;        // rows per band of the backward phase (0: whole volume)
-    Schedule sched;       // the aggregation's schedule
-    int sub_cm;           // 1: the final passes store column-major sub-pixel maps (two views; the
-                          // LR check reads them through LDS tiles); the slanted pass stores row-major
     int mf_rows;          // median fill tile rows (4 or 8 by frame size; SGM_MF_ROWS)
     // post_filter scratch (sgm_post.hip)
     float *d_pf_orig;     // the map as it entered the median fill
@@ -262,9 +247,6 @@ inline const char *window_cost_name(const sgm_handle *h, int kind) {
     return h->win.weighted ? "window_cost_weighted" : "window_cost";
 }
 
-// elements of one view's cost volume
-inline double vol_elems(Geom g) { return (double)g.H * g.W * g.D; }
-
 inline hipEvent_t pool_event(sgm_handle *h) {
     if (!h->ev_pool.empty()) {
         hipEvent_t e = h->ev_pool.back();
@@ -370,8 +352,7 @@ int aggregate_volume(sgm_handle *h, const sgm_volume &vol, float *d_out, int out
 // sgm_filter_volume_device: the cost filters `filters` in place on a caller's dense fp32 HWD volume
 // (the horizontal filter alone runs in it; with the vertical one, view 0's Ch is the scratch)
 int filter_volume(sgm_handle *h, float *d_cost, int filters, hipStream_t st);
-bool slant_default(Geom g, int nviews);
-int band_rows_for(Geom g);
+// the device's CU count (the plan's and the slanted passes' grids)
 int slant_cus();
 // sgm_reproject.hip: the frame's last launch on a handle with reprojection set
 // (the products of the frame's map into the handle's buffers)

@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sgm_geom.h"
 #include "sgm_gray_args.h"
 #include "sgm_rectify_maps.h"
 #include "sgm_resize_args.h"
@@ -35,12 +36,6 @@ constexpr int seg_k_v(int V) { return V >= 4 ? 4 : 8; }     // PAIR_V
 // WTA waves load a chunk from its top row; the partial last chunk's top lies
 // up to K-1 rows above row 0, K = the vertical family's segment length).
 constexpr int t_guard_rows(int D) { return seg_k_v(vals_per_lane(D)) - 1; }
-
-// Geometry of one frame on the working (decimated) grid.
-struct Geom {
-    int H, W, D;   // rows, cols, disparities
-    int scale;     // 1 or 2
-};
 
 // What a sweep does with its path costs L_r ("Sweeps").
 enum SweepMode {
@@ -157,16 +152,7 @@ hipError_t launch_vfwd(const float *const *in, float *const *out, const PairArgs
                        float *const *l3, Geom g, hipStream_t st);
 
 // ----------------------------------------------- slanted tiles (sgm_slant.hip)
-// Compute waves per tile; one more wave per workgroup, the receiver, turns
-// the next tile's exit-state granules into LDS states (the compute waves 0
-// and 1 store this tile's own exit states themselves).
-// The bottom-up pass's tiles are 15 columns wide (16 waves, the workgroup
-// maximum): its hand-off granules cost 3 / NW of a tile-step's bytes, and
-// slant_up ran 3.9-4.0% faster at HD256 with 15 than with 14; the top-down
-// pass keeps 14 (with 15 the H pair beside it lost more than it gained,
-// profiles/r06_experiments/r06l_tile_width.txt).
-constexpr int kSlantNW = 14;     // top-down
-constexpr int kSlantNWUp = 15;   // bottom-up
+// (the tiles' widths kSlantNW, kSlantNWUp: sgm_geom.h)
 // Polls before a receiver gives up on a hand-off (a hang guard: seconds).
 constexpr unsigned kSlantSpinLimit = 1u << 22;
 // Launch bookkeeping of one slanted pass kind, in device memory (zeroed at

@@ -131,7 +131,7 @@ def test_calls_on_different_streams_are_ordered():
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("views", [2, 1])
 def test_slant_default_by_size(views, monkeypatch):
-    # sgm_frame.hip slant_default: at D = 256 above the Infinity Cache the
+    # sgm_plan.h slant_default: at D = 256 above the Infinity Cache the
     # slanted passes run once every workgroup gets 0.5 full-height tiles of
     # work (views x W >= 0.5 x 14 x CUs; on a 256-CU MI355X HD256 with two
     # views, 3840 >= 1792, and with one view, 1920: both slanted since round

@@ -103,7 +103,7 @@ def test_slanted_schedule_falls_back_to_bands_without_memory():
     assert r.returncode == 0 and lines, r.stdout[-2000:] + r.stderr[-3000:]
     rec = json.loads(lines[-1])
     if not rec["base_slant"]:
-        pytest.skip("this device's CU count keeps the frame on the bands (sgm_capi.hip slant_default)")
+        pytest.skip("this device's CU count keeps the frame on the bands (sgm_plan.h slant_default)")
     assert not rec["fb_slant"] and rec["fb_bands"], rec
     assert rec["exact"], rec
     assert rec["bytes"][1] < rec["bytes"][0], rec

@@ -1,5 +1,5 @@
 """Frame time of the slanted-tile schedule against the bands over frame sizes
-above the Infinity Cache (sets sgm_frame.hip slant_default).  Each size: a
+above the Infinity Cache (sets sgm_plan.h slant_default).  Each size: a
 handle per schedule (SGM_SLANT read at create), 2 warm-up frames, then 6
 timed frames on device-resident inputs, alternated twice.
 Usage: python tools/slant_sizes.py [HxWxDxV ...]"""
