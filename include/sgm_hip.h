@@ -734,6 +734,9 @@ int sgm_stage_filter_volume(sgm_handle *h, float *cost, int filters);
 /* The steps of one prefetched block of the horizontal filter's main loop (tests
  * and tools derive their edge-case widths from it). */
 int sgm_volume_filter_block(void);
+/* The columns of one strip of the slanted schedule's strip pass (tests derive
+ * their edge-case widths from it). */
+int sgm_vstrip_cols(void);
 
 /* ---- the matching window: WIN_H, WIN_W of inc/Solver.h as a setting ----
  *

@@ -52,7 +52,7 @@ EXPORTS = (
     "sgm_set_cost", "sgm_get_cost", "sgm_window_cost_device", "sgm_stage_window_cost",
     "sgm_window_cost_tile_cols", "sgm_set_window", "sgm_get_window",
     "sgm_set_volume_filter", "sgm_get_volume_filter", "sgm_filter_volume_device",
-    "sgm_stage_filter_volume", "sgm_volume_filter_block",
+    "sgm_stage_filter_volume", "sgm_volume_filter_block", "sgm_vstrip_cols",
     "sgm_set_weighted", "sgm_get_weighted", "sgm_get_window_weights",
 )
 # sgm_set_volume_filter's bits (SGM_FILTER_*)
@@ -239,6 +239,7 @@ def lib():
     L.sgm_filter_volume_device.argtypes = [P, P, I, P]
     L.sgm_stage_filter_volume.argtypes = [P, P, I]
     L.sgm_volume_filter_block.argtypes = []
+    L.sgm_vstrip_cols.argtypes = []
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

@@ -1116,28 +1116,25 @@ __device__ __forceinline__ void vfwd_body(const float *__restrict__ in, float *_
     const int T = H - 2 * HALF;
     float *cy = BAND ? a.band.carry + (size_t)j * 3 * g.D + e0 : nullptr;
 
-    float raw0[V], rawl[V], sum[V], o1[V];
+    float raw0[V], rawl[V];
+    VFilter<WIN, V> vf;  // the recursion: sgm_cost_iir.h
     load_v_nt<V>(raw0, col, active);
     load_v_nt<V>(rawl, col + (size_t)(H - 1) * stride, active);  // the only row below LAG+T (WIN=3)
     float prev[V];
     float pmin = 0.0f;
     if (BAND && rb > 0) {  // the filter and path state entering the band
-        load_v<V>(sum, cy, active);
-        load_v<V>(o1, cy + g.D, active);
+        vf.load_carry([&](float (&x)[V], int k) { load_v<V>(x, cy + k * g.D, active); });
         load_v<V>(prev, cy + 2 * g.D, active);
         pmin = wave_min(lane_min(prev));
     } else {
+        // (row 0, raw, is also what step t = 0 subtracts: the state keeps it,
+        // and so does a band's carry, rather than re-reading it from `in`,
+        // whose row 0 the forward bands overwrite with T (T aliases the
+        // horizontally filtered volume) before the next band starts)
+        float r[WIN][V];
 #pragma unroll
-        for (int v = 0; v < V; ++v) sum[v] = 0.0f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            float r[V];
-            load_v_nt<V>(r, col + (size_t)k * stride, active);
-#pragma unroll
-            for (int v = 0; v < V; ++v) sum[v] += r[v];
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) o1[v] = 0.0f;
+        for (int k = 0; k < WIN; ++k) load_v_nt<V>(r[k], col + (size_t)k * stride, active);
+        vf.init(r);
         // L = 0, minL = 0 before row 0 makes the first step yield L = C (the
         // path start, SGM.cpp:161-170) without a per-row select (P1, P2 >= 0)
 #pragma unroll
@@ -1150,31 +1147,15 @@ __device__ __forceinline__ void vfwd_body(const float *__restrict__ in, float *_
 
     auto row = [&](int i, int u, bool refill) {
         float c[V];
-        if (i < LAG) {
-            // row 0 stays raw; it is also what step t = 0 subtracts, kept in
-            // o1 (and so in a band's carry) rather than re-read from `in`,
-            // whose row 0 the forward bands overwrite with T (T aliases the
-            // horizontally filtered volume) before the next band starts
+        if (i < LAG) {  // row 0 stays raw
 #pragma unroll
             for (int v = 0; v < V; ++v) c[v] = raw0[v];
-#pragma unroll
-            for (int v = 0; v < V; ++v) o1[v] = c[v];
         } else if (i >= LAG + T) {
 #pragma unroll
             for (int v = 0; v < V; ++v) c[v] = rawl[v];
         } else {
-            const int t = i - LAG;
-#pragma unroll
-            for (int v = 0; v < V; ++v) c[v] = div_win<WIN>(sum[v]);
-            if (t < T - 1) {
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const float sub = LAG == 0 ? c[v] : o1[v];
-                    sum[v] = (sum[v] + ring[u][v]) - sub;
-                }
-            }
-#pragma unroll
-            for (int v = 0; v < V; ++v) o1[v] = c[v];
+            vf.out(c);
+            if (i - LAG < T - 1) vf.advance(c, ring[u]);
         }
         // the slanted schedule's C (L3OUT: above the Infinity Cache) streams
         // past L2 like L3 does (paired A/B r05: -0.6% HD256, -0.5% 4K256);
@@ -1207,8 +1188,7 @@ __device__ __forceinline__ void vfwd_body(const float *__restrict__ in, float *_
     for (int u = 0; u < PF; ++u)
         if (i0 + u < re) row(i0 + u, u, false);
     if (BAND && re < H) {  // the state leaving the band
-        store_v<V>(cy, sum, active);
-        store_v<V>(cy + g.D, o1, active);
+        vf.store_carry([&](const float (&x)[V], int k) { store_v<V>(cy + k * g.D, x, active); });
         store_v<V>(cy + 2 * g.D, prev, active);
     }
 }

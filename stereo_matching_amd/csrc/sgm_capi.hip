@@ -796,6 +796,8 @@ int sgm_get_volume_filter(const sgm_handle *h, int *filters) {
 
 int sgm_volume_filter_block(void) { return sgm::volume_filter_block(); }
 
+int sgm_vstrip_cols(void) { return sgm::kVStripNC; }
+
 int sgm_filter_volume_device(sgm_handle *h, float *d_cost, int filters, void *stream) {
     if (!h) return SGM_ERR_INVALID_ARG;
     if (!d_cost || (uintptr_t)d_cost % 16)

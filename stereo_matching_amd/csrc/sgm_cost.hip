@@ -295,6 +295,15 @@ constexpr int COSTH_U = 8;
 
 __host__ __device__ constexpr int costh_pad(int D, int scale) { return D / scale + 2 * COSTH_U; }
 
+// The checkpoint pass's store (cost_h_body<..., CK> and cost_ck_body): the
+// chain's restart state (HCheckpoint, sgm_cost_iir.h) as 3 floats ds apart.
+__device__ __forceinline__ void ck_write(const HFilter<5> &f, float *q, size_t ds) {
+    HCheckpoint ck;
+    ck.save(f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k * ds] = ck.v[k];
+}
+
 // UNI (D >= 64, one row per wave): the census word every lane of a row needs
 // at step j -- cl[j] for the left view, cr[j] for the right -- is a uniform
 // scalar load from global memory; only the per-lane shifted row is staged in
@@ -358,6 +367,11 @@ __device__ __forceinline__ void cost_h_body(const uint64_t *__restrict__ ctl,
         for (int j = 0; j < W; ++j) costh_store(raw(j), o + (size_t)j * DS);
         return;
     }
+    // The recursion is HFilter<WIN>'s (sgm_cost_iir.h: init, out, advance), written out here with
+    // a history array of its own: through the type hipcc schedules the 5-wide chain differently,
+    // and the one-view kernel at 375 x 1242 x 128, which here runs in one of two modes (47-48 us
+    // or 54-59 us), sat at 56 us in both (paired A/B, profiles/cost_iir_isa.txt section 3).  The
+    // header's CPU test and the GPU tests pin both forms to the oracle.
     constexpr int HALF = WIN / 2, LAG = WIN - HALF - 1, U = COSTH_U;
     float sum = 0.0f;
 #pragma unroll
@@ -373,12 +387,7 @@ __device__ __forceinline__ void cost_h_body(const uint64_t *__restrict__ ctl,
     for (int p = 0; p < LAG; ++p) hist[p] = raw(p);
     auto ck_store = [&](int p) {
         if constexpr (CK > 0) {
-            if (p % CK == 0) {
-                float *q = o + (size_t)(p / CK) * 3 * DS;
-                q[0] = sum;
-                q[DS] = hist[0];
-                q[2 * DS] = hist[LAG - 1];
-            }
+            if (p % CK == 0) ck_write(HFilter<5>{sum, {hist[0], hist[LAG - 1]}}, o + (size_t)(p / CK) * 3 * DS, DS);
         }
     };
     auto step = [&](int t, float rw) {
@@ -507,25 +516,19 @@ __global__ __launch_bounds__(256) void cost_h_global_kernel(const uint64_t *__re
         return;
     }
     constexpr int HALF = WIN / 2, LAG = WIN - HALF - 1;
-    float sum = 0.0f;
+    HFilter<WIN> f;  // the recursion: sgm_cost_iir.h
+    float first[WIN];
 #pragma unroll
-    for (int k = 0; k < WIN; ++k) sum += raw(k);
+    for (int k = 0; k < WIN; ++k) first[k] = raw(k);
+    f.init(first);
 #pragma unroll
-    for (int p = 0; p < LAG; ++p) costh_store(raw(p), o + (size_t)p * D);
+    for (int p = 0; p < LAG; ++p) costh_store(first[p], o + (size_t)p * D);
     const int T = W - 2 * HALF;
-    float o1 = 0.0f, o2 = 0.0f;
     for (int t = 0; t < T; ++t) {
-        const float v = div_win<WIN>(sum);
+        const float v = f.out();
         costh_store(v, o + (size_t)(LAG + t) * D);
         if (t == T - 1) break;
-        sum += raw(WIN + t);
-        float a;
-        if (LAG == 0) a = v;
-        else if (LAG == 1) a = t >= 1 ? o1 : raw(t);
-        else a = t >= 2 ? o2 : raw(t);
-        sum -= a;
-        o2 = o1;
-        o1 = v;
+        f.advance(v, raw(WIN + t));
     }
     for (int p = LAG + T; p < W; ++p) costh_store(raw(p), o + (size_t)p * D);
 }
@@ -616,8 +619,8 @@ hipError_t launch_cost_h(const CostSlot *s, int nviews, int sky_pitch, int filte
     return hipGetLastError();
 }
 
-// The checkpoint pass's chain (sgm_vstrip.hip): cost_h_body's horizontal IIR
-// (WIN = 5, no sky mask), storing only the state at every strip edge.  Its
+// The checkpoint pass's chain (sgm_vstrip.hip): the horizontal IIR (WIN = 5,
+// no sky mask), storing only the state at every strip edge.  Its
 // bytes are negligible, so the chains' latency is its time: the steps run in
 // blocks of one strip (U = kVStripNC) that start at an edge, so the
 // checkpoint is the block's first action (no branch), and the next block's
@@ -634,6 +637,7 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
     uint64_t *sl = reinterpret_cast<uint64_t *>(smem);
     uint64_t *sr = sl + (UNI ? 0 : (size_t)R * RS);
     const int row0 = blk * R;
+    // (cost_h_body's staging loop without the sky row)
     for (int idx = tid_x(); idx < R * RS; idx += R * D) {
         const int r = idx / RS, jp = idx - r * RS, i = row0 + r;
         const int j = clampi(jp - P, 0, W - 1);
@@ -658,24 +662,14 @@ __device__ __forceinline__ void cost_ck_body(const uint64_t *__restrict__ ctl,
         j = min(j, W - 1);
         return VIEW == 0 ? hamming(wu(j), ws(j)) : hamming(ws(j), wu(j));
     };
-    float sum = 0.0f;
+    HFilter<5> f;  // the recursion: sgm_cost_iir.h
+    float first[5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) sum += raw(k);
-    float h0 = raw(0), h1 = raw(1);
+    for (int k = 0; k < 5; ++k) first[k] = raw(k);
+    f.init(first);
     const int T = W - 4;  // steps: output position t+2; steps t < T-1 update
-    auto step = [&](float rw) {
-        const float v = div_win<5>(sum);
-        sum += rw;
-        sum -= h0;
-        h0 = h1;
-        h1 = v;
-    };
-    auto ck_store = [&](int s) {
-        float *q = o + (size_t)s * 3 * D;
-        q[0] = sum;
-        q[D] = h0;
-        q[2 * D] = h1;
-    };
+    auto step = [&](float rw) { f.advance(f.out(), rw); };
+    auto ck_store = [&](int s) { ck_write(f, o + (size_t)s * 3 * D, (size_t)D); };
     // a step with its conditions (the prologue and the tail): the checkpoint
     // of the strip starting at position t+2, then the update
     auto gstep = [&](int t) {

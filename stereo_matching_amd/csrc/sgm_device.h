@@ -4,6 +4,7 @@
 #pragma once
 
 #include "sgm_internal.h"
+#include "sgm_cost_iir.h"  // div_win and the two cost filters' recursions
 
 #include <float.h>
 #include <limits.h>
@@ -202,30 +203,6 @@ __device__ __forceinline__ float readlane_f(float x, int lane) {
 // a diagonal path (SGM.cpp:266,282,330,346), so W chains of H steps cover
 // every pixel once per direction.  `off` is the element offset (i*W + j)*D of
 // the pixel's disparity vector; everything here is wave-uniform (SALU).
-// Correctly rounded x / WIN for the cost filters' window sizes (Solver.cpp:319,
-// 357: sum / win_size).  For WIN = 3 and 5, q0 = x*RN(1/WIN) corrected by one
-// FMA residual step equals IEEE division bit-for-bit for EVERY non-negative
-// finite float (exhaustive GPU check, tools/verify_div.hip; negative x follows
-// by symmetry, and -0 cannot occur in the filters); 3 VALU ops instead of the
-// ~10-op div_scale/div_fmas/div_fixup sequence.  For WIN = 7 and 9 (the window
-// costs' divisors, sgm_window_cost.hip) the same form is proven over the inputs
-// a window sum can reach, not over every float (sgm_window_cost_args.h).
-template <int WIN>
-__device__ __forceinline__ float div_win(float x) {
-    if constexpr (WIN == 1) {
-        return x;
-    } else if constexpr (WIN == 2) {
-        return x * 0.5f;
-    } else if constexpr (WIN == 4) {
-        return x * 0.25f;
-    } else {
-        constexpr float r = 1.0f / WIN;
-        const float q0 = x * r;
-        const float e = __builtin_fmaf(-q0, (float)WIN, x);
-        return __builtin_fmaf(e, r, q0);
-    }
-}
-
 // Integer division has no scalar instruction, so hipcc computes % in VALU
 // and then treats the (uniform) result as divergent; pin it back to an SGPR.
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }

@@ -5,16 +5,10 @@
 // costs from census words staged in LDS (cost_h_body, sgm_cost.hip).  The
 // volume entry of the pipeline -- a caller's volume (sgm_aggregate_device), a
 // SAD or SSD window cost -- has the raw costs as a dense fp32 HWD volume
-// instead, and this kernel is the same recursion reading them from there:
-//
-//   sum = raw[0] + .. + raw[WIN-1]                 (left to right, from 0)
-//   step t = 0 .. T-1, T = W - 2 (WIN/2):
-//     out[LAG + t] = sum / WIN                     (LAG = WIN - WIN/2 - 1)
-//     sum += raw[WIN + t];  sum -= x[t]            (two roundings; not the last step)
-//
-// where x[t] is what position t holds by then: raw below LAG, the step-(t-LAG)
-// output after (an IIR, not a box filter), kept in a register history of LAG
-// values.  Columns below LAG and from LAG + T on keep their raw values.
+// instead, and this kernel runs the same recursion (HFilter, sgm_cost_iir.h: an
+// IIR, not a box filter) reading them from there: step t = 0 .. T-1,
+// T = W - 2 (WIN/2), writes column LAG + t (LAG = WIN - WIN/2 - 1); columns
+// below LAG and from LAG + T on keep their raw values.
 //
 // Shape: cost_h's.  One lane per (row, d) chain, lanes along d, so every load
 // and store of a wave is one whole 256-byte line (128 bytes per half wave at
@@ -79,31 +73,16 @@ __global__ __launch_bounds__(256) void vol_hfilter_kernel(const float *in0, floa
     float cur[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) cur[u] = raw(WIN + u);
-    float sum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < WIN; ++k) sum += first[k];
-    // hist[0] is what step t subtracts: raw[t] for t < LAG, output t - LAG after
-    float hist[LAG > 0 ? LAG : 1];
-#pragma unroll
-    for (int q = 0; q < LAG; ++q) hist[q] = first[q];
+    HFilter<WIN> f;  // the recursion: sgm_cost_iir.h
+    f.init(first);
     if (copy) {
 #pragma unroll
         for (int q = 0; q < LAG; ++q) volf_store<NT>(first[q], o + (size_t)q * DS);
     }
     auto step = [&](int t, float rw) {
-        const float v = div_win<WIN>(sum);
+        const float v = f.out();
         volf_store<NT>(v, o + (size_t)(LAG + t) * DS);
-        sum += rw;
-        float a;
-        if constexpr (LAG == 0) {
-            a = v;
-        } else {
-            a = hist[0];
-#pragma unroll
-            for (int q = 0; q + 1 < LAG; ++q) hist[q] = hist[q + 1];
-            hist[LAG - 1] = v;
-        }
-        sum -= a;
+        f.advance(v, rw);
     };
     // steps t < T-1 write and update, the last step only writes.  Each step refills the ring slot
     // it consumed with the value U steps ahead: a load is followed by 2U - 1 younger loads and
@@ -126,7 +105,7 @@ __global__ __launch_bounds__(256) void vol_hfilter_kernel(const float *in0, floa
 #pragma unroll
     for (int u = 0; u < U; ++u)
         if (t + u < T - 1) step(t + u, cur[u]);
-    if (T >= 1) volf_store<NT>(div_win<WIN>(sum), o + (size_t)(LAG + T - 1) * DS);
+    if (T >= 1) volf_store<NT>(f.out(), o + (size_t)(LAG + T - 1) * DS);
     if (copy) {
 #pragma unroll
         for (int q = 0; q < TAIL; ++q) volf_store<NT>(last[q], o + (size_t)(LAG + T + q) * DS);

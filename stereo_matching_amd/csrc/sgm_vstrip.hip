@@ -23,9 +23,9 @@
 //   * NV "vertical" waves (CPW columns each, lane l holding disparities
 //     l*V .. l*V+V-1 as in vfwd_body) produce output row it-3 from the ring
 //     -- the vertical IIR reads Ch two rows ahead -- and run the L3 DP on it.
-// Every chain keeps the reference's order of operations (cost_h_body and
-// vfwd_body restate them; this pass computes the same values), so C and L3
-// are bit-identical to cost_h + vfwd_l3 (tests/test_gpu_vstrip.py).
+// Every chain is the recursion cost_h_body and vfwd_body run (HFilter, VFilter
+// and the checkpoint's HCheckpoint, sgm_cost_iir.h), so C and L3 are
+// bit-identical to cost_h + vfwd_l3 (tests/test_gpu_vstrip.py).
 //
 // Both passes launch over the frame's view slots (CostSlot, sgm_internal.h).
 // The kernel here keeps an argument struct of its own, filled from the slots
@@ -136,12 +136,11 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
         const size_t ck_row = (size_t)NS * 3 * D;
         // the rows' checkpoints (strips past the first; strip 0 starts the
         // chain from raw costs), PD rows ahead
-        float ks_[PD], k0_[PD], k1_[PD];
+        HCheckpoint ck_[PD];
         auto ck_load = [&](int u, int r) {
             const float *q = ck + (size_t)uniform(min(r, H - 1)) * ck_row;
-            ks_[u] = q[0];
-            k0_[u] = q[D];
-            k1_[u] = q[2 * D];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ck_[u].v[k] = q[k * D];
         };
 #pragma unroll
         for (int u = 0; u < PD; ++u) ck_load(u, u);
@@ -156,31 +155,19 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
                 float rw[NR];
 #pragma unroll
                 for (int xx = 0; xx < NR; ++xx) rw[xx] = rr[xx * 64 * V];
-                float sum, h0, h1;
-                if (s == 0) {
-                    // cost_h_body's start: sum of raw[0 .. 4], positions 0, 1 raw
-                    sum = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) sum += rw[k];
-                    h0 = rw[0];
-                    h1 = rw[1];
-                } else {
-                    sum = ks_[u];
-                    h0 = k0_[u];
-                    h1 = k1_[u];
-                }
+                // the chain (HFilter, sgm_cost_iir.h) from the row's start in
+                // strip 0, else restarted from the strip's checkpoint
+                HFilter<5> f;
+                if (s == 0) f.init(rw);
+                else ck_[u].restore(f);
                 float *row = &L.ch[it & 3][0][d];
-                // cost_h_body's steps with LAG = 2: output p = div(sum) for
-                // 2 <= p <= W-3 (raw outside), then for p < W-3 sum += raw[p+3],
-                // sum -= the value at p-2
+                // position p is filtered for 2 <= p <= W-3 (raw outside) and
+                // followed by an update, which adds raw[p+3], for p < W-3
                 if (interior) {
 #pragma unroll
                     for (int xx = 0; xx < NC; ++xx) {
-                        const float c = div_win<5>(sum);
-                        sum += rw[xx + 3];
-                        sum -= h0;
-                        h0 = h1;
-                        h1 = c;
+                        const float c = f.out();
+                        f.advance(c, rw[xx + 3]);
                         row[xx * 64 * V] = c;
                     }
                 } else {
@@ -190,13 +177,8 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
                     for (int xx = 0; xx < NC; ++xx) {
                         const int p = j0 + xx;
                         const bool filt = p >= 2 && p <= W - 3, upd = p >= 2 && p < W - 3;
-                        const float q = div_win<5>(sum);
-                        const float c = filt ? q : rw[xx];
-                        float ns = sum + rw[xx + 3];
-                        ns -= h0;
-                        sum = upd ? ns : sum;
-                        h0 = filt ? h1 : h0;
-                        h1 = filt ? c : h1;
+                        const float c = filt ? f.out() : rw[xx];
+                        f.advance_if(filt, upd, c, rw[xx + 3]);
                         row[xx * 64 * V] = c;
                     }
                 }
@@ -248,7 +230,8 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
             }
         }
     };
-    float sum[CPW][V], o1[CPW][V], prev[CPW][V], pmin[CPW];
+    VFilter<3, V> vf[CPW];  // the columns' vertical chains (sgm_cost_iir.h)
+    float prev[CPW][V], pmin[CPW];
     // the outputs of the iteration's row, stored after the branch (an
     // iteration without a row stores to the dummy area: a store inside a
     // branch makes the waitcnt pass wait for it before the ring's next use)
@@ -275,35 +258,26 @@ __global__ __launch_bounds__(64 * (NH + NV)) void vstrip_kernel(VStripArgs a, Ge
             for (int q = 0; q < CPW; ++q) {
                 const int xx = w * CPW + q;
                 if (i == 0) {
-                    // vfwd_body's start: sum = 0 + Ch0 + Ch1 + Ch2, row 0 raw
-                    float r0[V], r1[V], r2[V];
-                    rd(0, xx, r0);
-                    rd(1, xx, r1);
-                    rd(2, xx, r2);
+                    // the chain's start from Ch rows 0 .. 2; row 0 stays raw
+                    float r[3][V];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) rd(k, xx, r[k]);
+                    vf[q].init(r);
 #pragma unroll
                     for (int v = 0; v < V; ++v) {
-                        sum[q][v] = 0.0f;
-                        sum[q][v] += r0[v];
-                        sum[q][v] += r1[v];
-                        sum[q][v] += r2[v];
                         prev[q][v] = 0.0f;
-                        c[q][v] = r0[v];
-                        o1[q][v] = r0[v];
+                        c[q][v] = r[0][v];
                     }
                     pmin[q] = 0.0f;
                 } else if (i == H - 1) {
                     rd(H - 1, xx, c[q]);
                 } else {
-#pragma unroll
-                    for (int v = 0; v < V; ++v) c[q][v] = div_win<3>(sum[q][v]);
+                    vf[q].out(c[q]);
                     if (i < H - 2) {
                         float rr[V];
                         rd(i + 2, xx, rr);
-#pragma unroll
-                        for (int v = 0; v < V; ++v) sum[q][v] = (sum[q][v] + rr[v]) - o1[q][v];
+                        vf[q].advance(c[q], rr);
                     }
-#pragma unroll
-                    for (int v = 0; v < V; ++v) o1[q][v] = c[q][v];
                 }
                 // L3 forward step (L = 0, minL = 0 before row 0 gives L = C)
                 dp_step<V>(prev[q], pmin[q], c[q], Lv[q], a.p1, p2v);
