@@ -62,6 +62,9 @@ public:
     }
     virtual const Mat &get_disp() const { return filtered_disp; }
 
+    // the hole filling of the one view's map: SGM_FILL_BACKGROUND (sgm_set_fill)
+    using HipSolver::set_fill;
+    using HipSolver::get_fill_mask;
     using HipSolver::handle;
     using Solver::get_invalid_disp;
 };

@@ -31,6 +31,7 @@
  *   gray(src, dst, fmt)          node.cpp:69-70     the decoder's / cvtColor's grey conversion
  *                                on the GPU, Y = (4899 R + 9617 G + 1868 B + 8192) >> 14
  *   input_gray(view)             the grey image the last process() matched
+ *   set_fill(mode)               (not in the reference) every process() fills its map's holes
  *   set_reproject(q, outputs)    (not in the reference) every process() also reprojects its map
  *                                through stereoRectify's Q on the GPU: xyz() (CV_32FC3, what
  *                                cv::reprojectImageTo3D gives), depth() (CV_32FC1), depth16()
@@ -307,6 +308,8 @@ public:
         if (rc != SGM_OK) fail("process", sgm_last_error(handle_));
         if (confidence_on_ &&
             sgm_stage_confidence(handle_, SGM_VIEW_LEFT, confidence_.template ptr<float>(0)) != SGM_OK)
+            fail("process", sgm_last_error(handle_));
+        if (!fill_mask_.empty() && sgm_stage_fill_mask(handle_, fill_mask_.data) != SGM_OK)
             fail("process", sgm_last_error(handle_));
         if (staging()) {
             // what the frame matched: the node's resized img_l / img_r (node.cpp:75-76), the
@@ -603,6 +606,21 @@ public:
     // empty while confidence is off
     const Mat &get_confidence() const { return confidence_; }
 
+    // The occlusion-aware hole filling (sgm_set_fill; SGM_FILL_OFF,
+    // SGM_FILL_BACKGROUND, SGM_FILL_INTERPOLATE): with a mode set, every
+    // process() fills the invalid pixels of its post-filtered map on the GPU
+    // (Hirschmueller 2008, 2.6) before the reprojection, and get_disp() is the
+    // dense map.  SGM serves both modes, BM and GPU_SGM (one view) the
+    // background mode; anything else fails.
+    void set_fill(int mode) {
+        if (sgm_set_fill(handle_, mode) != SGM_OK) fail("set_fill", sgm_last_error(handle_));
+        fill_mask_ = mode != SGM_FILL_OFF ? Mat(img_h, img_w, CV_8UC1) : Mat();
+        if (!fill_mask_.empty()) std::memset(fill_mask_.data, 0, (size_t)fill_mask_.rows * fill_mask_.step);
+    }
+    // CV_8UC1 on the working grid, of the last process(): 0 measured, 1 filled
+    // as occlusion, 2 filled as mismatch, 3 still invalid; empty while fill is off
+    const Mat &get_fill_mask() const { return fill_mask_; }
+
 protected:
     // views = 1: the left view alone (BM; GPU_SGM, gpu_sgm/src/SGM.cu:105-232)
     // paths = 4: the reference built with USE_8_PATH = false (inc/SGM.h:7)
@@ -629,6 +647,7 @@ private:
     bool bm_;
     bool confidence_on_ = false;
     Mat confidence_;
+    Mat fill_mask_;          // set_fill: the last process()'s fill mask
     int full_h_, full_w_;    // the constructed size (in_h_, in_w_: what process() takes)
     bool resizing_ = false;  // set_input_size
     bool rectifying_ = false;  // set_rectify

@@ -461,6 +461,59 @@ int sgm_stage_reprojected(sgm_handle *h, int which, void *img);
  * field. */
 int sgm_camera_q(const sgm_camera *cam, double q[16]);
 
+/* ---- occlusion-aware hole filling ----
+ * A dense map from the frame's final one: the last step of the SGM paper
+ * (Hirschmueller 2008, 2.6).  Every invalid pixel (not <= max_disp + min_disp
+ * - 1; a NaN counts as invalid) takes one of the up to 8 values its rays find,
+ * the first valid pixel of the INPUT map in each of the 8 directions, sorted
+ * ascending: an occlusion the second lowest (the background; the lowest of one),
+ * a mismatch the upper median sorted[k / 2].  A pixel (i, j) is a mismatch iff
+ * some integer d in [min_disp, min_disp + max_disp) has jr = j - d / scale >= 0,
+ * the right view's map valid at (i, jr) and |R(i, jr) - d| <= lr_max_diff (the
+ * handle's LR tolerance); else an occlusion.  SGM_FILL_BACKGROUND treats every
+ * invalid pixel as an occlusion and reads no right map.  A pixel no ray serves
+ * stays max_disp + min_disp + 1.  Beside the map a uint8 fill mask:
+ *   0 measured, 1 filled as occlusion, 2 filled as mismatch, 3 still invalid.
+ * Two launches, no host wait, capturable; the results equal
+ * tests/fill_recipe.py bit for bit. */
+enum { SGM_FILL_OFF = 0, SGM_FILL_BACKGROUND = 1, SGM_FILL_INTERPOLATE = 2 };
+/* A property of the handle (like sgm_set_confidence; sgm_params and
+ * SGM_HIP_VERSION are unchanged): with a mode set, every later frame
+ * (sgm_process[_device] of any cost and schedule, BM frames, and
+ * sgm_aggregate_device) fills its map as its last map stage, after post_filter
+ * and LKRefine and before the reprojection, which then reads the dense map.
+ * SGM_FILL_INTERPOLATE needs a two-view SGM handle (its right map is the
+ * frame's own); one-view left and BM handles serve SGM_FILL_BACKGROUND; an
+ * aux_only handle runs no frames and takes either mode for the scratch of
+ * sgm_fill_device; a SGM_VIEW_RIGHT handle refuses any mode but off.  Setting a
+ * mode allocates 25 bytes per pixel (six candidate planes and the mask),
+ * SGM_FILL_OFF frees them; a handle with fill off enqueues exactly the launches
+ * it did.  Waits for the handle's work; SGM_ERR_INVALID_ARG inside stream
+ * capture, for an unknown mode and for the combinations above.  Re-capture
+ * graphs afterwards. */
+int sgm_set_fill(sgm_handle *h, int mode);
+int sgm_get_fill(const sgm_handle *h, int *mode);
+/* The fill in place on a DEVICE map of rows x cols true disparities (pitch in
+ * floats), on any handle whose fill scratch exists (sgm_set_fill), with the
+ * handle's min_disp and lr_max_diff.  mode: SGM_FILL_BACKGROUND or
+ * SGM_FILL_INTERPOLATE, whatever the handle's own.  d_right: the right view's
+ * row-major map (right_pitch floats per row; SGM_FILL_INTERPOLATE only, and not
+ * d_disp); NULL means this handle's last frame's right view, which only a
+ * two-view SGM handle keeps.  d_mask: the fill mask's destination (mask_pitch
+ * bytes per row), or NULL for the handle's own (sgm_get_fill_mask).  Two
+ * launches on `stream` (NULL: the handle's own; hipStreamLegacy is refused, as
+ * by the volume calls), enqueue only. */
+int sgm_fill_device(sgm_handle *h, float *d_disp, int pitch, const float *d_right, int right_pitch,
+                    int mode, uint8_t *d_mask, int mask_pitch, void *stream);
+/* The same with HOST arrays (dense; right and mask may be NULL); synchronous. */
+int sgm_stage_fill(sgm_handle *h, float *disp, const float *right, int mode, uint8_t *mask);
+/* The fill mask of the last filled frame (or sgm_fill_device call with d_mask
+ * NULL): handle-owned DEVICE memory, *pitch in bytes; valid until the next
+ * fill, sgm_set_fill or sgm_destroy.  SGM_ERR_INVALID_ARG before any fill. */
+int sgm_get_fill_mask(sgm_handle *h, const uint8_t **d_mask, int *pitch);
+/* The same mask copied to a HOST buffer (dense); synchronous. */
+int sgm_stage_fill_mask(sgm_handle *h, uint8_t *mask);
+
 /* Bytes of device memory the handle holds. */
 size_t sgm_device_bytes(const sgm_handle *h);
 /* The handle's own stream (a hipStream_t; what a NULL stream argument

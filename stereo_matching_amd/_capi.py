@@ -54,7 +54,11 @@ EXPORTS = (
     "sgm_set_volume_filter", "sgm_get_volume_filter", "sgm_filter_volume_device",
     "sgm_stage_filter_volume", "sgm_volume_filter_block", "sgm_vstrip_cols",
     "sgm_set_weighted", "sgm_get_weighted", "sgm_get_window_weights",
+    "sgm_set_fill", "sgm_get_fill", "sgm_fill_device", "sgm_stage_fill",
+    "sgm_get_fill_mask", "sgm_stage_fill_mask",
 )
+# sgm_set_fill's modes (SGM_FILL_*), by name
+FILL_MODES = {"off": 0, "background": 1, "interpolate": 2}
 # sgm_set_volume_filter's bits (SGM_FILTER_*)
 SGM_FILTER_H = 1
 SGM_FILTER_V = 2
@@ -240,6 +244,12 @@ def lib():
     L.sgm_stage_filter_volume.argtypes = [P, P, I]
     L.sgm_volume_filter_block.argtypes = []
     L.sgm_vstrip_cols.argtypes = []
+    L.sgm_set_fill.argtypes = [P, I]
+    L.sgm_get_fill.argtypes = [P, ctypes.POINTER(I)]
+    L.sgm_fill_device.argtypes = [P, P, I, P, I, I, P, I, P]
+    L.sgm_stage_fill.argtypes = [P, P, P, I, P]
+    L.sgm_get_fill_mask.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(I)]
+    L.sgm_stage_fill_mask.argtypes = [P, P]
     L.sgm_device_bytes.argtypes = [P]
     L.sgm_device_bytes.restype = ctypes.c_size_t
     L.sgm_get_stream.argtypes = [P]

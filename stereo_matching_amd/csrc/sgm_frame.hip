@@ -270,8 +270,10 @@ int bm_frame(sgm_handle *h, FrameIO f, hipStream_t st) {
     if (f.raw && f.raw != h->d_disp[0])  // (the host API passes d_disp[0] itself)
         HIPCHK(h, hipMemcpyAsync(f.raw, h->d_disp[0], (size_t)g.H * g.W * sizeof(uint16_t),
                                  hipMemcpyDeviceToDevice, st));
-    if (h->p.post_filter) return sgm::post_filter(h, f.out, f.out_pitch, st);
-    return SGM_OK;
+    if (h->p.post_filter)
+        if (int rc = sgm::post_filter(h, f.out, f.out_pitch, st)) return rc;
+    // (sgm_set_fill: the hole filling after BM's own post_filter call)
+    return h->fill_mode ? sgm::fill_frame(h, f.out, f.out_pitch, st) : SGM_OK;
 }
 
 // The slanted-tile schedule of the aggregation (DESIGN.md "Slanted tiles"),
@@ -450,7 +452,8 @@ int cost_stage(sgm_handle *h, FrameIO f, hipStream_t st, bool *have_c) {
     return SGM_OK;
 }
 
-// post_filter and LKRefine at the end of a frame (SGM.cpp:821-824)
+// post_filter and LKRefine at the end of a frame (SGM.cpp:821-824); on a handle with fill set
+// (sgm_set_fill) the hole filling after them, the frame's last map stage
 int finish_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     int rc;
     // with LKRefine next, the post filter's last kernel writes LKRefine's
@@ -458,9 +461,10 @@ int finish_frame(sgm_handle *h, const FrameIO &f, hipStream_t st) {
     const bool pf_to_lk = h->p.post_filter && h->p.lk_refine;
     if (h->p.post_filter && (rc = sgm::post_filter(h, f.out, f.out_pitch, st, pf_to_lk)))  // SGM.cpp:821
         return rc;
-    if (h->p.lk_refine)  // SGM.cpp:824
-        return sgm::lk_refine(h, f.left, f.right, f.pitch, f.out, f.out_pitch, st, pf_to_lk);
-    return SGM_OK;
+    if (h->p.lk_refine &&  // SGM.cpp:824
+        (rc = sgm::lk_refine(h, f.left, f.right, f.pitch, f.out, f.out_pitch, st, pf_to_lk)))
+        return rc;
+    return h->fill_mode ? sgm::fill_frame(h, f.out, f.out_pitch, st) : SGM_OK;
 }
 
 // The views' roles for a frame's maps.  Returns direct_out: one view with a dense output map, whose

@@ -107,6 +107,11 @@ struct sgm_handle {
     float *d_rp_xyz;      //   the frame's products (null: not asked for): rows x cols x 3 f32,
     float *d_rp_depth;    //   rows x cols f32,
     uint16_t *d_rp_d16;   //   rows x cols u16
+    int fill_mode;        // sgm_set_fill: SGM_FILL_OFF, or the hole filling every frame ends its maps with
+                          //   (sgm_fill.hip)
+    float *d_fill_planes; //   its scratch (null: off): six rows x cols planes of directional candidates,
+    uint8_t *d_fill_mask; //   and the rows x cols fill mask of the last filled map
+    bool fill_mask_valid; //   a fill has written the mask since the scratch was allocated
     uint8_t *h_pin;       // pinned host staging for sgm_process (allocated on first use)
     size_t h_pin_bytes;
     char err[512];
@@ -357,4 +362,11 @@ int slant_cus();
 // sgm_reproject.hip: the frame's last launch on a handle with reprojection set
 // (the products of the frame's map into the handle's buffers)
 int reproject_frame(sgm_handle *h, const float *d_map, int pitch, hipStream_t st);
+// sgm_fill.hip: the hole filling, two launches in place on a true-disparity map:
+// fill_frame as the frame's last map stage on a handle with fill set (the right view's map is the
+// handle's d_sub[1], the mask the handle's); fill_map with the right view's map by row and column
+// strides in elements (SGM_FILL_INTERPOLATE; else not read) and the mask's destination
+int fill_frame(sgm_handle *h, float *d_map, int pitch, hipStream_t st);
+int fill_map(sgm_handle *h, float *d_map, int pitch, const float *d_right, long long rs, long long cs, int mode,
+             uint8_t *d_mask, int mask_pitch, hipStream_t st);
 }  // namespace sgm

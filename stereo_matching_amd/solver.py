@@ -71,7 +71,7 @@ class SGM:
                  post_filter_launches: int = 0, confidence: bool = False, min_disp: int = 0,
                  input_size=None, rectify=None, input_format: str = "gray8", reproject=None,
                  cost: str = "census", window=None, volume_filter=None, weighted: bool = False,
-                 _solver: int = _capi.SGM_SOLVER_SGM):
+                 fill: str = "off", _solver: int = _capi.SGM_SOLVER_SGM):
         self._lib = lib()
         # cost ("census" | "sad" | "ssd" | "ct"): the matching cost of every frame
         # (set_cost): the 7x9 census, or the reference's SAD / SSD window cost or
@@ -128,6 +128,7 @@ class SGM:
         self._lr = np.full((self.rows, self.cols), self.invalid_disp, np.float32)
         self._raw = np.zeros((self.rows, self.cols), np.uint16)
         self._final = None
+        self._filled = False  # set_fill: frames return the filled map
         # post_filter_launches: the median fill's fixed launch budget
         # (set_post_filter_launches); 0 = the adaptive, host-synchronised fill
         # confidence: every frame also keeps its per-pixel uniqueness ratio
@@ -173,6 +174,10 @@ class SGM:
             # volume frame (aggregate(), SAD / SSD frames; set_volume_filter); None: off
             if volume_filter is not None:
                 self.set_volume_filter(*volume_filter)
+            # fill ("off" | "background" | "interpolate"): every frame ends its maps with the
+            # occlusion-aware hole filling (set_fill)
+            if fill != "off":
+                self.set_fill(fill)
         except Exception:
             self.close()
             raise
@@ -227,7 +232,8 @@ class SGM:
                                     self.cols, _ptr(out), self.cols, _ptr(raw)),
               self._h)
         self._raw = raw
-        if self.params.post_filter or self.params.lk_refine:  # sgm_process returned the final map
+        # (with fill set the frame's map is filled, its last map stage: the final map)
+        if self.params.post_filter or self.params.lk_refine or self._filled:  # sgm_process returned the final map
             self._final, self._lr = out, None
         else:
             self._final, self._lr = None, out
@@ -860,10 +866,88 @@ class SGM:
 
     def get_disp(self) -> np.ndarray:
         """Post-filtered disparity (inc/Solver.h:36: filtered_disp after
-        post_filter, Solver.cpp:600-649), computed on the GPU; invalid = D+1."""
+        post_filter, Solver.cpp:600-649), computed on the GPU; invalid = D+1.
+        On a handle with fill set: fill(post_filter(lr)), against the last
+        frame's right view (right=None)."""
         if self._final is None:
-            self._final = self.post_filter(self._lr)
+            f = self.post_filter(self._lr)
+            self._final = f if self.fill == "off" else self.fill_disp(f)[0]
         return self._final
+
+    # ------------------------------------------------------- hole filling
+    @staticmethod
+    def _fill_code(mode) -> int:
+        if isinstance(mode, str):
+            if mode not in _capi.FILL_MODES:
+                raise ValueError(f"fill must be one of {sorted(_capi.FILL_MODES)}, got {mode!r}")
+            return _capi.FILL_MODES[mode]
+        return int(mode)
+
+    def set_fill(self, mode: str) -> None:
+        """sgm_set_fill: "off" (the default), "background" or "interpolate":
+        every later frame -- process(), process_device(), aggregate(), of any
+        cost and schedule -- fills the invalid pixels of its final map as its
+        last map stage, after post_filter and LKRefine and before the
+        reprojection (Hirschmueller 2008, 2.6).  Each invalid
+        pixel takes one of the first valid values of the unfilled map along its
+        8 rays: "background" the second lowest; "interpolate" classifies it
+        against the frame's right view first, occlusions take the second
+        lowest and mismatches the upper median.  get_fill_mask() tells which
+        pixels are inferred.  "interpolate" needs a two-view SGM handle; BM
+        and one-view handles serve "background"; view="right" handles raise
+        SGMError.  Allocates 25 bytes per pixel ("off" frees them); waits for
+        the handle's work; not inside stream capture; re-capture graphs."""
+        check(self._lib.sgm_set_fill(self._h, self._fill_code(mode)), self._h)
+        self._filled = self._fill_code(mode) != 0
+
+    @property
+    def fill(self) -> str:
+        """sgm_get_fill, by name."""
+        m = ctypes.c_int()
+        check(self._lib.sgm_get_fill(self._h, ctypes.byref(m)), self._h)
+        return {v: n for n, v in _capi.FILL_MODES.items()}[m.value]
+
+    def fill_disp(self, disp, right=None, mode=None):
+        """sgm_stage_fill: (filled copy, uint8 fill mask) of a rows x cols
+        true-disparity map, on a handle whose fill is set (an aux_only handle
+        with the same min_disp included).  mode: "background" or
+        "interpolate" (None: the handle's own); right: the right view's rows x
+        cols map for "interpolate" (None: this handle's last frame's right
+        view, two-view handles only).  Mask: 0 measured, 1 filled as
+        occlusion, 2 filled as mismatch, 3 still invalid.  Synchronous."""
+        f = np.array(disp, dtype=np.float32, copy=True, order="C")
+        if f.shape != (self.rows, self.cols):
+            raise ValueError(f"disp: expected shape {(self.rows, self.cols)}, got {f.shape}")
+        r = None
+        if right is not None:
+            r = np.ascontiguousarray(right, dtype=np.float32)
+            if r.shape != f.shape:
+                raise ValueError(f"right: expected shape {(self.rows, self.cols)}, got {r.shape}")
+        mask = np.empty((self.rows, self.cols), np.uint8)
+        code = self._fill_code(self.fill if mode is None else mode)
+        check(self._lib.sgm_stage_fill(self._h, _ptr(f), _ptr(r), code, _ptr(mask)), self._h)
+        return f, mask
+
+    def fill_device(self, d_disp: int, *, d_right: int = 0, mode=None, d_mask: int = 0,
+                    pitch: int | None = None, right_pitch: int | None = None,
+                    mask_pitch: int | None = None, stream: int | None = None) -> None:
+        """In place on a device map (sgm_fill_device: two launches, enqueue
+        only, capturable); d_right = 0: this handle's last frame's right view;
+        d_mask = 0: the handle's own mask (get_fill_mask()); pitches in
+        elements.  hipStreamLegacy (stream=0) is refused."""
+        code = self._fill_code(self.fill if mode is None else mode)
+        check(self._lib.sgm_fill_device(
+            self._h, ctypes.c_void_p(d_disp or None), self.cols if pitch is None else pitch,
+            ctypes.c_void_p(d_right or None), self.cols if right_pitch is None else right_pitch, code,
+            ctypes.c_void_p(d_mask or None), self.cols if mask_pitch is None else mask_pitch,
+            _stream(stream)), self._h)
+
+    def get_fill_mask(self) -> np.ndarray:
+        """The fill mask of the last filled frame: rows x cols uint8, a host
+        copy (sgm_stage_fill_mask)."""
+        out = np.empty((self.rows, self.cols), np.uint8)
+        check(self._lib.sgm_stage_fill_mask(self._h, _ptr(out)), self._h)
+        return out
 
     def get_lr_disp(self) -> np.ndarray:
         """Sub-pixel disparity after the LR check (SGM.cpp:803-818)."""
@@ -1024,12 +1108,13 @@ class BM(SGM):
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  blur: bool = True, uniqueness: float = 0.7, sky_detect: bool = False,
                  post_filter_launches: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8", reproject=None, window=None, weighted: bool = False):
+                 input_format: str = "gray8", reproject=None, window=None, weighted: bool = False,
+                 fill: str = "off"):
         super().__init__(h, w, s, d, device=device, blur=blur, views=1, uniqueness=uniqueness,
                          post_filter=True, sky_detect=sky_detect,
                          post_filter_launches=post_filter_launches, input_size=input_size,
                          rectify=rectify, input_format=input_format, reproject=reproject,
-                         window=window, weighted=weighted, _solver=_capi.SGM_SOLVER_BM)
+                         window=window, weighted=weighted, fill=fill, _solver=_capi.SGM_SOLVER_BM)
 
 
 class GPU_SGM(SGM):
@@ -1043,11 +1128,12 @@ class GPU_SGM(SGM):
 
     def __init__(self, h: int, w: int, s: int = 1, d: int = 128, *, device: int = 0,
                  post_filter_launches: int = 0, min_disp: int = 0, input_size=None, rectify=None,
-                 input_format: str = "gray8", reproject=None, window=None, weighted: bool = False):
+                 input_format: str = "gray8", reproject=None, window=None, weighted: bool = False,
+                 fill: str = "off"):
         super().__init__(h, w, s, d, device=device, views=1, post_filter=True,
                          post_filter_launches=post_filter_launches, min_disp=min_disp,
                          input_size=input_size, rectify=rectify, input_format=input_format,
-                         reproject=reproject, window=window, weighted=weighted)
+                         reproject=reproject, window=window, weighted=weighted, fill=fill)
 
 
 # sgm_camera_q without a handle: the pinhole Q of a camera, 4 x 4 float64
