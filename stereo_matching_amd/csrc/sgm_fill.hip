@@ -169,11 +169,9 @@ using namespace sgm;
 
 namespace {
 
-size_t fill_plane_floats(const sgm_handle *h) { return (size_t)kFillPlanes * h->g.H * h->g.W; }
-
 void free_fill(sgm_handle *h) {
-    dfree(h, &h->d_fill_planes, fill_plane_floats(h));
-    dfree(h, &h->d_fill_mask, (size_t)h->g.H * h->g.W);
+    dfree(h, &h->d_fill_planes);
+    dfree(h, &h->d_fill_mask);
     h->fill_mask_valid = false;
 }
 
@@ -257,12 +255,11 @@ int sgm_set_fill(sgm_handle *h, int mode) {
         if (mode == kFillOff) {
             free_fill(h);
         } else if (!h->d_fill_planes) {
-            int rc = dalloc(h, &h->d_fill_planes, fill_plane_floats(h));
-            if (!rc) rc = dalloc(h, &h->d_fill_mask, (size_t)h->g.H * h->g.W);
-            if (rc) {
-                free_fill(h);
-                return rc;
-            }
+            const size_t npx = (size_t)h->g.H * h->g.W;
+            Ledger::Group scratch(h->mem);
+            if (int rc = dalloc(h, &h->d_fill_planes, kFillPlanes * npx)) return rc;
+            if (int rc = dalloc(h, &h->d_fill_mask, npx)) return rc;
+            scratch.commit();
         }
         h->fill_mode = mode;
         return SGM_OK;
@@ -316,19 +313,16 @@ int sgm_stage_fill(sgm_handle *h, float *disp, const float *right, int mode, uin
     if (!disp) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_fill: NULL map");
     if (!h->d_fill_planes)
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_fill: the handle has no fill scratch (sgm_set_fill)");
-    DeviceGuard guard(h->device);
     const size_t npx = (size_t)h->g.H * h->g.W;
-    {  // staging: the map in d_out, the right view's in the post filter's working map (dead between calls)
-        StreamScope scope(h, nullptr);
-        HIPCHK(h, hipMemcpyAsync(h->d_out, disp, npx * sizeof(float), hipMemcpyHostToDevice, h->st));
-        if (right) HIPCHK(h, hipMemcpyAsync(h->d_pf_work, right, npx * sizeof(float), hipMemcpyHostToDevice, h->st));
-    }
-    if (int rc = sgm_fill_device(h, h->d_out, h->g.W, right ? h->d_pf_work : nullptr, h->g.W, mode, nullptr, 0, nullptr))
-        return rc;
-    HIPCHK(h, hipMemcpyAsync(disp, h->d_out, npx * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    if (mask) HIPCHK(h, hipMemcpyAsync(mask, h->d_fill_mask, npx, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
+    Staging s(h);
+    // staging: the map in d_out, the right view's in the post filter's working map (dead between calls)
+    s.up(h->d_out, disp, npx * sizeof(float));
+    if (right) s.up(h->d_pf_work, right, npx * sizeof(float));
+    const float *d_right = right ? h->d_pf_work : nullptr;
+    s.run([&] { return sgm_fill_device(h, h->d_out, h->g.W, d_right, h->g.W, mode, nullptr, 0, nullptr); });
+    s.down(disp, h->d_out, npx * sizeof(float));
+    if (mask) s.down(mask, h->d_fill_mask, npx);
+    return s.finish();
 }
 
 int sgm_get_fill_mask(sgm_handle *h, const uint8_t **d_mask, int *pitch) {
@@ -347,11 +341,9 @@ int sgm_stage_fill_mask(sgm_handle *h, uint8_t *mask) {
     const uint8_t *d_mask = nullptr;
     int pitch = 0;
     if (int rc = sgm_get_fill_mask(h, &d_mask, &pitch)) return rc;
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    HIPCHK(h, hipMemcpyAsync(mask, d_mask, (size_t)h->g.H * h->g.W, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
+    Staging s(h);
+    s.down(mask, d_mask, (size_t)h->g.H * h->g.W);
+    return s.finish();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // sgm_handle.h -- the handle behind include/sgm_hip.h and the host helpers
-// every function that works on it uses: shared by the C-ABI (sgm_capi.hip, and
-// sgm_input.hip for the input stage) and the frame schedules (sgm_frame.hip).
+// every function that works on it uses: shared by the C-ABI (sgm_create.hip,
+// sgm_capi.hip, sgm_stages.hip, and sgm_input.hip for the input stage) and the frame schedules (sgm_frame.hip).
 // The handle holds the plan sgm_create made for it (sgm_plan.h: the schedule
 // of its frames) once, as `plan`.
 // Host-only; not part of the public interface.
@@ -9,9 +9,9 @@
 #include "../../include/sgm_hip.h"
 #include "sgm_input_stage.h"
 #include "sgm_internal.h"
+#include "sgm_ledger.h"
 #include "sgm_plan.h"
 
-#include <algorithm>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -21,7 +21,7 @@ using sgm::Geom;
 using sgm::SweepArgs;
 using sgm::vol_elems;
 
-struct sgm_handle {
+struct __attribute__((visibility("hidden"))) sgm_handle {  // (its inline members stay out of the exported symbols)
     sgm_params p;
     sgm::HandlePlan plan; // the schedule of the handle's frames (plan_handle, sgm_plan.h)
     Geom g;               // plan.g
@@ -30,8 +30,8 @@ struct sgm_handle {
                           // filter, point cloud: valid <= D+m-1, invalid D+m+1)
     int device;
     int nviews;           // plan.nviews
-    size_t bytes;         // of the device allocations below
-    std::vector<void *> allocs;  // every live dalloc (free_all frees these; dfree removes one)
+    sgm::Ledger mem{[](void **p, size_t n) { return (int)hipMalloc(p, n); }, [](void *p) { (void)hipFree(p); }};
+                          // every live dalloc and its size (sgm_device_bytes: their sum), in device memory
     hipStream_t st;      // the handle's own stream (host API, stages)
     hipEvent_t ev_pf;     // the post filter's convergence readback
     hipEvent_t ev_last;   // the end of the last call's work on last_st (StreamScope)
@@ -46,7 +46,7 @@ struct sgm_handle {
     uint32_t *d_map[2];   //   each view's packed map, two words per full-size pixel (sgm_rectify_maps.h;
                           //   aux_only handles: the maps alone, for sgm_remap_device)
     std::vector<uint8_t> valid[2];  //   each view's valid mask (host, full size, dense)
-    size_t raw_bytes;     // bytes of each d_raw (0: none): fit_input_buffers, sgm_input.hip
+    size_t raw_bytes;     // bytes of each d_raw (0: none): what fit_input_buffers compares, sgm_input.hip
     uint8_t *d_sky[2];    // working-grid sky masks (host API / stages)
     uint64_t *d_ct[2];    // census words
     int min_disp;         // sgm_set_min_disp: index d of the volumes stands for disparity min_disp + d
@@ -186,9 +186,10 @@ inline int set_err(sgm_handle *h, int code, const char *fmt, ...) {
                            __LINE__);                                                        \
     } while (0)
 
-// Waits for the last call's work (sgm_capi.hip; kept out of the library's
-// exported symbols).
+// sgm_capi.hip, shared by the C-ABI's files and kept out of the library's exported symbols: the
+// wait for the last call's work; a frame's give-up (hang guard, unproven fill) reported and cleared.
 __attribute__((visibility("hidden"))) int wait_last(sgm_handle *h);
+__attribute__((visibility("hidden"))) int check_frame_err(sgm_handle *h);
 
 // What every setter that reallocates buffers does after its argument checks:
 // refuse inside a stream capture (`fn`: the setter's name, for the message),
@@ -206,37 +207,63 @@ int change_setting(sgm_handle *h, const char *fn, bool unchanged, F &&apply) {
     return apply();
 }
 
-// A hipMallocAsync temporary of the stages: freed on its stream when the
-// scope ends, on every return path.
-template <typename T>
-struct StreamTemp {
-    T *p = nullptr;
-    hipStream_t st;
-    explicit StreamTemp(hipStream_t stream) : st(stream) {}
-    ~StreamTemp() {
-        if (p) (void)hipFreeAsync(p, st);
+// STAGE_HIP(s, call): a HIP call as a step of the Staging `s`, its failure reported as HIPCHK's.
+#define STAGE_HIP(s, expr) (s).run([&]() -> int { HIPCHK((s).h, expr); return SGM_OK; })
+
+// The host round trip of a sgm_stage_* function: the device guard, the scope on the handle's own
+// stream (a _device call made inside opens its own on the same stream: intended, it orders nothing
+// anew), uploads, stream-ordered temporaries (freed on every return path), the stage's work,
+// downloads, the final synchronise.  The first error sticks: later steps are skipped, finish() returns it.
+struct __attribute__((visibility("hidden"))) Staging {
+    sgm_handle *h;
+    DeviceGuard guard;
+    StreamScope scope;
+    int rc = SGM_OK;
+    std::vector<void *> temps;  // hipMallocAsync'ed
+    explicit Staging(sgm_handle *handle) : h(handle), guard(handle->device), scope(handle, nullptr) {}
+    ~Staging() { for (void *p : temps) (void)hipFreeAsync(p, h->st); }
+    // the stage's work: a _device call or another step that returns an rc, with h->err its own
+    template <typename F>
+    void run(F &&work) { if (!rc) rc = work(); }
+    // `count` elements that live until the round trip ends (null after an error)
+    template <typename T>
+    T *temp(size_t count) {
+        void *p = nullptr;
+        STAGE_HIP(*this, hipMallocAsync(&p, count * sizeof(T), h->st));
+        if (p) temps.push_back(p);
+        return (T *)p;
+    }
+    void up(void *d_dst, const void *src, size_t bytes) {
+        STAGE_HIP(*this, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, h->st));
+    }
+    // rows of row_bytes, `pitch` apart on the host, dense on the device
+    void up_rows(void *d_dst, const void *src, size_t row_bytes, size_t rows, size_t pitch) {
+        STAGE_HIP(*this, hipMemcpy2DAsync(d_dst, row_bytes, src, pitch, row_bytes, rows, hipMemcpyHostToDevice, h->st));
+    }
+    void down(void *dst, const void *d_src, size_t bytes) {
+        STAGE_HIP(*this, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, h->st));
+    }
+    void sync() { STAGE_HIP(*this, hipStreamSynchronize(h->st)); }
+    int finish() {
+        if (rc) (void)hipStreamSynchronize(h->st);  // (what was enqueued before the error still reads host memory)
+        sync();
+        return rc;
     }
 };
 
+// count elements of device memory on the handle's ledger (0: null, nothing allocated)
 template <typename T>
 int dalloc(sgm_handle *h, T **p, size_t count) {
-    *p = nullptr;
-    if (count == 0) return SGM_OK;
-    HIPCHK(h, hipMalloc((void **)p, count * sizeof(T)));
-    h->bytes += count * sizeof(T);
-    h->allocs.push_back(*p);
-    return SGM_OK;
+    const int e = h->mem.alloc((void **)p, count * sizeof(T));  // (hipMalloc's code; the text is HIPCHK's of it)
+    if (e == hipSuccess) return SGM_OK;
+    return set_err(h, e == hipErrorOutOfMemory ? SGM_ERR_OUT_OF_MEMORY : SGM_ERR_HIP, "hipMalloc((void **)p, count * sizeof(T)) "
+                   "failed: %s (%s:%d)", hipGetErrorString((hipError_t)e), __FILE__, __LINE__);
 }
 
-// Frees a dalloc of `count` elements and nulls the pointer (null: nothing).
+// Frees a dalloc and nulls the pointer (null: nothing).
 template <typename T>
-void dfree(sgm_handle *h, T **p, size_t count) {
-    if (!*p) return;
-    (void)hipFree(*p);
-    auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
-    if (it != h->allocs.end()) h->allocs.erase(it);
-    h->bytes -= count * sizeof(T);
-    *p = nullptr;
+void dfree(sgm_handle *h, T **p) {
+    h->mem.free((void **)p);
 }
 
 // The profile names of the two launches sgm_set_weighted changes: the masked

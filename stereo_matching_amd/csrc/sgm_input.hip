@@ -12,9 +12,8 @@ namespace {
 
 // Frees the maps and the masks and switches the remap off (the images follow in fit_input_buffers).
 void rectify_free_maps(sgm_handle *h) {
-    const size_t nfull = (size_t)h->p.height * h->p.width;
     for (int v = 0; v < 2; ++v) {
-        dfree(h, &h->d_map[v], 2 * nfull);
+        dfree(h, &h->d_map[v]);
         std::vector<uint8_t>().swap(h->valid[v]);
     }
     h->in.rc_rows = h->in.rc_cols = 0;
@@ -31,20 +30,19 @@ int fit_input_buffers(sgm_handle *h) {
     int rc = SGM_OK;
     h->rs_valid = false;
     for (int v = 0; v < 2 && !rc; ++v) {
-        if (!staged) dfree(h, &h->d_rs[v], nfull);
+        if (!staged) dfree(h, &h->d_rs[v]);
         else if (!h->d_rs[v]) rc = dalloc(h, &h->d_rs[v], nfull);
     }
     if (!rc && nraw != h->raw_bytes) {
-        for (int v = 0; v < 2; ++v) dfree(h, &h->d_raw[v], h->raw_bytes);
+        for (int v = 0; v < 2; ++v) dfree(h, &h->d_raw[v]);
         h->raw_bytes = 0;
         for (int v = 0; v < 2 && !rc; ++v) rc = dalloc(h, &h->d_raw[v], nraw);
         if (!rc) h->raw_bytes = nraw;
     }
-    if (rc) {
-        // (dalloc nulls the pointer it failed on; raw_bytes is still the freed size's 0 or the old one)
+    if (rc) {  // (not a group's rollback: what the handle held before goes too)
         for (int v = 0; v < 2; ++v) {
-            dfree(h, &h->d_raw[v], h->raw_bytes ? h->raw_bytes : nraw);
-            dfree(h, &h->d_rs[v], nfull);
+            dfree(h, &h->d_raw[v]);
+            dfree(h, &h->d_rs[v]);
         }
         h->raw_bytes = 0;
         rectify_free_maps(h);
@@ -94,37 +92,9 @@ int download_image(sgm_handle *h, const StageImage &t, int view, uint8_t *img) {
     const uint8_t *d_img = nullptr;
     int pitch = 0;
     if (int rc = get_image(h, t, view, &d_img, &pitch)) return rc;
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    HIPCHK(h, hipMemcpyAsync(img, d_img, (size_t)h->p.height * h->p.width, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
-}
-
-// The host round trip of sgm_stage_resize / _remap / _gray: the source (rows of row_bytes, pitch
-// apart) into a stream-ordered temporary, the stage's _device call (`device`, given the source and
-// the result on the device), n_out bytes of the result into dst, a sync.  The result lands in
-// d_out (the resize's and the remap's: d_in[0]) or, d_out null, in a second temporary (any size).
-template <typename F>
-int host_round_trip(sgm_handle *h, const uint8_t *src, int rows, size_t row_bytes, int pitch, uint8_t *d_out,
-                    size_t n_out, uint8_t *dst, F &&device) {
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    int rc;
-    {
-        StreamTemp<uint8_t> d_src(h->st), d_tmp(h->st);
-        HIPCHK(h, hipMallocAsync((void **)&d_src.p, row_bytes * rows, h->st));
-        if (!d_out) {
-            HIPCHK(h, hipMallocAsync((void **)&d_tmp.p, n_out, h->st));
-            d_out = d_tmp.p;
-        }
-        HIPCHK(h, hipMemcpy2DAsync(d_src.p, row_bytes, src, (size_t)pitch, row_bytes, (size_t)rows,
-                                   hipMemcpyHostToDevice, h->st));
-        rc = device(d_src.p, d_out);
-        if (!rc) HIPCHK(h, hipMemcpyAsync(dst, d_out, n_out, hipMemcpyDeviceToHost, h->st));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return rc;
+    Staging s(h);
+    s.down(img, d_img, (size_t)h->p.height * h->p.width);
+    return s.finish();
 }
 
 }  // namespace
@@ -196,11 +166,12 @@ int sgm_stage_resize(sgm_handle *h, const uint8_t *src, int src_rows, int src_co
     if (!src || !dst) return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resize: NULL pointer");
     if (!resize_src_ok(src_rows, src_cols, src_pitch, why, sizeof(why)))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_resize: %s", why);
-    return host_round_trip(h, src, src_rows, (size_t)src_cols, src_pitch, h->d_in[0],
-                           (size_t)h->p.height * h->p.width, dst, [&](const uint8_t *d_src, uint8_t *d_dst) {
-                               return sgm_resize_device(h, d_src, src_rows, src_cols, src_cols, d_dst,
-                                                        h->p.width, h->st);
-                           });
+    Staging s(h);  // (the source in a temporary, the result in d_in[0])
+    uint8_t *d_src = s.temp<uint8_t>((size_t)src_rows * src_cols);
+    s.up_rows(d_src, src, src_cols, src_rows, src_pitch);
+    s.run([&] { return sgm_resize_device(h, d_src, src_rows, src_cols, src_cols, h->d_in[0], h->p.width, h->st); });
+    s.down(dst, h->d_in[0], (size_t)h->p.height * h->p.width);
+    return s.finish();
 }
 
 // ---- rectification
@@ -231,6 +202,7 @@ int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_
         } catch (const std::bad_alloc &) {
             rc = set_err(h, SGM_ERR_OUT_OF_MEMORY, "sgm_set_rectify: out of host memory");
         }
+        Ledger::Group both(h->mem);
         for (int v = 0; v < 2 && !rc; ++v) {
             rectify_convert(maps[2 * v], maps[2 * v + 1], map_pitch, h->p.height, h->p.width, src_rows,
                             src_cols, packed.data(), h->valid[v].data());
@@ -239,11 +211,11 @@ int sgm_set_rectify(sgm_handle *h, int src_rows, int src_cols, const float *map_
                 hipSuccess)
                 rc = set_err(h, SGM_ERR_HIP, "sgm_set_rectify: the upload of the packed map failed");
         }
-        if (rc) {  // (off again: the handle runs as before)
-            rectify_free_maps(h);
-            (void)fit_input_buffers(h);
+        if (rc) {  // (off again: the group frees the maps, and the handle runs as before)
+            for (auto &mask : h->valid) std::vector<uint8_t>().swap(mask);
             return rc;
         }
+        both.commit();
         // (an aux_only handle runs no frames: it keeps the maps for sgm_remap_device alone)
         h->in.rc_rows = src_rows;
         h->in.rc_cols = src_cols;
@@ -285,10 +257,12 @@ int sgm_stage_remap(sgm_handle *h, int view, const uint8_t *src, int src_pitch, 
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: no maps are set (sgm_set_rectify)");
     if (!rectify_call_ok(view, src_pitch, h->in.rc_cols, h->p.width, h->p.width, why, sizeof(why)))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_remap: %s", why);
-    return host_round_trip(h, src, h->in.rc_rows, (size_t)h->in.rc_cols, src_pitch, h->d_in[0],
-                           (size_t)h->p.height * h->p.width, dst, [&](const uint8_t *d_src, uint8_t *d_dst) {
-                               return sgm_remap_device(h, view, d_src, h->in.rc_cols, d_dst, h->p.width, h->st);
-                           });
+    Staging s(h);  // (the source in a temporary, the result in d_in[0])
+    uint8_t *d_src = s.temp<uint8_t>((size_t)h->in.rc_rows * h->in.rc_cols);
+    s.up_rows(d_src, src, h->in.rc_cols, h->in.rc_rows, src_pitch);
+    s.run([&] { return sgm_remap_device(h, view, d_src, h->in.rc_cols, h->d_in[0], h->p.width, h->st); });
+    s.down(dst, h->d_in[0], (size_t)h->p.height * h->p.width);
+    return s.finish();
 }
 
 int sgm_get_rectified(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {
@@ -359,10 +333,12 @@ int sgm_stage_gray(sgm_handle *h, int fmt, const uint8_t *src, int rows, int col
     if (!gray_call_ok(fmt, rows, cols, src_pitch, cols, why, sizeof(why)))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_gray: %s", why);
     const size_t row = (size_t)cols * sgm::pix_bpp(fmt);
-    return host_round_trip(h, src, rows, row, src_pitch, nullptr, (size_t)rows * cols, dst,
-                           [&](const uint8_t *d_src, uint8_t *d_dst) {
-                               return sgm_gray_device(h, fmt, d_src, rows, cols, (int)row, d_dst, cols, h->st);
-                           });
+    Staging s(h);  // (the source and the result, of any size, in temporaries)
+    uint8_t *d_src = s.temp<uint8_t>(row * rows), *d_dst = s.temp<uint8_t>((size_t)rows * cols);
+    s.up_rows(d_src, src, row, rows, src_pitch);
+    s.run([&] { return sgm_gray_device(h, fmt, d_src, rows, cols, (int)row, d_dst, cols, h->st); });
+    s.down(dst, d_dst, (size_t)rows * cols);
+    return s.finish();
 }
 
 int sgm_get_input_gray(sgm_handle *h, int view, const uint8_t **d_img, int *pitch) {

@@ -1,6 +1,6 @@
 // sgm_internal.h -- kernel launchers and their argument structs (one view
 // slot's cost stage: CostSlot; one view's aggregation roles: ViewRoles) shared
-// by the host side (sgm_capi.hip, sgm_frame.hip) and the kernel files.  Not
+// by the host side (the C-ABI files, sgm_frame.hip) and the kernel files.  Not
 // part of the public interface.
 #pragma once
 

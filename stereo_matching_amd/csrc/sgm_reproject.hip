@@ -199,9 +199,9 @@ int enqueue(sgm_handle *h, const float *d_disp, int pitch, float *d_xyz, int xyz
 
 // Frees the frame's products.
 void free_products(sgm_handle *h) {
-    dfree(h, &h->d_rp_xyz, product_elems(h, kReprojectXyz));
-    dfree(h, &h->d_rp_depth, product_elems(h, kReprojectDepth));
-    dfree(h, &h->d_rp_d16, product_elems(h, kReprojectDepth16));
+    dfree(h, &h->d_rp_xyz);
+    dfree(h, &h->d_rp_depth);
+    dfree(h, &h->d_rp_d16);
     h->rp_valid = false;
 }
 
@@ -247,25 +247,17 @@ int sgm_set_reproject(sgm_handle *h, const sgm_reproject *r) {
         }
         // (an aux_only handle runs no frames: Q alone, for sgm_reproject_device)
         const int want = h->p.aux_only ? 0 : r->outputs;
-        // what is missing first, so that a failed allocation leaves the handle as it was
-        float *xyz = nullptr, *depth = nullptr;
-        uint16_t *d16 = nullptr;
+        // what is missing first, as one group, so that a failed allocation leaves the handle as it was
         int rc = SGM_OK;
-        if ((want & kReprojectXyz) && !h->d_rp_xyz) rc = dalloc(h, &xyz, product_elems(h, kReprojectXyz));
-        if (!rc && (want & kReprojectDepth) && !h->d_rp_depth) rc = dalloc(h, &depth, product_elems(h, kReprojectDepth));
-        if (!rc && (want & kReprojectDepth16) && !h->d_rp_d16) rc = dalloc(h, &d16, product_elems(h, kReprojectDepth16));
-        if (rc) {
-            dfree(h, &xyz, product_elems(h, kReprojectXyz));
-            dfree(h, &depth, product_elems(h, kReprojectDepth));
-            dfree(h, &d16, product_elems(h, kReprojectDepth16));
-            return rc;
-        }
-        if (xyz) h->d_rp_xyz = xyz;
-        if (depth) h->d_rp_depth = depth;
-        if (d16) h->d_rp_d16 = d16;
-        if (!(want & kReprojectXyz)) dfree(h, &h->d_rp_xyz, product_elems(h, kReprojectXyz));
-        if (!(want & kReprojectDepth)) dfree(h, &h->d_rp_depth, product_elems(h, kReprojectDepth));
-        if (!(want & kReprojectDepth16)) dfree(h, &h->d_rp_d16, product_elems(h, kReprojectDepth16));
+        Ledger::Group missing(h->mem);
+        if ((want & kReprojectXyz) && !h->d_rp_xyz) rc = dalloc(h, &h->d_rp_xyz, product_elems(h, kReprojectXyz));
+        if (!rc && (want & kReprojectDepth) && !h->d_rp_depth) rc = dalloc(h, &h->d_rp_depth, product_elems(h, kReprojectDepth));
+        if (!rc && (want & kReprojectDepth16) && !h->d_rp_d16) rc = dalloc(h, &h->d_rp_d16, product_elems(h, kReprojectDepth16));
+        if (rc) return rc;
+        missing.commit();
+        if (!(want & kReprojectXyz)) dfree(h, &h->d_rp_xyz);
+        if (!(want & kReprojectDepth)) dfree(h, &h->d_rp_depth);
+        if (!(want & kReprojectDepth16)) dfree(h, &h->d_rp_d16);
         h->rp = *r;
         h->rp_on = true;
         h->rp_valid = false;
@@ -299,26 +291,17 @@ int sgm_stage_reproject(sgm_handle *h, const float *disp, float *xyz, float *dep
     if (!reproject_call_ok(h->rp_on, disp != nullptr, W, xyz != nullptr, 3 * W, depth != nullptr, W,
                            depth16 != nullptr, W, W, why, sizeof(why)))
         return set_err(h, SGM_ERR_INVALID_ARG, "sgm_stage_reproject: %s", why);
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
     const size_t npx = (size_t)h->g.H * W;
-    int rc;
-    {
-        // staging: the map in d_out, the products in stream-ordered temporaries
-        StreamTemp<float> d_xyz(h->st), d_depth(h->st);
-        StreamTemp<uint16_t> d_d16(h->st);
-        if (xyz) HIPCHK(h, hipMallocAsync((void **)&d_xyz.p, 3 * npx * sizeof(float), h->st));
-        if (depth) HIPCHK(h, hipMallocAsync((void **)&d_depth.p, npx * sizeof(float), h->st));
-        if (depth16) HIPCHK(h, hipMallocAsync((void **)&d_d16.p, npx * sizeof(uint16_t), h->st));
-        HIPCHK(h, hipMemcpyAsync(h->d_out, disp, npx * sizeof(float), hipMemcpyHostToDevice, h->st));
-        rc = enqueue(h, h->d_out, W, d_xyz.p, 3 * W, d_depth.p, W, d_d16.p, W, h->st);
-        if (!rc && xyz) HIPCHK(h, hipMemcpyAsync(xyz, d_xyz.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, h->st));
-        if (!rc && depth) HIPCHK(h, hipMemcpyAsync(depth, d_depth.p, npx * sizeof(float), hipMemcpyDeviceToHost, h->st));
-        if (!rc && depth16)
-            HIPCHK(h, hipMemcpyAsync(depth16, d_d16.p, npx * sizeof(uint16_t), hipMemcpyDeviceToHost, h->st));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return rc;
+    Staging s(h);
+    // staging: the map in d_out, the products in stream-ordered temporaries
+    float *d_xyz = xyz ? s.temp<float>(3 * npx) : nullptr, *d_depth = depth ? s.temp<float>(npx) : nullptr;
+    uint16_t *d_d16 = depth16 ? s.temp<uint16_t>(npx) : nullptr;
+    s.up(h->d_out, disp, npx * sizeof(float));
+    s.run([&] { return enqueue(h, h->d_out, W, d_xyz, 3 * W, d_depth, W, d_d16, W, h->st); });
+    if (xyz) s.down(xyz, d_xyz, 3 * npx * sizeof(float));
+    if (depth) s.down(depth, d_depth, npx * sizeof(float));
+    if (depth16) s.down(depth16, d_d16, npx * sizeof(uint16_t));
+    return s.finish();
 }
 
 int sgm_get_reprojected(sgm_handle *h, int which, const void **d_img, int *pitch) {
@@ -333,12 +316,9 @@ int sgm_stage_reprojected(sgm_handle *h, int which, void *img) {
     const void *d_img = nullptr;
     int pitch = 0;
     if (int rc = get_product(h, "sgm_stage_reprojected", which, &d_img, &pitch)) return rc;
-    DeviceGuard guard(h->device);
-    StreamScope scope(h, nullptr);
-    HIPCHK(h, hipMemcpyAsync(img, d_img, product_elems(h, which) * reproject_elem_bytes(which),
-                             hipMemcpyDeviceToHost, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    return SGM_OK;
+    Staging s(h);
+    s.down(img, d_img, product_elems(h, which) * reproject_elem_bytes(which));
+    return s.finish();
 }
 
 int sgm_camera_q(const sgm_camera *cam, double q[16]) {

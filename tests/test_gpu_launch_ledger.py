@@ -9,7 +9,7 @@ shape that reaches it.  The bit-exact tests pin what the launches compute;
 this one pins which launches run.
 
 The table was recorded from the library as it was before the schedules moved
-out of sgm_capi.hip (`python tests/test_gpu_launch_ledger.py` prints it);
+out of the C-ABI file, sgm_capi.hip (`python tests/test_gpu_launch_ledger.py` prints it);
 slant_v1_cost_h and per_view_v2 from the library as it was before the one- and
 two-view launchers became one per role.
 """

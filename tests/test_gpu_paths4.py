@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the 8-path schedules' launch classes a 4-path frame must not report
 EIGHT_PATH_CLASSES = ("stage_a", "stage_b", "stage_a_d", "stage_b_d2", "sweep_L8_acc", "slant_down",
                       "slant_up")
-# the 4-path schedule's one choice by size, forced either way (sgm_capi.hip
+# the 4-path schedule's one choice by size, forced either way (sgm_create.hip
 # sgm_create): 0 = the one-launch H pair, 1 = forward + two-wave
 # backward launches
 SWITCHES = ("SGM_P4_HPAIR",)

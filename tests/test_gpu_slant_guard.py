@@ -91,7 +91,7 @@ print(json.dumps({"base_slant": "slant_up" in base[1], "fb_slant": "slant_up" in
 
 @pytest.mark.gpu
 def test_slanted_schedule_falls_back_to_bands_without_memory():
-    # sgm_create (sgm_capi.hip): the slanted schedule's buffers failing to
+    # sgm_create (sgm_create.hip): the slanted schedule's buffers failing to
     # allocate (forced on the debug build) -> the banded schedule, same maps;
     # with SGM_SLANT=1 the failure is returned
     env = {**os.environ, "SGM_HIP_LIB": DBG}

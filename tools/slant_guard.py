@@ -2,7 +2,7 @@
 (sgm_slant.hip receiver wave, sgm_capi.hip sgm_check).
 
 Runs on the debug build of the library (stereo_matching_amd/
-libsgm_hip_slantdbg.so: the release objects plus sgm_slant/sgm_frame/sgm_capi built
+libsgm_hip_slantdbg.so: the release objects plus sgm_slant/sgm_frame/sgm_create built
 with -DSGM_SLANT_DEBUG), on a small two-view frame forced onto the slanted
 schedule (SGM_SLANT=1), and prints one JSON line:
 
