@@ -17,7 +17,7 @@ import functools
 import numpy as np
 
 from paths4_recipe import (IDS, SHAPES, aggregate, assert_bits_equal, census, cost_volume,  # noqa: F401
-                           make_inputs)
+                           make_inputs, masks)
 from stereo_matching_amd import synthetic
 
 FLT_MAX = np.float32(np.finfo(np.float32).max)
@@ -42,10 +42,12 @@ def ratio_of(S):
     return r
 
 
-def view_volumes(left, right, D, s, sky, paths):
-    """The aggregated volumes (S_left, S_right) of a pair."""
+def view_volumes(left, right, D, s, sky, paths, P1=10, P2=100, sky_l=None, sky_r=None):
+    """The aggregated volumes (S_left, S_right) of a pair; the sky mask `sky` serves both
+    views unless sky_l / sky_r give a view its own."""
     ctl, ctr = census(left, s), census(right, s)
-    return tuple(aggregate(cost_volume(ctl, ctr, D, s, v, sky), paths) for v in (0, 1))
+    return tuple(aggregate(cost_volume(ctl, ctr, D, s, v, mask), paths, P1, P2)
+                 for v, mask in enumerate(masks(sky, sky_l, sky_r)))
 
 
 def _frozen(arrs):

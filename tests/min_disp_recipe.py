@@ -25,7 +25,7 @@ import numpy as np
 
 import oracle
 from confidence_recipe import ratio_of
-from paths4_recipe import aggregate, assert_bits_equal, census, cost_volume  # noqa: F401
+from paths4_recipe import aggregate, assert_bits_equal, census, cost_volume, masks  # noqa: F401
 from stereo_matching_amd import synthetic
 
 # (h, w, D, m, s, kind, sky)
@@ -69,27 +69,30 @@ def shift_tables(ctl, ctr, k):
             np.ascontiguousarray(ctr[:, np.maximum(x - k, 0)]))
 
 
-def view_volumes(left, right, D, m, s, sky, paths):
+def view_volumes(left, right, D, m, s, sky, paths, P1=10, P2=100, sky_l=None, sky_r=None):
     """The aggregated index-space volumes (S_left, S_right)."""
     assert m % s == 0
     ctl, ctr = census(left, s), census(right, s)
     ctl_s, ctr_s = shift_tables(ctl, ctr, m // s)
-    return (aggregate(cost_volume(ctl, ctr_s, D, s, 0, sky), paths),
-            aggregate(cost_volume(ctl_s, ctr, D, s, 1, sky), paths))
+    sky_l, sky_r = masks(sky, sky_l, sky_r)
+    return (aggregate(cost_volume(ctl, ctr_s, D, s, 0, sky_l), paths, P1, P2),
+            aggregate(cost_volume(ctl_s, ctr, D, s, 1, sky_r), paths, P1, P2))
 
 
-def recipe(left, right, D, m, s=1, sky=None, paths=8, lk=False):
+def recipe(left, right, D, m, s=1, sky=None, paths=8, lk=False, P1=10, P2=100, uniq=0.7, lr_dis=1.0,
+           sky_l=None, sky_r=None):
     """The maps of oracle.process (same keys) in true disparity, plus "ratio" /
     "ratio_beta" (the confidence quotient) and, with lk, "lk" (LKRefine of
-    "final"); the same sky mask serves both views."""
+    "final"); the sky mask `sky` serves both views unless sky_l / sky_r give a
+    view its own."""
     out = {}
-    for S, sfx in zip(view_volumes(left, right, D, m, s, sky, paths), ("", "_beta")):
-        d = oracle.wta(S)
+    for S, sfx in zip(view_volumes(left, right, D, m, s, sky, paths, P1, P2, sky_l, sky_r), ("", "_beta")):
+        d = oracle.wta(S, uniq)
         f = oracle.subpixel(d, S)
         out["disp" + sfx] = d + m
         out["sub" + sfx] = (f + np.float32(m)).astype(np.float32)
         out["ratio" + sfx] = ratio_of(S)
-    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
+    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s, lr_dis)
     out["final"] = oracle.post_filter(out["lr"], D + m, s)
     if lk:
         out["lk"] = oracle.lk_refine(left[::s, ::s], right[::s, ::s], out["final"], D + m)

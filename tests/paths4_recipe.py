@@ -50,9 +50,9 @@ def cost_volume(ctl, ctr, D, s, view, sky):
     return oracle.vfilter(oracle.hfilter(c, 5 // s), 3 // s)
 
 
-def aggregate(cost, paths):
+def aggregate(cost, paths, P1=10, P2=100):
     """S of one view, float32, the reference's association order."""
-    L = [oracle.path(cost, k)[0] for k in range(paths)]
+    L = [oracle.path(cost, k, P1, P2)[0] for k in range(paths)]
     S = ((L[0] + L[1]) + L[2]) + L[3]
     if paths == 8:
         S = S + (((L[4] + L[5]) + L[6]) + L[7])
@@ -60,20 +60,26 @@ def aggregate(cost, paths):
     return S
 
 
-def view_maps(cost, paths):
-    S = aggregate(cost, paths)
-    disp = oracle.wta(S)
+def view_maps(cost, paths, P1=10, P2=100, uniq=0.7):
+    S = aggregate(cost, paths, P1, P2)
+    disp = oracle.wta(S, uniq)
     return disp, oracle.subpixel(disp, S)
 
 
-def recipe(left, right, D, s=1, sky=None, paths=4):
-    """The maps of oracle.process (same keys), for 4 or 8 paths; the same sky
-    mask serves both views."""
+def masks(sky, sky_l=None, sky_r=None):
+    """(left view's mask, right view's): `sky` serves both unless a view's own is given."""
+    return (sky if sky_l is None else sky_l), (sky if sky_r is None else sky_r)
+
+
+def recipe(left, right, D, s=1, sky=None, paths=4, P1=10, P2=100, uniq=0.7, lr_dis=1.0, sky_l=None, sky_r=None):
+    """The maps of oracle.process (same keys), for 4 or 8 paths; the sky mask
+    `sky` serves both views unless sky_l / sky_r give a view its own."""
     ctl, ctr = census(left, s), census(right, s)
+    sky_l, sky_r = masks(sky, sky_l, sky_r)
     out = {}
-    out["disp"], out["sub"] = view_maps(cost_volume(ctl, ctr, D, s, 0, sky), paths)
-    out["disp_beta"], out["sub_beta"] = view_maps(cost_volume(ctl, ctr, D, s, 1, sky), paths)
-    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D, s)
+    out["disp"], out["sub"] = view_maps(cost_volume(ctl, ctr, D, s, 0, sky_l), paths, P1, P2, uniq)
+    out["disp_beta"], out["sub_beta"] = view_maps(cost_volume(ctl, ctr, D, s, 1, sky_r), paths, P1, P2, uniq)
+    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D, s, lr_dis)
     out["final"] = oracle.post_filter(out["lr"], D, s)
     return out
 

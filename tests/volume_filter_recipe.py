@@ -32,14 +32,15 @@ def filtered(C, s=1, filters=H_BIT | V_BIT):
     return C
 
 
-def recipe(C, m=0, s=1, paths=8, filters=H_BIT | V_BIT):
+def recipe(C, m=0, s=1, paths=8, filters=H_BIT | V_BIT, P1=10, P2=100, uniq=0.7, lr_dis=1.0):
     """volume_recipe.recipe's maps of the raw left volume C with each view filtered on its own:
     "disp", "sub", "ratio", "sub_beta", "ratio_beta", "lr", "final"."""
     H, W, D = C.shape
     out = {}
-    out["disp"], out["sub"], out["ratio"] = vr.view_maps(filtered(C, s, filters), m, paths)
-    _, out["sub_beta"], out["ratio_beta"] = vr.view_maps(filtered(vr.derive_right(C, m, s), s, filters), m, paths)
-    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
+    out["disp"], out["sub"], out["ratio"] = vr.view_maps(filtered(C, s, filters), m, paths, P1, P2, uniq)
+    _, out["sub_beta"], out["ratio_beta"] = vr.view_maps(filtered(vr.derive_right(C, m, s), s, filters), m, paths,
+                                                         P1, P2, uniq)
+    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s, lr_dis)
     out["final"] = oracle.post_filter(out["lr"], D + m, s)
     return out
 

@@ -36,25 +36,25 @@ def unclamped(W, D, m=0, s=1):
     return np.arange(W)[:, None] + (np.arange(D)[None, :] + m) // s <= W - 1
 
 
-def view_maps(C, m, paths):
+def view_maps(C, m, paths, P1=10, P2=100, uniq=0.7):
     C = np.ascontiguousarray(C, np.float32)
     if paths == 8:
-        S = oracle.aggregate([oracle.path(C, k)[0] for k in range(8)])
+        S = oracle.aggregate([oracle.path(C, k, P1, P2)[0] for k in range(8)])
     else:
-        S = aggregate4(C, 4)
-    d = oracle.wta(S)
+        S = aggregate4(C, 4, P1, P2)
+    d = oracle.wta(S, uniq)
     f = oracle.subpixel(d, S)
     return d + m, (f + np.float32(m)).astype(np.float32), ratio_of(S)
 
 
-def recipe(C, m=0, s=1, paths=8):
+def recipe(C, m=0, s=1, paths=8, P1=10, P2=100, uniq=0.7, lr_dis=1.0):
     """Every map of the frame from C on, in true disparity: "disp", "sub", "ratio" (left view),
     "sub_beta", "ratio_beta" (the derived right view), "lr" and "final" (post-filtered)."""
     H, W, D = C.shape
     out = {}
-    out["disp"], out["sub"], out["ratio"] = view_maps(C, m, paths)
-    _, out["sub_beta"], out["ratio_beta"] = view_maps(derive_right(C, m, s), m, paths)
-    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
+    out["disp"], out["sub"], out["ratio"] = view_maps(C, m, paths, P1, P2, uniq)
+    _, out["sub_beta"], out["ratio_beta"] = view_maps(derive_right(C, m, s), m, paths, P1, P2, uniq)
+    out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s, lr_dis)
     out["final"] = oracle.post_filter(out["lr"], D + m, s)
     return out
 

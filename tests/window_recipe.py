@@ -18,7 +18,8 @@ import volume_recipe
 import weighted_recipe
 import window_cost_recipe as wc
 from min_disp_recipe import shift_tables
-from paths4_recipe import aggregate, assert_bits_equal, bits, cost_volume  # noqa: F401
+from confidence_recipe import ratio_of
+from paths4_recipe import aggregate, assert_bits_equal, bits, cost_volume, masks  # noqa: F401
 from window_cases import effective, working  # noqa: F401
 
 DEFAULT = (7, 9)
@@ -120,35 +121,42 @@ def bm_wta(cost, uniq=0.7):
 
 
 def recipe(left, right, D, window=DEFAULT, s=1, sky=None, paths=8, m=0, blur=True, views=2, cost="census",
-           solver="sgm", weighted=False, filters=(False, False)):
+           solver="sgm", weighted=False, filters=(False, False), P1=10, P2=100, uniq=0.7, lr_dis=1.0,
+           sky_l=None, sky_r=None, ratio=False):
     """The maps of a frame on a handle with sgm_set_window(window): oracle.process's keys, in
     true disparity (min_disp m).  cost "sad" | "ssd": the window cost volume through
     tests/volume_recipe.py, with `filters` (horizontal, vertical) through
     tests/volume_filter_recipe.py (5q).  solver "bm": "disp" (BM's raw winner-take-all) and
     "final" (its post_filter) only.  weighted: sgm_set_weighted's masked tables or weighted
-    volume (tests/weighted_recipe.py) in the place of the plain ones."""
+    volume (tests/weighted_recipe.py) in the place of the plain ones.  The sky mask `sky`
+    serves both views unless sky_l / sky_r give a view its own; ratio: census frames also
+    return "ratio" / "ratio_beta", the confidence quotient (the volume recipes always do)."""
+    sky_l, sky_r = masks(sky, sky_l, sky_r)
     if cost != "census":
         C = (weighted_recipe.volume if weighted else volume)(left, right, D, cost, window, s, m)
         if any(filters):
-            return volume_filter_recipe.recipe(C, m, s, paths, (1 if filters[0] else 0) | (2 if filters[1] else 0))
-        return volume_recipe.recipe(C, m, s, paths)
+            return volume_filter_recipe.recipe(C, m, s, paths, (1 if filters[0] else 0) | (2 if filters[1] else 0),
+                                               P1, P2, uniq, lr_dis)
+        return volume_recipe.recipe(C, m, s, paths, P1, P2, uniq, lr_dis)
     if solver == "bm":
         ctl, ctr = (frame_census(x, window, s, blur, True, weighted) for x in (left, right))
-        d = bm_wta(cost_volume(ctl, ctr, D, s, 0, sky))
+        d = bm_wta(cost_volume(ctl, ctr, D, s, 0, sky_l), uniq)
         return {"disp": d, "final": oracle.post_filter(d.astype(np.float32), D, s)}
     ctl, ctr = (frame_census(x, window, s, blur, False, weighted) for x in (left, right))
     ctl_s, ctr_s = shift_tables(ctl, ctr, m // s)
     out = {}
-    vols = [cost_volume(ctl, ctr_s, D, s, 0, sky)]
+    vols = [cost_volume(ctl, ctr_s, D, s, 0, sky_l)]
     if views == 2:
-        vols.append(cost_volume(ctl_s, ctr, D, s, 1, sky))
+        vols.append(cost_volume(ctl_s, ctr, D, s, 1, sky_r))
     for C, sfx in zip(vols, ("", "_beta")):
-        S = aggregate(C, paths)
-        d = oracle.wta(S)
+        S = aggregate(C, paths, P1, P2)
+        d = oracle.wta(S, uniq)
+        if ratio:
+            out["ratio" + sfx] = ratio_of(S)
         out["disp" + sfx] = d + m
         out["sub" + sfx] = (oracle.subpixel(d, S) + np.float32(m)).astype(np.float32)
     if views == 2:
-        out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s)
+        out["lr"] = oracle.lr_check(out["sub"], out["sub_beta"], D + m, s, lr_dis)
         out["final"] = oracle.post_filter(out["lr"], D + m, s)
     else:
         out["final"] = oracle.post_filter(out["sub"], D + m, s)
